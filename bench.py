@@ -10,6 +10,12 @@ resident in HBM: the 7 modality-subset ELBO passes, backward and Adam (problems.
 64x64 visual + tactile + 7-DoF pose, 256 samples per GPU (weak scaling: pure data parallel, gradients
 all-reduced over RCCL).  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config).  --full adds what takes runs of its own: the per-kernel HIP-event profile and the `roofline` object, the
+other fp32 arithmetic timed beside the line (`native_fp32` / `alt_arithmetic`) and the CPU baseline (`cpu_baseline`):
+    python bench.py --full
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (seeded inputs: two builds compare file by file).
+
 Other BASELINE configs (same JSON contract, the workload named in config.workload):
     configs[2]  python bench.py --dtype bf16s --batch 128
     configs[3]  python bench.py --image-size 128 --problem dyn_modeling --batch 128
@@ -213,6 +219,28 @@ def _emit(obj):
     os.write(_RESULT_FD if _RESULT_FD is not None else 1, (json.dumps(obj) + "\n").encode())
 
 
+DUMP_BYTES = 63 * 10 ** 6          # the .npy payloads of --dump-outputs (64 MB in all with their headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each (name, tensor) as out_dir/<name>.npy, float64 kept, every other dtype as float32.  When the arrays
+    exceed DUMP_BYTES together, every array above 1 MB is replaced by a sample of its flattened elements, in index order, the
+    indices drawn from a fixed seed: the same elements in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = [(name, (t.double() if t.dtype == torch.float64 else t.float()).detach().cpu().numpy()) for name, t in arrays]
+    total = sum(a.nbytes for _, a in arrs)
+    small = sum(a.nbytes for _, a in arrs if a.nbytes <= 2 ** 20)
+    for name, a in arrs:
+        if total > DUMP_BYTES and a.nbytes > 2 ** 20:
+            n = a.size
+            keep = int(n * (DUMP_BYTES - small) / (total - small))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(n, keep, replace=False))]
+            print(f"[bench] {name}: a seeded sample of {keep} of its {n} elements", file=sys.stderr)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] outputs written to {out_dir}: {', '.join(n for n, _ in arrs)}", file=sys.stderr)
+
+
 def _self_launch(n):
     """``python bench.py --gpus N`` without a launcher: start the N ranks ourselves, the way the driver does for N > 1
     (``python -m torch.distributed.run --nproc-per-node N``), as a CHILD process -- this process has not touched the GPU
@@ -243,7 +271,14 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256, help="samples per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel profile and roofline, the other fp32 "
+                         "arithmetic beside the line and the CPU baseline (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, partial ELBOs, updated parameters and "
+                         "BatchNorm buffers; --infer: the forward's outputs) as DIR/<name>.npy, float32 / float64, at most 64 MB in all "
+                         "(a fixed seeded sample of an array beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="do not replay the step from a HIP graph")
     ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
     ap.add_argument("--image-size", type=int, choices=(64, 128, 256), default=64,
@@ -255,8 +290,8 @@ def main():
     ap.add_argument("--seq-length", type=int, default=4)
     ap.add_argument("--dtype", choices=("f32", "f32x3", "bf16", "bf16s", "fp16", "fp16s"), default="f32x3",
                     help="f32x3 (default): BASELINE configs[1] with the fp32 GEMMs on the bf16 matrix cores through the exact "
-                         "three-term split of their fp32 operands (fp32 storage, results and tolerances; the native fp32 run is timed by "
-                         "the same process and reported beside it as native_fp32).  f32: the native fp32 matrix cores.  bf16s: bf16 activation storage + bf16 matrix "
+                         "three-term split of their fp32 operands (fp32 storage, results and tolerances; with --full the native fp32 run is "
+                         "timed by the same process and reported beside it as native_fp32).  f32: the native fp32 matrix cores.  bf16s: bf16 activation storage + bf16 matrix "
                          "cores, fp32 accumulate / master weights = the per-GPU share of configs[2] (use --batch 128).  "
                          "bf16: bf16 matrix-core operands only (fp32 storage).  fp16: fp16 matrix-core operands, fp32 "
                          "accumulate / storage / master weights (configs[4]).  fp16s: fp16 + fp16 activation storage")
@@ -268,7 +303,7 @@ def main():
                          "direction, captured into the lanes' HIP graphs, each lane on its own RCCL communicator).  Default: "
                          "local statistics")
     ap.add_argument("--no-alt", action="store_true",
-                    help="skip the extra timed run in the other fp32 arithmetic (native fp32 beside the default f32x3 line, f32x3 "
+                    help="(--full) skip the extra timed run in the other fp32 arithmetic (native fp32 beside the default f32x3 line, f32x3 "
                          "beside --dtype f32) that a one-GPU run reports next to its value")
     ap.add_argument("--infer", action="store_true",
                     help="time forward-only inference instead (model.eval(): joint visual+tactile+pose pass through the "
@@ -294,6 +329,8 @@ def main():
                     help="no visual/tactile stream overlap: per-kernel durations in a rocprofv3 trace then match "
                          "the roofline object's live HIP-event measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return _self_launch(args.gpus)
@@ -394,6 +431,9 @@ def main():
             out = eng([v, t], pose=p)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [(name, x) for name, x in zip(
+                ("visual_recon", "tactile_recon", "pose_recon", "means", "log_var"), out) if x is not None])
         _emit({"metric": "visuotactile samples/sec (inference, joint v+t+p forward, eval mode)",
                           "value": args.batch * args.steps / dt, "unit": "samples/s", "n_gpus": 1, "steps": args.steps,
                           "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
@@ -418,9 +458,10 @@ def main():
         for k in (0, 1):
             targets[k][Lq - 1::Lq] = final[k][Lq - 1::Lq]
 
-    def measure(dtype, with_pg):
+    def measure(dtype, with_pg, profile, dump_dir=None):
         """W warm-up + K timed steps of the workload in one arithmetic (between barrier + synchronize, max over ranks), then
-        the per-kernel HIP-event profile of one more (untimed, single-lane, eager) step.  Same seeds for every arithmetic."""
+        (dump_dir) what the last timed step computed, then (profile) the per-kernel HIP-event profile of one more (untimed,
+        single-lane, eager) step.  Same seeds for every arithmetic."""
         model = new_model()
         step = MVAEStep(model, lr=1e-3, pose_multiplier=1000.0, noise=NoiseSource(1234 + rank), process_group=pg if with_pg else None,
                         world_size=world if with_pg else 1, two_lanes=not args.single_lane,
@@ -455,19 +496,25 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t)
         res = {"dtype": dtype, "elapsed": elapsed, "host_enqueue": host_enqueue, "final_loss": float(loss)}
+        if dump_dir and rank == 0:
+            # what a caller of the step holds after it: the loss and the partial ELBO of each modality subset of the last
+            # timed step, the parameters its Adam update wrote and the BatchNorm running buffers, in module order
+            dump_outputs(dump_dir, [("loss", step.loss), ("partials", step.partials[:step.P]),
+                                    ("params", torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])),
+                                    ("buffers", torch.cat([b.detach().reshape(-1).double() for b in model.buffers()]))])
         # per-kernel timing of one extra (untimed) step, HIP events on the launch stream (one lane, eager launches: per-kernel
         # durations are then not inflated by the other lane's kernels).  The step is profiled TWICE and the second pass is
         # kept: the first eager step after the graph replays draws its scratch tensors (stream-K slabs, partial-sum tables)
         # from the default memory pool for the first time, and that allocation sits between the two events of the launch that
         # asked for it (the k4 s1 p0 layer read 282 us by events against 204 us in the rocprofv3 trace of the same run:
         # VERDICT r4, profiles/r5/event_vs_trace_s1p0.txt)
-        lanes_on, step.lanes.on = step.lanes.on, False
         kern, by_shape = {}, {}
-        if not dry:
+        if profile and not dry:
+            lanes_on, step.lanes.on = step.lanes.on, False
             profile_step(eager_step)
             kern = profile_step(eager_step)
             by_shape = dict(profile_step.by_shape)
-        step.lanes.on = lanes_on
+            step.lanes.on = lanes_on
         res["kern"], res["by_shape"] = kern, by_shape
         step.close()
         del step, model
@@ -578,7 +625,7 @@ def main():
 
     if pg is not None:
         import torch.distributed as dist
-    primary = measure(args.dtype, True)
+    primary = measure(args.dtype, True, args.full or args.breakdown, args.dump_outputs)
     if pg is not None:
         dist.barrier()
     if rank != 0:
@@ -586,10 +633,9 @@ def main():
             dist.destroy_process_group()
         return
 
-    elapsed, final_loss, kern = primary["elapsed"], primary["final_loss"], primary["kern"]
+    elapsed, final_loss = primary["elapsed"], primary["final_loss"]
     global_batch = args.batch * world
     sps = global_batch * args.steps / elapsed
-    roof, total_ms = roofline_of(primary, sps)
     arith = {"f32": "fp32 (native fp32 matrix cores)",
              "f32x3": "fp32 storage and results, GEMMs in the fp32x3 arithmetic (exact three-term bf16 split of the fp32 operands, "
                       "six of nine products on the bf16 matrix cores, fp32 accumulate; error vs fp64 <= native fp32 MFMA)",
@@ -618,8 +664,9 @@ def main():
                    "global_batch": global_batch, "parallelism": f"dp{world}", "bn": "sync" if (args.sync_bn and pg is not None) else "local",
                    "launch": "eager" if (args.no_graph or (args.sync_bn and pg is not None and dry)) else "hip_graph",
                    "final_loss": final_loss, "host_enqueue_ms_per_step": 1e3 * primary["host_enqueue"] / args.steps},
-        "roofline": roof,
     }
+    if args.full:
+        out["roofline"], _ = roofline_of(primary, sps)
     if rehearse:
         out["rehearsal"] = "all ranks on ONE GPU, collectives over gloo (MMDYN_BENCH_REHEARSE_ONE_GPU=1): schedule check, not a scaling number"
     if dry:
@@ -641,12 +688,12 @@ def main():
 
     if args.breakdown:
         print_breakdown(primary, f"{args.dtype} (the measured arithmetic)")
-    if world == 1 and args.dtype in ("f32", "f32x3") and not args.no_alt and not dry and not args.no_graph:
+    if args.full and world == 1 and args.dtype in ("f32", "f32x3") and not args.no_alt and not dry and not args.no_graph:
         # The same workload, same seeds, in the OTHER fp32 arithmetic, timed the same way by the same process on the same box and
         # reported NEXT to `value` with its own roofline: native fp32 matrix cores beside the default fp32x3 line (VERDICT r4
         # item 2), or fp32x3 beside an explicit --dtype f32 run.
         other = "f32" if args.dtype == "f32x3" else "f32x3"
-        sec = measure(other, False)
+        sec = measure(other, False, True)
         sps2 = args.batch * args.steps / sec["elapsed"]
         roof2, _ = roofline_of(sec, sps2)
         obj = {"dtype": other, "value": sps2, "unit": "samples/s", "ms_per_step": 1e3 * sec["elapsed"] / args.steps,
@@ -663,7 +710,7 @@ def main():
             out["alt_arithmetic"] = obj
         if args.breakdown:
             print_breakdown(sec, other)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # torch.set_num_threads(os.cpu_count()).  On a box whose CPU share is smaller than the
         # machine (the one-GPU box: 16 of 256 hardware threads, no visible quota) the figure at the documented share is
         # reported next to it; `value` / `cores` are the faster of the two, i.e. the strongest CPU baseline measured.

@@ -1,11 +1,13 @@
 #!/bin/bash
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}
+mkdir -p $OUT
 for i in 1 2; do
-  timeout -k 10 200 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > gpurun_out/bench_f32_$i.json 2> gpurun_out/bench_f32_$i.err || exit 1
-  timeout -k 10 200 python bench.py --dtype bf16s --batch 128 --steps 100 --warmup 10 --no-cpu-baseline > gpurun_out/bench_b16_$i.json 2> gpurun_out/bench_b16_$i.err || exit 1
+  timeout -k 10 200 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_f32_$i.json 2> $OUT/bench_f32_$i.err || exit 1
+  timeout -k 10 200 python bench.py --full --dtype bf16s --batch 128 --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_b16_$i.json 2> $OUT/bench_b16_$i.err || exit 1
 done
 python3 - <<'PY'
-import json,glob
-for f in sorted(glob.glob('gpurun_out/bench_f32_[12].json')+glob.glob('gpurun_out/bench_b16_[12].json')):
+import json,glob,os
+o = os.environ['OUT']
+for f in sorted(glob.glob(o + '/bench_f32_[12].json')+glob.glob(o + '/bench_b16_[12].json')):
     d=json.loads(open(f).read().strip().splitlines()[-1]); print(f, round(d['value']), round(d['ms_per_step'],3), round(d['roofline']['achieved'],1))
 PY

@@ -1,7 +1,10 @@
 """Drop-in module API + problem layer + fused engine, host logic on CPU (kernels emulated by
 tests/emu_backend.py), checked against the golden vectors produced by the reference."""
 import argparse
+import atexit
 import os
+import shutil
+import tempfile
 
 import numpy as np
 import pytest
@@ -15,6 +18,10 @@ from mmdyn_hip.problems.problems import SeqModeling, DynModeling, SyntheticVisuo
 from mmdyn_hip.utils.seeded_init import seeded_state_dict, seeded_batch, seeded_noise
 from emu_backend import EmuBackend
 from test_oracle_golden import summarize, close_summary, close_params, load
+
+# the problems' log / checkpoint directory: one per test process, never a fixed path another user may own
+LOG_DIR = tempfile.mkdtemp(prefix="mmdyn_test_logs_")
+atexit.register(shutil.rmtree, LOG_DIR, True)
 
 MODEL_KW = dict(condition_dim=0, input_dim=4096, architecture="cnn", conditional=False, categorical_conditions=False,
                 latent_size=256)
@@ -72,7 +79,7 @@ def check_reference_schedule_step(golden_dir, device, fname, use_pose):
     """fused=False: seven model() calls + autograd, as the reference does."""
     g = load(golden_dir, fname)
     B = int(g["batch"])
-    prob = SeqModeling(args(use_pose=use_pose, no_cuda=(device == "cpu")), log_dir="/tmp/mmdyn_test_logs", fused=False)
+    prob = SeqModeling(args(use_pose=use_pose, no_cuda=(device == "cpu")), log_dir=LOG_DIR, fused=False)
     m = prob.model
     m.load_state_dict(seeded_state_dict(m.state_dict(), 0))
     inputs, targets = seeded_batch(B, 1234, with_pose=use_pose)
@@ -173,7 +180,7 @@ def check_fused_engine_mask_loss(device, mask_channels, B=3):
     gen = torch.Generator().manual_seed(5)
     mask = (torch.rand(B, mask_channels, 64, 64, generator=gen) > 0.4).float().to(device)
     eps, masks = seeded_noise(B, 256, 3, 4, 4321)
-    prob = SeqModeling(args(use_pose=False, mask_loss=True, no_cuda=(device == "cpu")), log_dir="/tmp/mmdyn_test_logs", fused=False)
+    prob = SeqModeling(args(use_pose=False, mask_loss=True, no_cuda=(device == "cpu")), log_dir=LOG_DIR, fused=False)
     m = prob.model
     m.load_state_dict(seeded_state_dict(m.state_dict(), 0))
     m.noise = InjectedNoise(eps, masks)
@@ -210,17 +217,17 @@ def test_exact_running_stats_flag_reaches_the_fused_step():
     ns = build_parser().parse_args(["--problem-type", "seq_modeling", "--model-name", "cnn-mvae", "--input-type", "visuotactile",
                                     "--use-pose", "--exact-running-stats", "--no-cuda"])
     assert ns.exact_running_stats is True
-    prob = SeqModeling(args(no_cuda=True, exact_running_stats=True), log_dir="/tmp/mmdyn_test_logs")
+    prob = SeqModeling(args(no_cuda=True, exact_running_stats=True), log_dir=LOG_DIR)
     assert prob._step is not None and prob._step.exact_running_stats is True
-    assert SeqModeling(args(no_cuda=True), log_dir="/tmp/mmdyn_test_logs")._step.exact_running_stats is False
+    assert SeqModeling(args(no_cuda=True), log_dir=LOG_DIR)._step.exact_running_stats is False
 
 
 def test_mask_loss_engine_selection_and_errors():
     """--mask-loss runs the fused step when the model has no pose term; with --use-pose the reference fails on the (B, 7)
     pose term (problems.py:445-447) and so does the engine."""
-    prob = SeqModeling(args(use_pose=False, mask_loss=True, no_cuda=True), log_dir="/tmp/mmdyn_test_logs")
+    prob = SeqModeling(args(use_pose=False, mask_loss=True, no_cuda=True), log_dir=LOG_DIR)
     assert prob._step is not None
-    prob = SeqModeling(args(use_pose=True, mask_loss=True, no_cuda=True), log_dir="/tmp/mmdyn_test_logs")
+    prob = SeqModeling(args(use_pose=True, mask_loss=True, no_cuda=True), log_dir=LOG_DIR)
     assert prob._step is None
     inputs, targets = seeded_batch(2, 1)
     step = MVAEStep(build("cnn-mvae", True, True, "cpu"))
@@ -435,7 +442,7 @@ def test_fused_engine_exact_running_stats(golden_dir, fname, use_pose):
 def check_vae_config1(golden_dir, device):
     g = load(golden_dir, "vae_visual_B16.npz")
     prob = SeqModeling(args(model_name="cnn-vae", input_type="visual", use_pose=False, no_cuda=(device == "cpu")),
-                       log_dir="/tmp/mmdyn_test_logs", fused=False)
+                       log_dir=LOG_DIR, fused=False)
     m = prob.model
     m.load_state_dict(seeded_state_dict(m.state_dict(), 0))
     eps, masks = seeded_noise(16, 256, 2, 2, 31)
