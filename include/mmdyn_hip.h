@@ -52,7 +52,8 @@ const char* mmdyn_version(void);
 /* ABI revision of this header.  It changes whenever an exported signature or a workspace requirement changes (round 4 added
  * the `ws` argument of mmdyn_igemm_nt_dgrad_act / _dgrad_bn and the slab workspace of large launches: revision 4; round 5 the
  * plane-packed weight kinds of the pack plan: revision 5; round 6 the `zdst` field of mmdyn_pass_experts, the arrival-flag words in
- * front of the slab workspace (mmdyn_igemm_slab_floats*) and new entry points: revision 6).  A binding checks mmdyn_abi_version() == MMDYN_ABI_VERSION right after
+ * front of the slab workspace (mmdyn_igemm_slab_floats*) and new entry points: revision 6; the per-sample
+ * ELBO entry points (mmdyn_*_rows*) were added without touching an existing signature or workspace and keep revision 6).  A binding checks mmdyn_abi_version() == MMDYN_ABI_VERSION right after
  * loading the library (mmdyn_hip/_lib.py does) so that a caller built against an older header fails at load time instead of
  * passing its stream handle where the library now expects a workspace pointer. */
 #define MMDYN_ABI_VERSION 6
@@ -256,6 +257,14 @@ int mmdyn_tconv_out3_bn_bce(const void* y, const float* mean, const float* rstd,
                             const float* w, float* logits, int logits_group, const float* target, const float* mask,
                             int mask_channels, float* dlogit, double* loss_slots, double* unmasked_slots,
                             const int* slot_of_group, float grad_scale, int G, int Bg, int Hi, int Wi, int b16, void* stream);
+/* The evaluation form of that launch with one sum per SAMPLE (the reduce=False branch, problems.py:451-456: torch.sum(e, (1, 2, 3))):
+ * loss_rows[slot_of_group[g]][b] += the sum over sample b of group g, loss_rows / unmasked_rows [n_slots][Bg] double (a slot at or
+ * above n_slots is MMDYN_ERR_SHAPE).  Same arguments otherwise, no gradient output; the same kernel (a block of its grid never spans
+ * two samples), so the logits of the passes nobody reads are not written here either. */
+int mmdyn_tconv_out3_bn_bce_rows(const void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                 const float* w, float* logits, int logits_group, const float* target, const float* mask,
+                                 int mask_channels, double* loss_rows, double* unmasked_rows, const int* slot_of_group,
+                                 int n_slots, int G, int Bg, int Hi, int Wi, int b16, void* stream);
 
 /* ---- train-mode BatchNorm2d + Swish, channels-last, per group (vae.py:201-208, 269-276) ----- */
 /* column sums of y and y*y over row chunks -> partial[G][T][2][C], T = mmdyn_colstats_tiles(rows_per_group) */
@@ -418,6 +427,32 @@ int mmdyn_mse_groups(const float* r, const float* t, float* dr, double* loss_slo
  * epoch of the schedule. */
 int mmdyn_elbo_assemble(const double* bce, const double* mse, const double* kl, float* loss, float* partials,
                         int P, int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev, void* stream);
+
+/* ---- per-sample ELBO (the reduce=False branch of problems.py:401-458; evaluation only, no gradients) -------- */
+/* torch.sum(F.binary_cross_entropy_with_logits(recon, x, reduce=False), (1, 2, 3)) (problems.py:409-416, 445-452) for G decoder
+ * passes against ONE target: logits [G][Bg][chw], target [Bg][chw], mask (may be null) [Bg][mask_channels][hw] as in
+ * mmdyn_bce_logits_groups_masked; rows_out[slot_of_group[g]][b] += the sum over sample b of pass g, rows_out [n_slots][Bg] double
+ * (the caller zeroes it; two passes may share a slot; a negative slot is a discarded pass; a slot >= n_slots is MMDYN_ERR_SHAPE).
+ * unmasked_rows (with a mask; may be null) also receives the plain sums.  chw % 4 == 0, hw % 4 == 0.  The target / mask row of a
+ * sample is read once for all G passes.  Element arithmetic identical to mmdyn_bce_logits_groups. */
+int mmdyn_bce_logits_rows_groups(const float* logits, const float* target, const float* mask, int mask_channels, double* rows_out,
+                                 double* unmasked_rows, const int* slot_of_group, int n_slots, int G, int Bg, int chw, int hw,
+                                 void* stream);
+/* torch.sum(F.mse_loss(r, t, reduce=False), 1) (problems.py:439-452, the pose term) for G passes against one target: r [G][Bg][n],
+ * t [Bg][n], rows_out[slot_of_group[g]][b] += sum_n (r - t)^2.  Slots in [0, n_slots). */
+int mmdyn_mse_rows_groups(const float* r, const float* t, double* rows_out, const int* slot_of_group, int n_slots, int G, int Bg,
+                          int n, void* stream);
+/* kl_rows[p][b] = -0.5 * sum_L (1 + logvar - mu^2 - exp(logvar)) of mu / logvar [P][B][L] (what mmdyn_poe_fwd wrote, or the heads of
+ * a VAE with P = 1): the terms of problems.py:406, 429 kept per sample -- the reference adds the batch TOTAL to every row.  Same
+ * element expression as the kl_sum of mmdyn_poe_fwd / mmdyn_reparam_fwd: the rows of pass p add up to kl_sum[p] to fp64 rounding. */
+int mmdyn_kl_rows(const float* mu, const float* logvar, double* kl_rows, int P, int B, int L, void* stream);
+/* partials[p][b] = bce_rows[p][b] + pose_multiplier * mse_rows[p][b] + kl_weight * KL, out[b] = sum_p partials[p][b]; tables [P][B]
+ * double (any may be null = 0), out [B] and partials [P][B] (may be null) float.  kl_mode 0: KL = kl_sum[p], the batch total in
+ * every row -- what the reference returns (problems.py:415-417, 455-456); kl_mode 1: KL = kl_rows[p][b].  No division by B in either
+ * mode.  kl_weight_dev as in mmdyn_elbo_assemble. */
+int mmdyn_elbo_assemble_rows(const double* bce_rows, const double* mse_rows, const double* kl_rows, const double* kl_sum, float* out,
+                             float* partials, int P, int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev,
+                             int kl_mode, void* stream);
 
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call

@@ -44,14 +44,16 @@ struct Out3Loss {
   const float* target;    // [Bg][3][2Hi][2Wi]: every group is scored against the same target
   const float* mask;      // [Bg][mask_c][2Hi][2Wi] or null (--mask-loss)
   float* dlogit;          // [G*Bg][3][2Hi][2Wi] or null (evaluation)
-  double* loss;           // loss[slot[g]] += sum over group g
+  double* loss;           // loss[slot[g]] += sum over group g (ROWS: loss[slot[g]][sample] += sum over one sample of group g)
   double* unmasked;       // with a mask: the plain sums as well (or null)
   int slot[MMDYN_BCE_GROUPS_MAX];      // < 0: a discarded pass (zero gradient, no loss)
   int mask_c;
   int logit_group;        // group whose logits go to `out` ([Bg][3][2Hi][2Wi]); -1: all groups ([G*Bg]...)
   float grad_scale;
 };
-template <typename TA, bool FUSED = false, bool LOSS = false>
+// ROWS (a mode of LOSS, evaluation only): the grid is (tiles, sample), a block never spans two samples, so its sum can go to the
+// SAMPLE's entry of a [slots][Bg] table instead of the pass's slot -- the per-sample ELBO (problems.py:451-456, reduce=False).
+template <typename TA, bool FUSED = false, bool LOSS = false, bool ROWS = false>
 __global__ __launch_bounds__(256) void tconv_out3_kernel(const TA* __restrict__ a,         // [Bt][Hi][Wi][32]
                                                          const float* __restrict__ w,      // [32][3][4][4]
                                                          float* __restrict__ out,          // [Bt][3][2Hi][2Wi]
@@ -201,8 +203,9 @@ __global__ __launch_bounds__(256) void tconv_out3_kernel(const TA* __restrict__ 
       }
       __syncthreads();
       if (tid == 0) {
-        atomicAdd(ls.loss + slot, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-        if (ls.mask && ls.unmasked) atomicAdd(ls.unmasked + slot, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+        const size_t o = ROWS ? (size_t)slot * bn.Bg + smp : (size_t)slot;
+        atomicAdd(ls.loss + o, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+        if (ls.mask && ls.unmasked) atomicAdd(ls.unmasked + o, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
       }
     }
   }
@@ -272,6 +275,42 @@ extern "C" int mmdyn_tconv_out3_bn_bce(const void* y, const float* mean, const f
     hipLaunchKernelGGL((tconv_out3_kernel<bf16_t, true, true>), grid, dim3(256), smem, (hipStream_t)stream, (const bf16_t*)y, w, logits, Hi, Wi, bn, ls);
   else
     hipLaunchKernelGGL((tconv_out3_kernel<float, true, true>), grid, dim3(256), smem, (hipStream_t)stream, (const float*)y, w, logits, Hi, Wi, bn, ls);
+  MMDYN_LAUNCH_CHECK();
+}
+
+/* mmdyn_tconv_out3_bn_bce in evaluation with one sum per SAMPLE: loss_rows[slot_of_group[g]][b] += the sum over sample b of group g
+ * (loss_rows / unmasked_rows: [n_slots][Bg]).  The same kernel, ROWS mode of its loss epilogue; no gradient output. */
+extern "C" int mmdyn_tconv_out3_bn_bce_rows(const void* y, const float* mean, const float* rstd, const float* gamma,
+                                            const float* beta, const float* w, float* logits, int logits_group, const float* target,
+                                            const float* mask, int mask_channels, double* loss_rows, double* unmasked_rows,
+                                            const int* slot_of_group, int n_slots, int G, int Bg, int Hi, int Wi, int b16,
+                                            void* stream) {
+  if (!y || !mean || !rstd || !gamma || !beta || !w || !target || !loss_rows || !slot_of_group) return MMDYN_ERR_NULL;
+  const int64_t Bt = (int64_t)G * Bg;
+  if (G <= 0 || G > MMDYN_BCE_GROUPS_MAX || Bg <= 0 || Hi % TI || Wi % TI || Bt > 65535 || b16 < 0 || b16 > 2) return MMDYN_ERR_SHAPE;
+  if (logits_group < -1 || logits_group >= G || (mask && mask_channels != 1 && mask_channels != 3) || n_slots <= 0) return MMDYN_ERR_SHAPE;
+  if (Bt * Hi * Wi * 32 >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  dim3 grid((Hi / TI) * (Wi / TI), (unsigned)Bt);
+  size_t smem = (size_t)32 * CH_LD * sizeof(float);
+  const Out3Bn bn{mean, rstd, gamma, beta, Bg};
+  Out3Loss ls{};
+  ls.target = target;
+  ls.mask = mask;
+  ls.loss = loss_rows;
+  ls.unmasked = unmasked_rows;
+  for (int i = 0; i < G; ++i) {
+    if (slot_of_group[i] >= n_slots) return MMDYN_ERR_SHAPE;
+    ls.slot[i] = slot_of_group[i];
+  }
+  ls.mask_c = mask ? mask_channels : 1;
+  ls.logit_group = logits_group;
+  ls.grad_scale = 0.f;
+  if (b16 == 2)
+    hipLaunchKernelGGL((tconv_out3_kernel<half_t, true, true, true>), grid, dim3(256), smem, (hipStream_t)stream, (const half_t*)y, w, logits, Hi, Wi, bn, ls);
+  else if (b16 == 1)
+    hipLaunchKernelGGL((tconv_out3_kernel<bf16_t, true, true, true>), grid, dim3(256), smem, (hipStream_t)stream, (const bf16_t*)y, w, logits, Hi, Wi, bn, ls);
+  else
+    hipLaunchKernelGGL((tconv_out3_kernel<float, true, true, true>), grid, dim3(256), smem, (hipStream_t)stream, (const float*)y, w, logits, Hi, Wi, bn, ls);
   MMDYN_LAUNCH_CHECK();
 }
 

@@ -118,6 +118,11 @@ _SIGNATURES = {
     "mmdyn_resize_u8_to_chw_f32": "ppp" + "iiiii" + "pppp" + "p",
     "mmdyn_nchw_to_nhwc": "pp" + "iii" + "p",
     "mmdyn_nhwc_to_nchw": "pp" + "iii" + "p",
+    "mmdyn_tconv_out3_bn_bce_rows": "ppppppp" + "i" + "pp" + "i" + "ppp" + "iiiiii" + "p",
+    "mmdyn_bce_logits_rows_groups": "ppp" + "i" + "ppp" + "iiiii" + "p",
+    "mmdyn_mse_rows_groups": "pppp" + "iiii" + "p",
+    "mmdyn_kl_rows": "ppp" + "iii" + "p",
+    "mmdyn_elbo_assemble_rows": "pppppp" + "ii" + "ff" + "p" + "i" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

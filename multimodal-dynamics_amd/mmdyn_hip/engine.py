@@ -470,7 +470,8 @@ class MVAEStep:
                     "tg": {"v": targets[0].contiguous(), "t": targets[1].contiguous()},
                     "pose": inputs[2].contiguous() if self.use_pose else None,
                     "pose_tg": targets[2].contiguous() if self.use_pose else None,
-                    "kl_weight": float(kl_weight), "train": train, "pk": {}, "lmask": loss_mask, "cond": condition}
+                    "kl_weight": float(kl_weight), "train": train, "pk": {}, "lmask": loss_mask, "cond": condition,
+                    "rows": None}                 # score_step: fp64 [4][P][B] per-sample bce / mse / kl / unmasked-bce tables
 
     def _passes_of(self, m):
         return self.pass_v if m == "v" else self.pass_t
@@ -583,6 +584,8 @@ class MVAEStep:
             d["zpl"] = [zpl[m].t.data_ptr() + lists[m].index(p) * B * 3 * L * 2 if (zpl.get(m) is not None and p in lists[m]) else None
                         for m in ("v", "t")]
         ops.B.poe_fwd(passes, c["eps"], c["mu"], c["lv"], c["z"], self.acc[2], True, P, B, L)
+        if c["rows"] is not None:
+            ops.B.kl_rows(c["mu"], c["lv"], c["rows"][2], P, B, L)
 
     def _ph_dec_fwd_steps(self, m):
         """Image decoder on its live passes (groups) followed by the BCE sums (+ logit gradients when training)."""
@@ -600,6 +603,9 @@ class MVAEStep:
         spec = dict(target=tg, slots=slots, acc=self.acc[0], grad_scale=self.loss_scale / B, want_grad=c["train"],
                     keep=None if self.keep_logits else plist.index(joint), mask=mk,
                     mask_channels=1 if mk is None else mk.shape[1], acc_u=None if mk is None else self.acc[3])
+        rows = c["rows"]
+        if rows is not None:
+            spec.update(rows=rows[0], rows_u=None if mk is None else rows[3])
         lg, c["d" + m] = yield from layers.decoder_forward_steps(FP.sub(dec), self._buffers(dec), zz, len(plist),
                                                                  packed=c["pk"].get("d" + m), cond=cond, loss=spec if FUSED_BCE else None,
                                                                  z_planes=c.get("zzpl" + m))
@@ -608,6 +614,12 @@ class MVAEStep:
             c["lg_joint_only" + m] = not self.keep_logits
             return
         c["lg_joint_only" + m] = False
+        if rows is not None:
+            ops.B.bce_logits_rows_groups(lg, tg, rows[0], slots, B, tg[0].numel(), mask=mk, hw=tg[0, 0].numel(),
+                                         mask_channels=1 if mk is None else mk.shape[1],
+                                         unmasked_rows=None if mk is None else rows[3])
+            c["lg" + m], c["dl" + m] = lg, None
+            return
         dl = torch.empty_like(lg) if c["train"] else None
         if mk is None:
             ops.B.bce_logits_groups(lg, tg, dl, self.acc[0], slots, tg.numel(), self.loss_scale / B)
@@ -625,11 +637,20 @@ class MVAEStep:
             pr, c["dp"] = layers.pose_decoder_forward(FP.sub("pose_decoder"), zp)
             dpr = torch.empty_like(pr) if c["train"] else None
             # every pose-bearing pass against the same target: one launch, one loss slot per pass
-            ops.B.mse_groups(pr, c["pose_tg"], dpr, self.acc[1], list(self.pass_p), B * 7, self.loss_scale * self.pose_multiplier / B)
+            if c["rows"] is not None:
+                ops.B.mse_rows_groups(pr, c["pose_tg"], c["rows"][1], list(self.pass_p), B, 7)
+            else:
+                ops.B.mse_groups(pr, c["pose_tg"], dpr, self.acc[1], list(self.pass_p), B * 7,
+                                 self.loss_scale * self.pose_multiplier / B)
             c["pr"], c["dpr"] = pr, dpr
 
     def _ph_assemble(self):
         c = self.ctx
+        if c["rows"] is not None:
+            # the per-pass sums eval_step would have produced are the sums of the rows (no second run of the scalar kernels)
+            for k, used in ((0, True), (1, self.use_pose), (3, c["lmask"] is not None)):
+                if used:                          # (acc was zeroed by _ph_pre: an unused table's sums stay zero)
+                    torch.sum(c["rows"][k], 1, out=self.acc[k][:self.P])
         ops.B.elbo_assemble(self.acc[0], self.acc[1], self.acc[2], self.loss, self.partials, self.P, c["B"],
                             1.0, self.pose_multiplier, self.klw)
 
@@ -743,13 +764,17 @@ class MVAEStep:
 
     # ------------------------------------------------------------------------------------------
     @_with_precision
-    def forward(self, inputs, targets, kl_weight, train=True, loss_mask=None, condition=None):
+    def forward(self, inputs, targets, kl_weight, train=True, loss_mask=None, condition=None, rows=False):
         """Runs the forward schedule and the loss; with train=True also fills the loss gradients needed by
         :meth:`backward`.  Returns the device scalar loss (fp32).  ``loss_mask`` ([B][1 or C][H][W], models without pose):
         the reference's --mask-loss, multiplying logits and targets of every image term.  ``condition`` ([B][condition_dim]):
         the shock force of the --conditional models."""
         LN = self.lanes
         self._begin(inputs, targets, kl_weight, train, loss_mask, condition)
+        if rows:
+            if train:
+                raise ValueError("per-sample rows are an evaluation result (train=False): there is no gradient path")
+            self.ctx["rows"] = torch.zeros(4, self.P, self.ctx["B"], dtype=torch.float64, device=self.ctx["dev"])
         self._ph_pre()
         LN.fork()
         self._ph_pack_late()
@@ -1163,6 +1188,34 @@ class MVAEStep:
         self.ctx = None
         return loss
 
+    @torch.no_grad()
+    @_with_precision
+    def score_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, kl="batch"):
+        """Per-sample ELBO of one batch: the schedule of :meth:`eval_step` (same BatchNorm mode, subset passes and lanes) ending in
+        the row kernels -- the fused last decoder layer adds each block's BCE sum to its SAMPLE's entry, so no logits beyond the
+        published joint reconstruction are written.  Returns a dict of device tensors:
+
+          ``rows`` fp32 [B]: sum over the subset passes of bce + pose_multiplier * mse + kl_weight * KL, nothing divided by B.
+            ``kl="batch"``: KL is the total over the batch, in every row -- what the reference's ``reduce=False`` returns
+            (problems.py:429, 456); ``kl="sample"``: each sample's own KL, the quantity to rank samples by.
+          ``partials`` fp32 [P][B] the same per pass; ``bce_rows`` / ``mse_rows`` / ``kl_rows`` fp64 [P][B];
+          ``loss`` (fp32 scalar) and ``loss_partials`` ([P]): what ``eval_step`` returns / leaves in ``self.partials`` on the same
+          inputs and noise, from the sums of the rows.  ``self.last`` / ``self.acc`` are filled as by ``eval_step``.
+        Forward only."""
+        if kl not in ("batch", "sample"):
+            raise ValueError("kl must be 'batch' (the reference's row: the batch-total KL) or 'sample'")
+        loss = self.forward(inputs, targets, kl_weight, train=False, loss_mask=loss_mask, condition=condition, rows=True)
+        c, P = self.ctx, self.P
+        B, tab = c["B"], c["rows"]
+        out = torch.empty(B, device=c["dev"])
+        partials = torch.empty(P, B, device=c["dev"])
+        ops.B.elbo_assemble_rows(tab[0], tab[1] if self.use_pose else None, tab[2], self.acc[2], out, partials, P, B, 1.0,
+                                 self.pose_multiplier, self.klw, 1 if kl == "sample" else 0)
+        self.ctx = None
+        return {"rows": out, "partials": partials, "bce_rows": tab[0], "mse_rows": tab[1], "kl_rows": tab[2],
+                "unmasked_bce_rows": tab[3] if self.last["masked"] else None, "loss": loss.clone(),
+                "loss_partials": self.partials[:P].clone(), "kl": kl}
+
 
 class MVAEInference:
     """Forward-only serving path for a trained :class:`mmdyn_hip.models.MVAE` in ``eval()`` mode
@@ -1343,6 +1396,68 @@ class MVAEInference:
         return self._run(key, self._forward, None, ins)
 
     __call__ = forward
+
+    def _score(self, self_target, visual, tactile, pose, tv, tt, tp, mask):
+        """One forward of the given subset, then the per-sample terms of that pass: the row kernels on the logits, the pose
+        reconstruction and the posterior the forward left on the device.  Tables (fp64 [2][B], zeroed by a fill that a captured
+        graph replays): bce = (visual, tactile), mse = (pose, 0), kl = (KL, 0); the assembly adds the two rows of each table."""
+        v, t, pr, mu, lv = self._forward(visual, tactile, pose)
+        if self_target:
+            tv, tt, tp = visual, tactile, pose if self.use_pose else None
+        B, L = mu.shape
+        bce, mse, kl = torch.zeros(3, 2, B, dtype=torch.float64, device=mu.device)
+        chw, hw = v[0].numel(), v[0, 0].numel()
+        mc = 1 if mask is None else mask.shape[1]
+        for slot, (lg, tg) in enumerate(((v, tv), (t, tt))):
+            if tg is not None:
+                ops.B.bce_logits_rows_groups(lg, tg, bce, [slot], B, chw, mask=mask, hw=hw, mask_channels=mc)
+        if tp is not None:
+            ops.B.mse_rows_groups(pr, tp, mse, [0], B, tp.shape[1])
+        ops.B.kl_rows(mu, lv, kl[0:1], 1, B, L)
+        rows = torch.empty(B, device=mu.device)
+        ops.B.elbo_assemble_rows(bce, mse, kl, None, rows, None, 2, B, 1.0, self._pose_multiplier, self._klw, 1)
+        return {"rows": rows, "bce_visual": bce[0] if tv is not None else None, "bce_tactile": bce[1] if tt is not None else None,
+                "mse_pose": mse[0] if tp is not None else None, "kl": kl[0],
+                "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
+
+    @torch.no_grad()
+    def score(self, x, pose=None, targets=None, loss_mask=None, kl_weight=1.0, pose_multiplier=1000.0):
+        """Per-sample terms of ONE eval-mode forward of the modality subset ``x = [visual | None, tactile | None]`` (+ ``pose``)
+        against ``targets = [visual | None, tactile | None, pose | None]`` (default: the inputs that were given): a dict of
+        device tensors, all ``[B]`` -- ``bce_visual`` / ``bce_tactile`` (sum over (C, H, W) of BCE-with-logits; with ``loss_mask``
+        [B][1 or 3][H][W] both operands are multiplied by it first, problems.py:445-447), ``mse_pose`` (sum of the 7 squared
+        differences), ``kl`` (each sample's own KL; fp64) and ``rows`` = bce_visual + bce_tactile + pose_multiplier * mse_pose +
+        kl_weight * kl (fp32; a term without a target is left out and its entry is None) -- plus ``recon_x`` / ``means`` /
+        ``log_var`` of the pass.  Captured and replayed under a key of its own like :meth:`forward`; the tensors are the graph's
+        static outputs: copy them if they must survive the next call with the same shapes.  Forward only."""
+        visual, tactile = x
+        c = lambda t: None if t is None else t.contiguous()
+        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
+        if all(t is None for t in ins):
+            raise ValueError("score needs at least one modality")
+        B = next(t for t in ins if t is not None).shape[0]
+        self_target = targets is None
+        tg = [None] * 3 if self_target else [c(t) for t in (list(targets) + [None] * 3)[:3]]
+        if not self.use_pose:
+            tg[2] = None
+        for t, shape in zip(tg, ((B, 3), (B, 3), (B, 7))):
+            if t is not None and tuple(t.shape[:2]) != shape:
+                raise ValueError(f"target {tuple(t.shape)} does not match the batch of {B}")
+        if loss_mask is not None:
+            if (ins[2] is not None) if self_target else (tg[2] is not None):
+                raise ValueError("loss_mask is image-shaped and cannot multiply the (B, 7) pose term (score without a pose target)")
+            if loss_mask.dim() == 3:
+                loss_mask = loss_mask.unsqueeze(1)
+            if loss_mask.dim() != 4 or loss_mask.shape[0] != B or loss_mask.shape[1] not in (1, 3):
+                raise ValueError(f"loss_mask {tuple(loss_mask.shape)} is not [B={B}][1 or 3][H][W]")
+            loss_mask = loss_mask.to(torch.float32).contiguous()
+        if getattr(self, "_klw", None) is None:
+            self._klw = torch.zeros(1, device=self.dev)         # read from device memory: one captured graph serves every weight
+        self._klw.fill_(float(kl_weight))
+        self._pose_multiplier = float(pose_multiplier)
+        args = ins + tg + [loss_mask]
+        key = ("score", self_target, self._pose_multiplier) + tuple(None if t is None else tuple(t.shape) for t in args)
+        return self._run(key, lambda *a: self._score(self_target, *a), None, args)
 
     @torch.no_grad()
     def inference(self, n=1):

@@ -934,11 +934,17 @@ def decoder_forward_steps(P, buf, z, G=1, repeat=1, logits=True, packed=None, co
         if t["a"] is None and loss is not None:
             keep = loss.get("keep")
             out = _new(z, Bt if keep is None else Bg, 3, S, S)
-            c["dl"] = _new(z, Bt, 3, S, S) if loss["want_grad"] else None
-            ops.B.tconv_out3_bn_bce(t["y"], t["m"], t["r"], t["bn"].gamma, t["bn"].beta, P[f"hallucinate.{last}.weight"], out,
-                                    -1 if keep is None else keep, loss["target"], c["dl"], loss["acc"], loss["slots"],
-                                    loss["grad_scale"], G, Bg, H, H, mask=loss.get("mask"),
-                                    mask_channels=loss.get("mask_channels", 1), unmasked_slots=loss.get("acc_u"))
+            bn_args = (t["y"], t["m"], t["r"], t["bn"].gamma, t["bn"].beta, P[f"hallucinate.{last}.weight"], out,
+                       -1 if keep is None else keep, loss["target"])
+            mk = dict(mask=loss.get("mask"), mask_channels=loss.get("mask_channels", 1))
+            if loss.get("rows") is not None:
+                # per-sample scoring (evaluation only): the same epilogue, one sum per sample -> loss["rows"] [slots][Bg]
+                c["dl"] = None
+                ops.B.tconv_out3_bn_bce_rows(*bn_args, loss["rows"], loss["slots"], G, Bg, H, H, unmasked_rows=loss.get("rows_u"), **mk)
+            else:
+                c["dl"] = _new(z, Bt, 3, S, S) if loss["want_grad"] else None
+                ops.B.tconv_out3_bn_bce(*bn_args, c["dl"], loss["acc"], loss["slots"], loss["grad_scale"], G, Bg, H, H,
+                                        unmasked_slots=loss.get("acc_u"), **mk)
             c["loss_fused"] = True
             c.update(u0=u0, h0=h0, stages=stages)
             return out, c

@@ -286,6 +286,44 @@ class BCEWithLogitsSumFn(torch.autograd.Function):
         return _scaled(d, g), None, None
 
 
+def _loss_mask(mask, x):
+    """The loss mask as the kernels take it: [B][1 or C][H][W] contiguous, in the logits' dtype (anything else that broadcasts
+    against the logits is expanded to their shape first).  Returns (mask, mask_channels)."""
+    mk = mask.detach().to(x.dtype)
+    if mk.dim() != 4 or mk.shape[0] != x.shape[0] or mk.shape[2:] != x.shape[2:] or mk.shape[1] not in (1, x.shape[1]):
+        mk = mk.expand_as(x)
+    mk = mk.contiguous()
+    return mk, mk.shape[1]
+
+
+def bce_with_logits_rows_add(rows, logits, target, mask=None):
+    """rows[0][b] += torch.sum(F.binary_cross_entropy_with_logits(x, t, reduce=False), (1, 2, 3))[b], with the optional loss
+    mask of problems.py:445-447 (problems.py:409-416, 445-452).  rows: fp64 [1][B].  Forward only: no autograd node."""
+    x, t = logits.detach().contiguous(), target.detach().contiguous()
+    B = x.shape[0]
+    chw, hw = x.numel() // B, x.shape[-1] * x.shape[-2]
+    mk, mc = (None, 1) if mask is None else _loss_mask(mask, x)
+    ops.B.bce_logits_rows_groups(x, t, rows, [0], B, chw, mask=mk, hw=hw, mask_channels=mc)
+
+
+def mse_rows_add(rows, r, t):
+    """rows[0][b] += torch.sum(F.mse_loss(r, t, reduce=False), 1)[b] (problems.py:439-452).  rows: fp64 [1][B].  Forward only."""
+    rr, tt = r.detach().contiguous(), t.detach().contiguous()
+    ops.B.mse_rows_groups(rr, tt, rows, [0], rr.shape[0], rr.numel() // rr.shape[0])
+
+
+def elbo_rows(bce_rows, mse_rows, means, log_var, kl_weight, pose_multiplier):
+    """The reference's per-sample ELBO of ONE pass (problems.py:415-417, 451-456): recon rows + kl_weight * KL, where KL is the sum
+    over the WHOLE batch -- that one scalar goes into every row, and nothing is divided by B.  -> fp32 [B], no autograd node."""
+    B, L = means.shape
+    m, v = means.detach().contiguous(), log_var.detach().contiguous()
+    kl = torch.zeros(1, dtype=torch.float64, device=m.device)
+    ops.B.reparam_fwd(m, v, None, None, kl, B, L, L)
+    out = torch.empty(B, dtype=torch.float32, device=m.device)
+    ops.B.elbo_assemble_rows(bce_rows, mse_rows, None, kl, out, None, 1, B, kl_weight, pose_multiplier)
+    return out
+
+
 class MSESumFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, t):

@@ -528,6 +528,27 @@ class HipBackend:
                                                ctypes.addressof(slots), float(grad_scale), G, Bg, Hi, Wi, y16, _stream()),
               "mmdyn_tconv_out3_bn_bce")
 
+    def tconv_out3_bn_bce_rows(self, y, mean, rstd, gamma, beta, w, logits, logits_group, target, loss_rows, slot_of_group, G, Bg,
+                               Hi, Wi, mask=None, mask_channels=1, unmasked_rows=None):
+        """tconv_out3_bn_bce in evaluation with one sum per SAMPLE: loss_rows [n_slots][Bg] fp64, loss_rows[slot_of_group[g]][b] +=
+        the BCE-with-logits sum over sample b of group g.  No gradient output."""
+        py, y16 = _aptr(y)
+        if len(slot_of_group) != G or tuple(target.shape) != (Bg, 3, 2 * Hi, 2 * Wi):
+            raise ValueError("mmdyn_hip: tconv_out3_bn_bce_rows: one slot per group and a [Bg][3][2Hi][2Wi] target")
+        if logits is not None and logits.numel() != (G if logits_group < 0 else 1) * Bg * 3 * 4 * Hi * Wi:
+            raise ValueError("mmdyn_hip: tconv_out3_bn_bce_rows: logits buffer of the wrong size")
+        if mask is not None and tuple(mask.shape) != (Bg, mask_channels, 2 * Hi, 2 * Wi):
+            raise ValueError(f"mmdyn_hip: tconv_out3_bn_bce_rows: mask {tuple(mask.shape)} is not [Bg][{mask_channels}][2Hi][2Wi]")
+        n_slots = self._row_slots(loss_rows, Bg, "tconv_out3_bn_bce_rows")
+        if unmasked_rows is not None and self._row_slots(unmasked_rows, Bg, "tconv_out3_bn_bce_rows") != n_slots:
+            raise ValueError("mmdyn_hip: tconv_out3_bn_bce_rows: unmasked_rows and loss_rows differ in shape")
+        slots = (ctypes.c_int * G)(*[int(s) for s in slot_of_group])
+        check(self.lib.mmdyn_tconv_out3_bn_bce_rows(py, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(w), _ptr(logits),
+                                                    int(logits_group), _ptr(target), _ptr(mask), int(mask_channels),
+                                                    _ptr(loss_rows, torch.float64), _ptr(unmasked_rows, torch.float64),
+                                                    ctypes.addressof(slots), n_slots, G, Bg, Hi, Wi, y16, _stream()),
+              "mmdyn_tconv_out3_bn_bce_rows")
+
     def wgrad_out3_bn(self, y, mean, rstd, gamma, beta, Gt, partial, G, Bg, Hr, chunks):
         """Weight gradient of the last decoder layer with swish(BatchNorm(y)) recomputed on the operand fetch."""
         py, y16 = _aptr(y)
@@ -799,6 +820,64 @@ class HipBackend:
                                            _ptr(kl, torch.float64), _ptr(loss), _ptr(partials), P, B,
                                            float(kl_weight), float(pose_multiplier), _ptr(kl_weight_dev), _stream()),
               "mmdyn_elbo_assemble")
+
+    # ---- per-sample ELBO (evaluation only) ----
+    @staticmethod
+    def _row_slots(rows, Bg, name):
+        """Number of slots of a [n_slots][Bg] fp64 row table."""
+        if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != Bg:
+            raise ValueError(f"mmdyn_hip: {name}: the row table must be fp64 [n_slots][Bg={Bg}], got {rows.dtype} {tuple(rows.shape)}")
+        return rows.shape[0]
+
+    def bce_logits_rows_groups(self, logits, target, rows_out, slot_of_group, Bg, chw, mask=None, hw=0, mask_channels=1,
+                               unmasked_rows=None):
+        """logits: [G*Bg*chw]; target: [Bg*chw]; rows_out: fp64 [n_slots][Bg], rows_out[slot_of_group[g]][b] += the BCE-with-logits
+        sum over sample b of pass g (slot < 0 = discarded pass).  mask ([Bg][mask_channels][hw]): the --mask-loss form;
+        unmasked_rows then also gets the plain sums."""
+        G = len(slot_of_group)
+        n_slots = self._row_slots(rows_out, Bg, "bce_logits_rows_groups")
+        if logits.numel() != G * Bg * chw or target.numel() != Bg * chw:
+            raise ValueError(f"mmdyn_bce_logits_rows_groups: logits of {logits.numel()} / target of {target.numel()} elements do "
+                             f"not match [G={G}][Bg={Bg}][chw={chw}]")
+        if mask is not None and (hw <= 0 or mask.numel() != Bg * mask_channels * hw):
+            raise ValueError(f"mmdyn_bce_logits_rows_groups: mask of {mask.numel()} elements does not match "
+                             f"[Bg={Bg}][{mask_channels}][hw={hw}]")
+        if unmasked_rows is not None and self._row_slots(unmasked_rows, Bg, "bce_logits_rows_groups") != n_slots:
+            raise ValueError("mmdyn_bce_logits_rows_groups: unmasked_rows and rows_out differ in shape")
+        slots = (ctypes.c_int * G)(*[int(s) for s in slot_of_group])
+        check(self.lib.mmdyn_bce_logits_rows_groups(_ptr(logits), _ptr(target), _ptr(mask), int(mask_channels),
+                                                    _ptr(rows_out, torch.float64), _ptr(unmasked_rows, torch.float64),
+                                                    ctypes.addressof(slots), n_slots, G, Bg, chw, hw, _stream()),
+              "mmdyn_bce_logits_rows_groups")
+
+    def mse_rows_groups(self, r, t, rows_out, slot_of_group, Bg, n):
+        """r: [G*Bg*n]; t: [Bg*n]; rows_out: fp64 [n_slots][Bg], rows_out[slot_of_group[g]][b] += sum_n (r - t)^2."""
+        G = len(slot_of_group)
+        n_slots = self._row_slots(rows_out, Bg, "mse_rows_groups")
+        if r.numel() != G * Bg * n or t.numel() != Bg * n:
+            raise ValueError(f"mmdyn_mse_rows_groups: r of {r.numel()} / t of {t.numel()} elements do not match [G={G}][Bg={Bg}][n={n}]")
+        slots = (ctypes.c_int * G)(*[int(s) for s in slot_of_group])
+        check(self.lib.mmdyn_mse_rows_groups(_ptr(r), _ptr(t), _ptr(rows_out, torch.float64), ctypes.addressof(slots), n_slots, G,
+                                             Bg, n, _stream()), "mmdyn_mse_rows_groups")
+
+    def kl_rows(self, mu, logvar, kl_rows, P, B, L):
+        """mu / logvar: [P][B][L] (contiguous); kl_rows: fp64 [P][B] = -0.5 * sum_L (1 + lv - mu^2 - exp(lv))."""
+        if mu.numel() != P * B * L or logvar.numel() != P * B * L or kl_rows.numel() != P * B:
+            raise ValueError(f"mmdyn_kl_rows: tensors do not match [P={P}][B={B}][L={L}]")
+        check(self.lib.mmdyn_kl_rows(_ptr(mu), _ptr(logvar), _ptr(kl_rows, torch.float64), P, B, L, _stream()), "mmdyn_kl_rows")
+
+    def elbo_assemble_rows(self, bce_rows, mse_rows, kl_rows, kl_sum, out, partials, P, B, kl_weight, pose_multiplier,
+                           kl_weight_dev=None, kl_mode=0):
+        """out [B] / partials [P][B] fp32 from the fp64 [P][B] row tables; kl_mode 0: the reference's row (kl_weight * kl_sum[p],
+        the batch total, in every row), 1: kl_weight * kl_rows[p][b].  No division by B."""
+        for t, n, what in ((bce_rows, P * B, "bce_rows"), (mse_rows, P * B, "mse_rows"), (kl_rows, P * B, "kl_rows"),
+                           (kl_sum, P, "kl_sum"), (partials, P * B, "partials"), (out, B, "out")):
+            if t is not None and t.numel() < n:
+                raise ValueError(f"mmdyn_elbo_assemble_rows: {what} holds {t.numel()} elements, needs {n}")
+        check(self.lib.mmdyn_elbo_assemble_rows(_ptr(bce_rows, torch.float64), _ptr(mse_rows, torch.float64),
+                                                _ptr(kl_rows, torch.float64), _ptr(kl_sum, torch.float64), _ptr(out),
+                                                _ptr(partials), P, B, float(kl_weight), float(pose_multiplier),
+                                                _ptr(kl_weight_dev), int(kl_mode), _stream()), "mmdyn_elbo_assemble_rows")
 
     def adam_step(self, p, g, m, v, state, lr, beta1, beta2, eps, grad_scale, guarded=False):
         """guarded: ``state`` has six doubles and a gradient holding inf / NaN skips the step (counted in state[4])."""

@@ -4,7 +4,7 @@ Mirrors the parts of /root/reference/mmdyn/pytorch/problems/problems.py that dri
 ``Problem`` (ctor flags, ``set_optimizer`` :130-138, ``_train_epoch`` step body :148-156,
 ``_test_epoch`` :173-191, ``train`` :193-210, ``_anneal_KL`` :212-216), ``Reconstruction``
 (``set_model`` :367-389, ``_elbo_loss`` :401-419, ``_mvae_elbo_loss`` :421-458, ``_evaluate_mvae``
-:473-546, best-validation checkpoint :580-586), ``SeqModeling`` (``parse_input`` :634-673,
+:473-546, each with the per-sample ``reduce=False`` branch, best-validation checkpoint :580-586), ``SeqModeling`` (``parse_input`` :634-673,
 ``_evaluate_model`` :683-716) and ``DynModeling.parse_input`` (:765-803).
 
 Out of scope here: the PNG/json dataset reader, TensorBoard image/figure logging,
@@ -313,6 +313,17 @@ class Problem:
                 pickle.dump(dict(self._logger_dict), f)
         return perf
 
+    def score(self, data_input, data_target):
+        """Per-sample ELBO of one batch in the loader's format: ``parse_input``, then ``_evaluate_model(..., reduce=False)`` without
+        autograd -> fp32 ``[B]``, one value per sample, in whatever mode (train / eval) the model is in.  The rows are the
+        reference's (problems.py:415-417, 451-456): each holds the sample's own reconstruction terms plus ``kl_weight`` times the
+        KL of the WHOLE batch, summed over the subset passes, and nothing is divided by B -- so ``rows.mean()`` is not the scalar
+        loss, and differences between rows of one batch are differences of reconstruction error only."""
+        inputs, targets = self.parse_input(data_input, data_target)
+        with torch.no_grad():
+            _, rows = self._evaluate_model(inputs, targets, reduce=False)
+        return rows
+
     # ---- fused-engine plumbing -------------------------------------------------------------------
     def _fused_applicable(self, inputs):
         return isinstance(inputs, dict) and isinstance(inputs.get('model_input'), list)
@@ -425,10 +436,25 @@ class Reconstruction(Problem):
     def set_criterion(self):
         self._criterion = self._mvae_elbo_loss if 'mvae' in self.parameters['model_name'] else self._elbo_loss
 
+    @staticmethod
+    def _check_reduce(reduce, reduction):
+        """torch's legacy ``reduce`` flag: False turns ``reduction`` into 'none' whatever it says -- the per-sample branch."""
+        if reduce:
+            raise NotImplementedError("mmdyn_hip: reduce=True (the legacy spelling of reduction='sum' without the division by B) "
+                                      "is not built; use reduce=None for the scalar loss or reduce=False for the per-sample one")
+        if reduce is None and reduction != 'sum':
+            raise NotImplementedError("mmdyn_hip: reduction=%r with reduce=None is not built (reduce=None, reduction='sum' is the "
+                                      "scalar loss; reduce=False the per-sample one)" % (reduction,))
+
     def _elbo_loss(self, recon_x, x, means, log_var, loss_mask=None, reduce=None, reduction='sum'):
-        """(BCE_sum + kl_weight * KL) / B for VAE / CVAE (problems.py:401-419, reduce=None branch)."""
-        if reduce is not None or reduction != 'sum':
-            raise NotImplementedError("mmdyn_hip: per-sample (reduce) losses are never used by main.py")
+        """(BCE_sum + kl_weight * KL) / B for VAE / CVAE (problems.py:401-419).  ``reduce=False``: the reference's per-sample
+        branch (:415-417), a fp32 ``[B]`` tensor ``sum(BCE, (1, 2, 3)) + kl_weight * KL`` where KL is the total over the batch
+        (not divided by B).  That branch is forward only: the result carries no autograd graph, ``.backward()`` on it raises."""
+        self._check_reduce(reduce, reduction)
+        if reduce is not None:
+            rows = torch.zeros(1, x.size(0), dtype=torch.float64, device=x.device)
+            Fn.bce_with_logits_rows_add(rows, recon_x.view(x.size()), x, loss_mask)
+            return Fn.elbo_rows(rows, None, means, log_var, self._kl_weight, self._pose_multiplier)
         batch_size = x.size(0)
         KLD = Fn.KLFn.apply(means, log_var)
         BCE = Fn.BCEWithLogitsSumFn.apply(recon_x.view(x.size()), x, loss_mask)
@@ -436,10 +462,25 @@ class Reconstruction(Problem):
 
     def _mvae_elbo_loss(self, recon_x, x, means, log_var, loss_mask=None, reduce=None, reduction='sum'):
         """Sum over modalities of BCE (images) / pose_multiplier * MSE (pose) + kl_weight * KL, over B
-        (problems.py:421-458, reduce=None branch)."""
-        if reduce is not None or reduction != 'sum':
-            raise NotImplementedError("mmdyn_hip: per-sample (reduce) losses are never used by main.py")
+        (problems.py:421-458).  ``reduce=False``: the reference's per-sample branch (:451-456), a fp32 ``[B]`` tensor of the
+        reconstruction terms of each sample plus ``kl_weight`` times the KL of the WHOLE batch, nothing divided by B.  Forward only:
+        the result carries no autograd graph, ``.backward()`` on it raises."""
+        self._check_reduce(reduce, reduction)
         assert len(recon_x) == len(x)
+        if reduce is not None:
+            B, dev = x[0].size(0), x[0].device
+            bce, mse = torch.zeros(1, B, dtype=torch.float64, device=dev), None
+            for i in range(len(recon_x)):
+                if len(recon_x[i].size()) > 2:
+                    Fn.bce_with_logits_rows_add(bce, recon_x[i].view(x[i].size()), x[i], loss_mask)
+                else:
+                    if loss_mask is not None:
+                        raise ValueError("loss_mask is image-shaped and cannot multiply the (B, 7) pose term "
+                                         "(the reference raises here too: problems.py:445-447)")
+                    if mse is None:
+                        mse = torch.zeros(1, B, dtype=torch.float64, device=dev)
+                    Fn.mse_rows_add(mse, recon_x[i], x[i])
+            return Fn.elbo_rows(bce, mse, means, log_var, self._kl_weight, self._pose_multiplier)
         batch_size = x[0].size(0)
         recon_error = 0
         kl_divergence = Fn.KLFn.apply(means, log_var)
@@ -454,16 +495,17 @@ class Reconstruction(Problem):
             recon_error = recon_error + e
         return (recon_error + self._kl_weight * kl_divergence) / batch_size
 
-    def _evaluate_model(self, x, targets, **kwargs):
+    def _evaluate_model(self, x, targets, reduce=None, reduction='sum', **kwargs):
         if 'mvae' in self.parameters['model_name']:
-            return self._evaluate_mvae(x=x, targets=x)
+            return self._evaluate_mvae(x=x, targets=x, reduce=reduce, reduction=reduction)
         recon_x, means, log_var = self._model(x)
-        loss = self._criterion(recon_x, x, means, log_var)
+        loss = self._criterion(recon_x, x, means, log_var, reduce=reduce, reduction=reduction)
         return {'recon_x': recon_x, 'means': means, 'log_var': log_var}, loss
 
     def _evaluate_mvae(self, x, targets, loss_mask=None, reduce=None, reduction='sum', condition=None):
         """The reference's 3- or 7-subset schedule, one full model call per subset (problems.py:473-546)."""
         assert isinstance(x, list) and isinstance(targets, list)
+        self._check_reduce(reduce, reduction)          # (before the first model call draws noise and moves running statistics)
         kw = dict(loss_mask=loss_mask, reduce=reduce, reduction=reduction)
         m = self._model
         v_joint, t_joint, _, means, log_var = m([x[0], x[1]], condition=condition)
@@ -541,9 +583,17 @@ class SeqModeling(Reconstruction):
                 {'target_output': to, 'target_object_pose': pose_t, 'loss_mask': mask})
 
     def _evaluate_model(self, x, targets, reduction='sum', reduce=None, **kwargs):
+        self._check_reduce(reduce, reduction)
         loss_mask = targets['loss_mask'] if self.parameters['mask_loss'] else None
         if 'mvae' in self.parameters['model_name']:
             xs, ts = self._fused_io(x, targets)
+            if reduce is False and getattr(self, '_step', None) is not None and self._fused_applicable(x):
+                # the fused engine's evaluation schedule ending in the row kernels (the reference's rows: batch-total KL)
+                res = self._step.score_step(xs, ts, self._kl_weight, loss_mask=loss_mask,
+                                            condition=x.get('shock') if self._conditional else None, kl="batch")
+                last = self._step.last
+                return {'recon_x': last['recon_x'], 'means': last['means'], 'log_var': last['log_var'],
+                        'perf_measure': self._fused_perf()}, res['rows']
             return self._evaluate_mvae(x=xs, targets=ts, loss_mask=loss_mask, reduce=reduce, reduction=reduction,
                                        condition=x.get('shock'))
         if self._conditional:
