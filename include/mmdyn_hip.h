@@ -570,6 +570,22 @@ int mmdyn_tconv_out3_fwd_b16(const uint16_t* a, const float* w, float* out, int 
 int mmdyn_nchw_to_nhwc(const float* in, float* out, int B, int C, int HW, void* stream);
 int mmdyn_nhwc_to_nchw(const float* in, float* out, int B, int C, int HW, void* stream);
 
+/* ---- conditional models: the operand join ------------------------------------------------------
+ * out [rows][width] = [x | condition | 0]: out[r][0:K) = x[r][0:K) (x has its own row stride ldx >= K), out[r][K:K+cd) = the
+ * condition of row r, out[r][K+cd:width) = 0.  width % 32 == 0 (the K-step of the GEMM that consumes out), K + cd <= width.
+ * Exactly one condition source is non-null (MMDYN_ERR_NULL otherwise):
+ *   cond     [rows][cd] fp32 : real-valued conditions -- torch.cat((x, c.float()), dim=-1), vae.py:231-237 (encoder heads) and
+ *                              vae.py:286-291 (decoder input);
+ *   cond_idx [rows] int64    : categorical conditions -- the one-hot row of idx2onehot (vae.py:337-344: the assert, the
+ *                              torch.zeros and the scatter_) is written by the kernel; no one-hot tensor exists in memory.
+ * An index outside [0, cd) is input, not a fault: that row's condition block is all zero and bit 0 of *bad_index (nullable) is
+ * OR-ed in; the caller clears the word and reads it where it synchronises anyway (the reference asserts with a host read-back,
+ * vae.py:338).  Every element of out is written, the padding included.  Pure copy: bit-identical to torch.cat + zero padding.
+ * One launch (16-byte accesses when K % 4 == 0, ldx % 4 == 0 and x / out are 16-byte aligned, one element per thread otherwise);
+ * replaces the memset + two mmdyn_repack2d_ld launches per consumer. */
+int mmdyn_concat_condition(const float* x, const float* cond, const int64_t* cond_idx, float* out, int* bad_index, int rows,
+                           int K, int ldx, int cd, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

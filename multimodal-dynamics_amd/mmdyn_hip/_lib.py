@@ -123,6 +123,7 @@ _SIGNATURES = {
     "mmdyn_mse_rows_groups": "pppp" + "iiii" + "p",
     "mmdyn_kl_rows": "ppp" + "iii" + "p",
     "mmdyn_elbo_assemble_rows": "pppppp" + "ii" + "ff" + "p" + "i" + "p",
+    "mmdyn_concat_condition": "ppppp" + "iiiii" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

@@ -241,6 +241,11 @@ class MVAEStep:
         # --conditional (vae.py:231-237, 286-291): the condition joins the 512 features in front of the image encoders' heads
         # and the latent in front of the image decoders' first layer; the pose MLPs are built unconditional (vae.py:117-123)
         self.conditional = bool(getattr(model, "conditional", False))
+        # categorical conditions (vae.py:337-344): class indices [B]; the join kernel writes the one-hot rows and ORs bit 0 into
+        # this engine-owned word for an index outside [0, condition_dim) -- cleared by the step's pre-phase (inside the captured
+        # region), read by check_condition()
+        self.categorical = self.conditional and bool(getattr(model, "categorical_conditions", False))
+        self._bad_index = None
         # False (default): the image decoders' logits are materialised only for the pass whose reconstruction the caller receives
         # (outputs['recon_x'] = the joint pass: problems.py:537-545) -- the BCE term and dlogits come out of the last layer's
         # epilogue.  True: the logits of every live pass are written as well (self.last["logits_v" / "logits_t"])
@@ -443,9 +448,11 @@ class MVAEStep:
         self._set_kl_weight(kl_weight)
         if self.conditional:
             from .models.vae import _condition
-            condition = _condition(condition, True).to(torch.float32).contiguous()
-            if condition.dim() != 2 or condition.shape[0] != inputs[0].shape[0]:
+            condition = _condition(condition, True, self.categorical)
+            if condition.dim() != (1 if self.categorical else 2) or condition.shape[0] != inputs[0].shape[0]:
                 raise ValueError(f"condition {tuple(condition.shape)} does not match the batch of {inputs[0].shape[0]}")
+            if self.categorical and self._bad_index is None:
+                self._bad_index = torch.zeros(1, dtype=torch.int32, device=inputs[0].device)
         elif condition is not None:
             raise ValueError("a condition was passed to an unconditional model")
         if loss_mask is not None:
@@ -492,6 +499,8 @@ class MVAEStep:
         c["mask"] = {"v": mv, "t": mt}
         LN.join()
         self.acc.zero_()
+        if self._bad_index is not None:
+            self._bad_index.zero_()
         if self._hg_grad is not None:
             # operand of the grouped heads launch: the (dropped-out) features of every pass of every encoder, group-major
             c["hg_rows"] = len(self.pass_v) * c["B"]
@@ -521,7 +530,7 @@ class MVAEStep:
             return
         hd = torch.empty(n * B, 512, device=c["dev"])
         ops.B.dropout_expand(h, c["mask"][m], hd, n, B, 512, DROPOUT_P)
-        cond = None if c["cond"] is None else c["cond"].repeat(n, 1)           # the same condition rows for every pass
+        cond = layers.repeat_condition(c["cond"], n)                           # the same condition rows for every pass
         c["o" + m], c["h" + m] = layers.heads_forward(FP.sub(enc), hd, c["pk"].get("h" + m), cond=cond)
 
     def _ph_pose_enc(self):
@@ -592,7 +601,7 @@ class MVAEStep:
         c, FP, B = self.ctx, self.params, self.ctx["B"]
         dec, plist, live = self._MOD[m][1], self._dec_passes(m), self._passes_of(m)
         zz = c["zz" + m]
-        cond = None if c["cond"] is None else c["cond"].repeat(len(plist), 1)
+        cond = layers.repeat_condition(c["cond"], len(plist))
         # every live pass of the modality against the same target: one loss slot per pass
         # (slot -1: exact_running_stats ran a pass whose reconstruction is discarded -- zero gradient, no loss)
         tg, mk = c["tg"][m], c["lmask"]
@@ -767,10 +776,15 @@ class MVAEStep:
     def forward(self, inputs, targets, kl_weight, train=True, loss_mask=None, condition=None, rows=False):
         """Runs the forward schedule and the loss; with train=True also fills the loss gradients needed by
         :meth:`backward`.  Returns the device scalar loss (fp32).  ``loss_mask`` ([B][1 or C][H][W], models without pose):
-        the reference's --mask-loss, multiplying logits and targets of every image term.  ``condition`` ([B][condition_dim]):
-        the shock force of the --conditional models."""
-        LN = self.lanes
+        the reference's --mask-loss, multiplying logits and targets of every image term.  ``condition``: the condition of the
+        --conditional models -- [B][condition_dim] real values (the shock force), or class indices [B] / [B,1] of any integer
+        dtype for a categorical model (an index out of range: :meth:`check_condition`)."""
         self._begin(inputs, targets, kl_weight, train, loss_mask, condition)
+        with layers.bad_index_into(self._bad_index):
+            return self._forward_schedule(rows, train)
+
+    def _forward_schedule(self, rows, train):
+        LN = self.lanes
         if rows:
             if train:
                 raise ValueError("per-sample rows are an evaluation result (train=False): there is no gradient path")
@@ -790,6 +804,17 @@ class MVAEStep:
         self._ph_assemble()
         self._publish()
         return self.loss
+
+    def bad_condition(self):
+        """True when the most recent step of a categorical model held a class index outside [0, condition_dim): those rows ran
+        with an all-zero condition block.  One 4-byte read from the device -- a synchronisation; no step makes it on its own."""
+        return bool(self._bad_index is not None and int(self._bad_index.item()))
+
+    def check_condition(self):
+        """Raises ValueError where the reference asserts (vae.py:338).  Call it where the host synchronises anyway -- next to the
+        read-back of the loss -- so that the step itself stays free of synchronisation."""
+        if self.bad_condition():
+            raise ValueError(f"categorical condition outside [0, {self.model.condition_dim}) in the last step")
 
     def _passes(self, c, B, dheads, dz_blocks=None):
         """Per-pass expert descriptors: row block of each modality's fused heads output."""
@@ -894,8 +919,8 @@ class MVAEStep:
         key = tuple(tuple(x.shape) for x in inputs) + ((tuple(loss_mask.shape),) if loss_mask is not None else ())
         if condition is not None:
             from .models.vae import _condition
-            condition = _condition(condition, True).to(torch.float32)
-            key += (("cond",) + tuple(condition.shape),)
+            condition = _condition(condition, True, self.categorical)
+            key += (("cond", str(condition.dtype)) + tuple(condition.shape),)
         self._set_kl_weight(kl_weight)
         if self._graph is None or self._graph[0] != key:
             self._static_in = [x.clone() for x in inputs]
@@ -1085,6 +1110,8 @@ class MVAEStep:
         self._capturing = True
         lanes_on, LN.on = LN.on, False            # inside a lane graph everything stays on the capture stream ...
         captured = []
+        bad_scope = layers.bad_index_into(self._bad_index)
+        bad_scope.__enter__()
         try:
             self._begin(self._static_in, self._static_tg, kl_weight, True, self._static_mask, self._static_cond)
             for stage in stages:
@@ -1104,6 +1131,7 @@ class MVAEStep:
             LN.on = lanes_on
             layers.CUR_LANE = None
             self.ctx = None
+            bad_scope.__exit__(None, None, None)
         return captured
 
     DEC_STAGE = 3          # index of the decoder forward+backward stage in _capture's list
@@ -1226,16 +1254,26 @@ class MVAEInference:
     operand form ONCE (``refresh()`` after loading new weights); the visual and the tactile halves run on two HIP
     streams; and the whole forward for a given (batch shape, modality subset) is captured into a HIP graph on first
     use and replayed afterwards, so a request costs one graph launch.  Latent draws come from the device-side Philox
-    stream, so replays draw fresh noise."""
+    stream, so replays draw fresh noise.
+
+    Conditional models (--conditional, real-valued or categorical) are served too: ``forward`` / ``score`` take ``condition=``,
+    ``inference`` takes ``c``.  The condition is joined to the 512 features in front of each image encoder's heads and to the
+    latent in front of each image decoder by one mmdyn_concat_condition launch per consumer (four for a joint request); the
+    packed head / up-sampling weights carry the condition columns, zero-padded to the GEMM's K-step.  A categorical model takes
+    class indices; its one-hot rows are written by the join kernel.  :meth:`bad_condition` reports an index out of range."""
 
     def __init__(self, model, precision="fp32x3", use_graph=True, seed=0):
         from .models.vae import NoiseSource
-        if getattr(model, "conditional", False):
-            raise NotImplementedError("mmdyn_hip: MVAEInference is built for the unconditional cnn-mvae")
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'fp32x3' (default), 'fp32', 'bf16' / 'fp16' (matrix-core operands) or 'bf16s' / 'fp16s' (+ 16-bit "
                              "activation storage)")
         self.model, self.precision, self.use_graph = model, precision, use_graph
+        # --conditional (vae.py:231-237, 286-291): the condition joins the 512 features in front of the image encoders' heads and
+        # the latent in front of the image decoders' first layer; the pose MLPs are built unconditional (vae.py:117-123)
+        self.conditional = bool(getattr(model, "conditional", False))
+        self.categorical = self.conditional and bool(getattr(model, "categorical_conditions", False))
+        self.condition_dim = int(model.condition_dim or 0) if self.conditional else 0
+        self._bad = None                       # int32 [1]: bit 0 = the last request held a class index outside [0, condition_dim)
         self.use_pose = bool(model._use_pose)
         self.L = model.latent_size
         self.dev = next(model.parameters()).device
@@ -1298,12 +1336,48 @@ class MVAEInference:
                 del layers.PLANE_TWIN[ptr]
 
     # ---- the forward itself (eager; captured by _graphed) -------------------------------------------------
-    def _encode(self, key, x):
+    def _condition(self, condition, B):
+        """The request's condition in the form the join kernel takes (fp32 [B, condition_dim], or int64 class indices [B] for a
+        categorical model), on the engine's device; ValueError when it is missing, surplus or of the wrong shape."""
+        if not self.conditional:
+            if condition is not None:
+                raise ValueError("a condition was passed to an unconditional model")
+            return None
+        from .models.vae import _condition
+        cond = _condition(condition, True, self.categorical).to(self.dev)
+        want = (B,) if self.categorical else (B, self.condition_dim)
+        if tuple(cond.shape) != want:
+            raise ValueError(f"condition {tuple(cond.shape)} does not match the batch of {B} (condition_dim = {self.condition_dim})")
+        return cond
+
+    def _cond_key(self, cond):
+        return None if cond is None else ("index" if self.categorical else "real",) + tuple(cond.shape)
+
+    def _index_scope(self):
+        """Installs the engine's bad-index word for the join launches of one request and clears it first -- inside the captured
+        region, so every replay starts from a clear word."""
+        if self.categorical:
+            if self._bad is None:
+                self._bad = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            self._bad.zero_()
+        return layers.bad_index_into(self._bad)
+
+    def bad_condition(self):
+        """True when the most recent request of a categorical model held a class index outside [0, condition_dim): such a row
+        was served with an all-zero condition block (the reference asserts, vae.py:338).  One 4-byte read from the device: a
+        synchronisation, which :meth:`forward` / :meth:`score` / :meth:`inference` do not make on their own."""
+        return bool(self._bad is not None and int(self._bad.item()))
+
+    def _encode(self, key, x, cond=None):
         h, _ = layers.run(layers.encoder_trunk_forward_steps(self.P[key], self.buf[key], x, packed=self.pk[key],
                                                              training=False))
-        return layers.heads_forward(self.P[key], h, self.pk[key[0] + "h"])[0]
+        return layers.heads_forward(self.P[key], h, self.pk[key[0] + "h"], cond=cond)[0]
 
-    def _forward(self, visual, tactile, pose):
+    def _forward(self, visual, tactile, pose, cond=None):
+        with self._index_scope():
+            return self._forward_scoped(visual, tactile, pose, cond)
+
+    def _forward_scoped(self, visual, tactile, pose, cond):
         LN, L = self.lanes, self.L
         ref = visual if visual is not None else (tactile if tactile is not None else pose)
         B = ref.shape[0]
@@ -1311,10 +1385,10 @@ class MVAEInference:
         LN.fork()
         if visual is not None:
             with LN.lane(0):
-                heads[0] = self._encode("ve", visual)
+                heads[0] = self._encode("ve", visual, cond)
         if tactile is not None:
             with LN.lane(1):
-                heads[1] = self._encode("te", tactile)
+                heads[1] = self._encode("te", tactile, cond)
         if pose is not None and self.use_pose:
             hp, _ = layers.pose_encoder_trunk_forward(self.P["pe"], pose)
             heads[2] = layers.heads_forward(self.P["pe"], hp, self.pk["ph"])[0]
@@ -1324,23 +1398,24 @@ class MVAEInference:
         p = {"mu": [None if h is None else h[:, :L] for h in heads], "lv": [None if h is None else h[:, L:] for h in heads],
              "dmu": [None] * 3, "dlv": [None] * 3, "ld": [2 * L] * 3}
         ops.B.poe_fwd([p], eps, mu, lv, z, None, True, 1, B, L)
-        return self._decode(z) + (mu, lv)
+        return self._decode(z, cond) + (mu, lv)
 
-    def _decode(self, z):
+    def _decode(self, z, cond=None):
         LN = self.lanes
         LN.fork()
         with LN.lane(0):
-            v, _ = layers.run(layers.decoder_forward_steps(self.P["vd"], self.buf["vd"], z, packed=self.pk["vd"],
+            v, _ = layers.run(layers.decoder_forward_steps(self.P["vd"], self.buf["vd"], z, packed=self.pk["vd"], cond=cond,
                                                            training=False))
         with LN.lane(1):
-            t, _ = layers.run(layers.decoder_forward_steps(self.P["td"], self.buf["td"], z, packed=self.pk["td"],
+            t, _ = layers.run(layers.decoder_forward_steps(self.P["td"], self.buf["td"], z, packed=self.pk["td"], cond=cond,
                                                            training=False))
         pr = layers.pose_decoder_forward(self.P["pd"], z)[0] if self.use_pose else None
         LN.join()
         return v, t, pr
 
-    def _sample(self, n):
-        return self._decode(self._draw_latent(n))[:2]
+    def _sample(self, n, cond=None):
+        with self._index_scope():
+            return self._decode(self._draw_latent(n), cond)[:2]
 
     def _draw_latent(self, n):
         """[n, L] standard-normal draw; the commit moves the stream position into the device counter, inside the
@@ -1385,23 +1460,31 @@ class MVAEInference:
             layers.W_DTYPE = prev_w
 
     @torch.no_grad()
-    def forward(self, x, pose=None):
+    def forward(self, x, pose=None, condition=None):
         """``MVAE.forward`` semantics: x = [visual | None, tactile | None]; returns (visual_recon, tactile_recon,
-        pose_recon | None, means, log_var) -- logits, like the reference.  The returned tensors are the graph's static
-        outputs: copy them if they must survive the next call with the same shapes."""
+        pose_recon | None, means, log_var) -- logits, like the reference.  ``condition`` (conditional models; ValueError when it
+        is missing, or given to an unconditional model): [B, condition_dim] real values, or class indices [B] / [B,1] of any
+        integer dtype for a categorical model.  It is a static input of the captured graph -- the key carries its shape and
+        kind -- so a replay with a new condition of the same shape gives that condition's result.  An index outside
+        [0, condition_dim) is served as an all-zero condition block and reported by :meth:`bad_condition`; forward itself does
+        not synchronise.  The returned tensors are the graph's static outputs: copy them if they must survive the next call with
+        the same shapes."""
         visual, tactile = x
         c = lambda t: None if t is None else t.contiguous()
         ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        key = ("fwd",) + tuple(None if t is None else tuple(t.shape) for t in ins)
-        return self._run(key, self._forward, None, ins)
+        if all(t is None for t in ins):
+            raise ValueError("forward needs at least one modality")
+        cond = self._condition(condition, next(t for t in ins if t is not None).shape[0])
+        key = ("fwd",) + tuple(None if t is None else tuple(t.shape) for t in ins) + (self._cond_key(cond),)
+        return self._run(key, self._forward, None, ins + [cond])
 
     __call__ = forward
 
-    def _score(self, self_target, visual, tactile, pose, tv, tt, tp, mask):
+    def _score(self, self_target, visual, tactile, pose, tv, tt, tp, mask, cond=None):
         """One forward of the given subset, then the per-sample terms of that pass: the row kernels on the logits, the pose
         reconstruction and the posterior the forward left on the device.  Tables (fp64 [2][B], zeroed by a fill that a captured
         graph replays): bce = (visual, tactile), mse = (pose, 0), kl = (KL, 0); the assembly adds the two rows of each table."""
-        v, t, pr, mu, lv = self._forward(visual, tactile, pose)
+        v, t, pr, mu, lv = self._forward(visual, tactile, pose, cond)
         if self_target:
             tv, tt, tp = visual, tactile, pose if self.use_pose else None
         B, L = mu.shape
@@ -1421,7 +1504,7 @@ class MVAEInference:
                 "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
 
     @torch.no_grad()
-    def score(self, x, pose=None, targets=None, loss_mask=None, kl_weight=1.0, pose_multiplier=1000.0):
+    def score(self, x, pose=None, targets=None, loss_mask=None, kl_weight=1.0, pose_multiplier=1000.0, condition=None):
         """Per-sample terms of ONE eval-mode forward of the modality subset ``x = [visual | None, tactile | None]`` (+ ``pose``)
         against ``targets = [visual | None, tactile | None, pose | None]`` (default: the inputs that were given): a dict of
         device tensors, all ``[B]`` -- ``bce_visual`` / ``bce_tactile`` (sum over (C, H, W) of BCE-with-logits; with ``loss_mask``
@@ -1429,13 +1512,15 @@ class MVAEInference:
         differences), ``kl`` (each sample's own KL; fp64) and ``rows`` = bce_visual + bce_tactile + pose_multiplier * mse_pose +
         kl_weight * kl (fp32; a term without a target is left out and its entry is None) -- plus ``recon_x`` / ``means`` /
         ``log_var`` of the pass.  Captured and replayed under a key of its own like :meth:`forward`; the tensors are the graph's
-        static outputs: copy them if they must survive the next call with the same shapes.  Forward only."""
+        static outputs: copy them if they must survive the next call with the same shapes.  Forward only.  ``condition``: as in
+        :meth:`forward` (required by a conditional model)."""
         visual, tactile = x
         c = lambda t: None if t is None else t.contiguous()
         ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
         if all(t is None for t in ins):
             raise ValueError("score needs at least one modality")
         B = next(t for t in ins if t is not None).shape[0]
+        cond = self._condition(condition, B)
         self_target = targets is None
         tg = [None] * 3 if self_target else [c(t) for t in (list(targets) + [None] * 3)[:3]]
         if not self.use_pose:
@@ -1457,9 +1542,12 @@ class MVAEInference:
         self._pose_multiplier = float(pose_multiplier)
         args = ins + tg + [loss_mask]
         key = ("score", self_target, self._pose_multiplier) + tuple(None if t is None else tuple(t.shape) for t in args)
+        key, args = key + (self._cond_key(cond),), args + [cond]
         return self._run(key, lambda *a: self._score(self_target, *a), None, args)
 
     @torch.no_grad()
-    def inference(self, n=1):
-        """``MVAE.inference``: z ~ N(0, I) -> (visual, tactile) logits."""
-        return self._run(("sample", int(n)), lambda: self._sample(int(n)), None, [])
+    def inference(self, n=1, c=None):
+        """``MVAE.inference(n, c)`` (vae.py:167-176): z ~ N(0, I) -> (visual, tactile) logits; ``c``: the n conditions of a
+        conditional model, as in :meth:`forward`."""
+        cond = self._condition(c, int(n))
+        return self._run(("sample", int(n), self._cond_key(cond)), lambda c_: self._sample(int(n), c_), None, [cond])

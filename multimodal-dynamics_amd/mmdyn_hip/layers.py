@@ -457,11 +457,54 @@ def _pad32(n):
     return (n + 31) // 32 * 32
 
 
-def concat_condition(x, cond, width):
+# Where the one-launch join reports a categorical index outside [0, condition_dim): an int32 [1] device word, or None.  The caller
+# that owns the word (an eager model call, an engine) installs it around its launches with ``bad_index_into``, clears it before and
+# reads it where it synchronises anyway.
+_BAD_INDEX = None
+
+
+class bad_index_into:
+    def __init__(self, word):
+        self.word = word
+
+    def __enter__(self):
+        global _BAD_INDEX
+        self.prev, _BAD_INDEX = _BAD_INDEX, self.word
+        return self.word
+
+    def __exit__(self, *exc):
+        global _BAD_INDEX
+        _BAD_INDEX = self.prev
+
+
+def is_index_condition(cond):
+    """Categorical conditions travel as int64 class indices [rows]; real-valued ones as fp32 [rows, cd]."""
+    return cond is not None and cond.dtype == torch.int64
+
+
+def repeat_condition(cond, n):
+    """The same condition rows for each of ``n`` stacked passes."""
+    if cond is None or n == 1:
+        return cond
+    return cond.repeat(n) if is_index_condition(cond) else cond.repeat(n, 1)
+
+
+def concat_condition(x, cond, width, cd=None):
     """[x | cond | 0] as one [rows, width] matrix (width = K padded to the MFMA K-step): the reference's
-    torch.cat((x, c.float()), dim=-1) of the conditional models (vae.py:231-237, 286-291)."""
+    torch.cat((x, c.float()), dim=-1) of the conditional models (vae.py:231-237, 286-291).  ``cond``: fp32 [rows, cd], or int64
+    class indices [rows] of a categorical model (``cd`` = condition_dim: the one-hot of vae.py:337-344 is written by the kernel).
+    One launch (mmdyn_concat_condition) where the backend offers it, a zero fill and two block copies otherwise.  No gradient
+    flows to the condition: the callers' backward drops the condition columns of the operand's gradient."""
     rows, K = x.shape
-    cd = cond.shape[1]
+    index = is_index_condition(cond)
+    if not index:
+        cd = cond.shape[1]
+    if hasattr(ops.B, "concat_condition"):
+        out = _new(x, rows, width)
+        ops.B.concat_condition(x, cond if index else cond.to(torch.float32).contiguous(), out, K, cd, _BAD_INDEX if index else None)
+        return out
+    if index:
+        raise RuntimeError("mmdyn_hip: categorical conditions need the backend's concat_condition (mmdyn_concat_condition)")
     out = torch.zeros(rows, width, device=x.device, dtype=torch.float32)
     ops.B.repack2d_ld(x, out, rows, K, rows, K, width, 0)
     ops.B.repack2d_ld(cond.to(torch.float32).contiguous(), out.view(-1)[K:], rows, cd, rows, cd, width, 0)
@@ -885,7 +928,7 @@ def decoder_forward_steps(P, buf, z, G=1, repeat=1, logits=True, packed=None, co
     Lc = P["upsample.0.weight"].shape[1]         # latent + condition_dim
     L = _pad32(Lc)
     if cond is not None or L != L0:
-        z = concat_condition(z, cond, L)          # [z | c | 0]  (vae.py:286-291)
+        z = concat_condition(z, cond, L, Lc - L0)          # [z | c | 0]  (vae.py:286-291)
     c = {"Bt": Bt, "G": G, "Bg": Bg, "L": L, "L0": L0, "Lc": Lc, "z": z, "pk": pk, "S": S, "last": last}
     # rows -> hw*256+c.  bf16 storage mode: the activated output is the first transposed convolution's operand and is stored
     # as such (the matrix cores round it to bf16 either way); the pre-activation stays fp32 for the backward
@@ -1018,7 +1061,7 @@ def heads_forward(P, hd, packed=None, cond=None):
     pk = packed if packed is not None else pack_now(heads_pack_specs(P))
     K0 = hd.shape[1]                                   # width of the features proper (512 for the image encoders)
     if cond is not None or Kp != K0:
-        hd = concat_condition(hd, cond, Kp)
+        hd = concat_condition(hd, cond, Kp, K - K0)
     out, _ = dense(hd, pk["Wh"], pk["bh"], hd.shape[0], Kp, 2 * L)
     return out, {"hd": hd, "pk": pk, "L": L, "K": K, "Kp": Kp, "K0": K0}
 

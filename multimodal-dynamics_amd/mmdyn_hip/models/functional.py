@@ -75,6 +75,23 @@ class HeadsFn(torch.autograd.Function):
         return (dx,) + tuple(grads[k] for k in layers.HEAD_KEYS) + (None,)
 
 
+class ConcatConditionFn(torch.autograd.Function):
+    """[z | condition] for the mlp Decoder (vae.py:286-291): one join launch (the one-hot of a categorical condition is written
+    by the kernel), cropped to K + cd columns.  No gradient flows to the condition."""
+
+    @staticmethod
+    def forward(ctx, z, cond, cd):
+        K = z.shape[1]
+        width = layers._pad32(K + cd)
+        out = layers.concat_condition(z.detach().contiguous(), cond, width, cd)
+        ctx.K, ctx.cd = K, cd
+        return out if width == K + cd else layers.crop_columns(out, width, K + cd)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return layers.crop_columns(dout.contiguous(), ctx.K + ctx.cd, ctx.K), None, None
+
+
 class DropoutFn(torch.autograd.Function):
     """x * keep_mask / (1 - p) with an explicit uint8 keep-mask (vae.py:213)."""
 

@@ -212,9 +212,8 @@ class Autoencoder(nn.Module):
 
 
 def _check_supported(architecture, conditional, categorical_conditions=False):
-    if conditional and categorical_conditions:
-        raise NotImplementedError("mmdyn_hip: categorical (one-hot) conditions are not built; the seq/dyn modeling "
-                                  "problems use real-valued shock conditions (problems.py:675-681)")
+    """Real-valued and categorical (one-hot, vae.py:337-344) conditions are both built; the one refusal left is the conditional
+    mlp Encoder (raised in Encoder.__init__ with its reason)."""
 
 
 def cnn_image_size(input_dim):
@@ -228,15 +227,50 @@ def cnn_image_size(input_dim):
     return 64
 
 
-def _condition(c, conditional):
-    """The reference's treatment of the condition tensor (vae.py:231-237): 1-D -> column, cast to float."""
+_INDEX_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
+def _condition(c, conditional, categorical=False):
+    """The reference's treatment of the condition tensor (vae.py:231-237).  Real-valued: 1-D -> column, cast to float.
+    Categorical: class indices [B] or [B,1] of any integer dtype -> int64 [B]; the one-hot row (idx2onehot, vae.py:337-344) is
+    written by the join kernel, never stored.  A non-integer tensor cannot index (scatter_ takes int64 only): ValueError.
+    The condition is an input without a gradient in both forms."""
     if not conditional:
         return None
     if c is None:
         raise ValueError("conditional model called without a condition")
+    if categorical:
+        if c.dtype not in _INDEX_DTYPES:
+            raise ValueError(f"categorical conditions are class indices of an integer dtype, got {c.dtype}")
+        if c.dim() == 2 and c.shape[1] == 1:
+            c = c[:, 0]
+        if c.dim() != 1:
+            raise ValueError(f"categorical conditions are one index per sample ([B] or [B,1]), got {tuple(c.shape)}")
+        return c.detach().to(torch.int64).contiguous()
     if c.dim() == 1:
         c = c.unsqueeze(1)
-    return c.to(torch.float32).contiguous()
+    return c.detach().to(torch.float32).contiguous()
+
+
+class _IndexGuard:
+    """Range check of an eager categorical call (the reference asserts max(idx) < n with a host read-back, vae.py:338): the
+    outermost guarded call owns a bad-index word, the join kernels OR into it, and it is read -- one synchronisation -- when the
+    call is over.  Inside another owner's scope (an enclosing model call, an engine) it does nothing."""
+
+    def __init__(self, module, c):
+        self.active = (module.conditional and module.categorical_conditions and c is not None and layers._BAD_INDEX is None)
+        self.c, self.n = c, module.condition_dim
+
+    def __enter__(self):
+        if self.active:
+            self.scope = layers.bad_index_into(torch.zeros(1, dtype=torch.int32, device=self.c.device))
+            self.word = self.scope.__enter__()
+
+    def __exit__(self, et, ev, tb):
+        if self.active:
+            self.scope.__exit__(et, ev, tb)
+            if et is None and int(self.word.item()):
+                raise ValueError(f"categorical condition outside [0, {self.n}) (condition_dim = {self.n})")
 
 
 class Encoder(nn.Module):
@@ -298,9 +332,12 @@ class Encoder(nn.Module):
         return Fn.MLPFn.apply(x, *[p for m in lin for p in (m.weight, m.bias)])
 
     def heads(self, h, c=None):
-        out = Fn.HeadsFn.apply(h, self.linear_means.weight, self.linear_means.bias, self.linear_log_var.weight,
-                               self.linear_log_var.bias, _condition(c, self.conditional))
-        return out
+        """The condition (real-valued rows or class indices) joins the features in front of both heads.  No gradient flows to
+        it; the weight gradient is taken over the joined operand, so the condition columns of linear_means / linear_log_var
+        train like any other."""
+        with _IndexGuard(self, c):
+            return Fn.HeadsFn.apply(h, self.linear_means.weight, self.linear_means.bias, self.linear_log_var.weight,
+                                    self.linear_log_var.bias, _condition(c, self.conditional, self.categorical_conditions))
 
     def forward_fused(self, x, noise, c=None):
         """Returns the fused heads output [B, 2L] (means | log_vars)."""
@@ -354,21 +391,28 @@ class Decoder(nn.Module):
         return layers.dec_keys(self.extra)
 
     def forward(self, z, c=None):
+        """The condition joins the latent in front of the first layer (vae.py:286-291); no gradient flows to it, and the
+        condition columns of upsample.0 / deconv_net.0 get their gradient from the joined operand."""
+        with _IndexGuard(self, c):
+            return self._forward(z, c)
+
+    def _forward(self, z, c):
         sd = dict(self.named_parameters())
+        cat = self.categorical_conditions
         if self.architecture == 'cnn' and not self.training:   # eval: running-estimate BatchNorm, forward only
             with torch.no_grad():
                 P = {k: sd[k].detach() for k in self.param_keys()}
                 return layers.run(layers.decoder_forward_steps(P, self.bn_buffers(), z.detach().contiguous(),
-                                                               cond=_condition(c, self.conditional), training=False))[0]
+                                                               cond=_condition(c, self.conditional, cat), training=False))[0]
         if self.architecture == 'cnn':
-            self._cond = _condition(c, self.conditional)      # read by ImageDecoderFn.forward through `holder`
+            self._cond = _condition(c, self.conditional, cat)      # read by ImageDecoderFn.forward through `holder`
             try:
                 return Fn.ImageDecoderFn.apply(z, self, *[sd[k] for k in self.param_keys()])
             finally:
                 self._cond = None
-        cc = _condition(c, self.conditional)
+        cc = _condition(c, self.conditional, cat)
         if cc is not None:
-            z = torch.cat((z, cc), dim=-1)                   # vae.py:286-291 (a copy; no arithmetic)
+            z = Fn.ConcatConditionFn.apply(z, cc, self.condition_dim)      # vae.py:286-291 (a copy; no arithmetic)
         lin = [m for m in self.deconv_net if isinstance(m, LinearParams)]
         return Fn.MLPFn.apply(z, *[p for m in lin for p in (m.weight, m.bias)])
 
@@ -396,6 +440,10 @@ class VAE(Autoencoder):
         self.decoder = Decoder(**kwargs)
 
     def forward(self, x, c=None):
+        with _IndexGuard(self, c):
+            return self._forward(x, c)
+
+    def _forward(self, x, c):
         noise = _noise_of(self)
         if x.dim() > 2 and self.architecture == 'mlp':
             x = x.view(-1, self.input_dim)
@@ -409,7 +457,8 @@ class VAE(Autoencoder):
     def inference(self, n=1, c=None):
         dev = next(self.parameters()).device
         z = _noise_of(self).eps((n, self.latent_size), dev)
-        return self.decoder(z, c)
+        with _IndexGuard(self, c):
+            return self.decoder(z, c)
 
 
 class MVAE(Autoencoder):
@@ -431,6 +480,10 @@ class MVAE(Autoencoder):
         self.experts = ProductOfExperts()
 
     def forward(self, x, pose=None, condition=None):
+        with _IndexGuard(self, condition):
+            return self._forward(x, pose, condition)
+
+    def _forward(self, x, pose, condition):
         assert isinstance(x, list) or isinstance(x, tuple)
         visual, tactile = x
         ref = visual if visual is not None else (tactile if tactile is not None else pose)
@@ -454,4 +507,5 @@ class MVAE(Autoencoder):
     def inference(self, n=1, c=None):
         dev = next(self.parameters()).device
         z = _noise_of(self).eps((n, self.latent_size), dev)
-        return self.visual_decoder(z, c), self.tactile_decoder(z, c)
+        with _IndexGuard(self, c):
+            return self.visual_decoder(z, c), self.tactile_decoder(z, c)

@@ -483,6 +483,23 @@ class HipBackend:
         check(self.lib.mmdyn_repack2d_ld(_ptr(src), dst.data_ptr(), rows_in, cols_in, rows_out, cols_out, ld_out, mode,
                                          _stream()), "mmdyn_repack2d_ld")
 
+    def concat_condition(self, x, cond, out, K, cd, bad_index=None):
+        """out [rows][width] = [x[:, :K] | condition | 0] in one launch (mmdyn_concat_condition).  ``x``: fp32 rows of unit element
+        stride (any row stride >= K); ``cond``: fp32 [rows][cd] (real-valued) or int64 [rows] (categorical: the kernel writes the
+        one-hot row); ``bad_index``: int32 [1], bit 0 is set when an index lies outside [0, cd) (that row's block is all zero)."""
+        rows, width = out.shape
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != rows or x.shape[1] < K or \
+                (x.stride(1) != 1 and x.shape[1] > 1) or (rows > 1 and x.stride(0) < K):
+            raise ValueError("mmdyn_concat_condition: x must be fp32 GPU rows [rows][>= K] of unit element stride")
+        ldx = x.stride(0) if rows > 1 else max(x.stride(0), K)
+        index = cond.dtype == torch.int64
+        if tuple(cond.shape) != ((rows,) if index else (rows, cd)):
+            raise ValueError(f"mmdyn_concat_condition: condition {tuple(cond.shape)} ({cond.dtype}) does not match rows={rows}, "
+                             f"cd={cd}")
+        check(self.lib.mmdyn_concat_condition(x.data_ptr(), None if index else _ptr(cond), _ptr(cond, torch.int64) if index else None,
+                                              _ptr(out), _ptr(bad_index, torch.int32), rows, K, ldx, cd, width, _stream()),
+              "mmdyn_concat_condition")
+
     def pack_plan(self, plan_dev, n):
         """plan_dev: uint8 device tensor holding n mmdyn_pack_entry structs (see layers.PackPlan)."""
         check(self.lib.mmdyn_pack_plan(_ptr(plan_dev, torch.uint8), n, _stream()), "mmdyn_pack_plan")

@@ -430,8 +430,16 @@ class Reconstruction(Problem):
         self._model.to(self._device)
 
     def _set_condition_dim(self):
-        self._categorical_conditions = False
-        self._condition_dim = 0
+        """--conditional on a labelled dataset: the class labels are the conditions, one-hot over max(targets) + 1 classes
+        (problems.py:391-393).  Without labels (or without --conditional) there is nothing to condition on."""
+        dataset = getattr(self, 'train_dataset', None) or getattr(self.train_loader, 'dataset', None)
+        targets = getattr(dataset, 'targets', None)
+        if self._conditional and targets is not None:
+            self._categorical_conditions = True
+            self._condition_dim = int(torch.as_tensor(targets).max()) + 1
+        else:
+            self._categorical_conditions = False
+            self._condition_dim = 0
 
     def set_criterion(self):
         self._criterion = self._mvae_elbo_loss if 'mvae' in self.parameters['model_name'] else self._elbo_loss
@@ -498,7 +506,11 @@ class Reconstruction(Problem):
     def _evaluate_model(self, x, targets, reduce=None, reduction='sum', **kwargs):
         if 'mvae' in self.parameters['model_name']:
             return self._evaluate_mvae(x=x, targets=x, reduce=reduce, reduction=reduction)
-        recon_x, means, log_var = self._model(x)
+        if self._conditional:
+            # targets here is really the conditions (class labels): problems.py:463-465
+            recon_x, means, log_var = self._model(x, targets)
+        else:
+            recon_x, means, log_var = self._model(x)
         loss = self._criterion(recon_x, x, means, log_var, reduce=reduce, reduction=reduction)
         return {'recon_x': recon_x, 'means': means, 'log_var': log_var}, loss
 
@@ -536,7 +548,15 @@ class Reconstruction(Problem):
         return {'recon_x': recon, 'means': means, 'log_var': log_var, 'perf_measure': perf}, loss
 
     def _sample(self, n=50):
+        """Decoded draws from the prior; a conditional model gets a random condition per draw (problems.py:550-555): a class index
+        for a categorical model, uniform [0, 1) values for a real-valued one."""
         with torch.no_grad():
+            if self._conditional:
+                if self._categorical_conditions:
+                    y = torch.randint(0, self._condition_dim, (n,)).unsqueeze(1).to(self._device)
+                else:
+                    y = torch.rand((n, self._condition_dim)).to(self._device)
+                return self._model.inference(n=n, c=y)
             return self._model.inference(n=n)
 
     def parse_input(self, data, target):
