@@ -454,6 +454,39 @@ int mmdyn_elbo_assemble_rows(const double* bce_rows, const double* mse_rows, con
                              float* partials, int P, int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev,
                              int kl_mode, void* stream);
 
+/* ---- mixed-modality batches: per-ROW modality availability (replaces MVAE.forward, vae.py:126-165, run once per modality
+ * subset on a sub-batch: the dataset yields the availability per frame, utils/datasets.py) -------------------------------- */
+/* An availability table is uint8 [B][MMDYN_MAX_EXPERTS] in device memory, 4-byte aligned (the kernels read one 32-bit word per
+ * row): byte m != 0 = expert m (visual, tactile, pose, spare) is present in row b.  Its contents are never inspected on the host.
+ *
+ * mmdyn_poe_fwd with one table per pass: avail (host array of P device pointers; null, or a null entry = every row holds every
+ * expert of the pass, which reproduces mmdyn_poe_fwd bit for bit).  Expert m takes part in row b iff passes[p].mu[m] != NULL and
+ * avail[p][b][m] != 0.  Same arithmetic and order as mmdyn_poe_fwd, so a row is bitwise the result of a pass that holds that
+ * row's subset; all outputs (mu, logvar, z, zdst, zpl, kl_sum) are kept.  An absent (row, expert) is not read: its words may hold
+ * NaN / Inf.  A row without any expert is the prior alone.  A table needs with_prior = 1 (MMDYN_ERR_SHAPE otherwise: without the
+ * prior such a row divides by zero, and finding it would need the table's contents); a misaligned table is MMDYN_ERR_SHAPE. */
+int mmdyn_poe_fwd_avail(const mmdyn_pass_experts* passes, const uint8_t* const* avail, const float* eps_noise, float* mu,
+                        float* logvar, float* z, double* kl_sum, int with_prior, int P, int B, int L, void* stream);
+/* mmdyn_poe_bwd with the same tables: present (row, expert) pairs get the gradient mmdyn_poe_bwd gives for the row's subset, bit
+ * for bit; the dmu / dlv row of an absent pair is WRITTEN as exact zeros (the heads' weight-gradient GEMM reads it). */
+int mmdyn_poe_bwd_avail(const mmdyn_pass_experts* passes, const uint8_t* const* avail, const float* eps_noise, const float* mu,
+                        const float* logvar, const float* dz, const float* g_mu, const float* g_lv, float kl_scale, int with_prior,
+                        int P, int B, int L, const float* kl_weight_dev, void* stream);
+/* The completed modality of a request (replaces a per-subset forward + a row scatter): out[b] = present(b) ? x[b] :
+ * (logits ? sigmoid(recon[b]) : recon[b]) for [B][row_len] fp32 tensors, present(b) = x != NULL && (avail == NULL ||
+ * avail[b][modality] != 0).  Present rows are copied bit for bit; 16-byte accesses where the pointers are 16-byte aligned, any
+ * row_len (a quad that straddles two rows selects per element).  sigmoid(v) = 1 / (1 + expf(-v)). */
+int mmdyn_complete_select(const float* x, const float* recon, const uint8_t* avail, int modality, float* out, int B, int row_len,
+                          int logits, void* stream);
+/* mmdyn_elbo_assemble_rows with a TARGET-availability table: slot p of bce_rows / mse_rows belongs to the target modality
+ * bce_modality[p] / mse_modality[p] (host arrays of P ints, copied by value; negative = the slot always counts).  A (row, slot)
+ * whose target modality is absent in that row is left out of partials / out and its table entry is overwritten with 0 (whatever
+ * it held).  P <= MMDYN_MAX_PASSES.  Everything else as mmdyn_elbo_assemble_rows: one launch, like the assembly it stands in for. */
+int mmdyn_elbo_assemble_rows_avail(double* bce_rows, double* mse_rows, const double* kl_rows, const double* kl_sum, float* out,
+                                   float* partials, const uint8_t* avail, const int* bce_modality, const int* mse_modality, int P,
+                                   int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev, int kl_mode,
+                                   void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call
  * (graph-replay safe); p/g/m/v: flat fp32 buffers of n elements; g is multiplied by grad_scale first */

@@ -124,6 +124,10 @@ _SIGNATURES = {
     "mmdyn_kl_rows": "ppp" + "iii" + "p",
     "mmdyn_elbo_assemble_rows": "pppppp" + "ii" + "ff" + "p" + "i" + "p",
     "mmdyn_concat_condition": "ppppp" + "iiiii" + "p",
+    "mmdyn_poe_fwd_avail": "ppppppp" + "iiii" + "p",
+    "mmdyn_poe_bwd_avail": "pppppppp" + "f" + "iiii" + "pp",
+    "mmdyn_complete_select": "ppp" + "i" + "p" + "iii" + "p",
+    "mmdyn_elbo_assemble_rows_avail": "ppppppppp" + "ii" + "ff" + "p" + "i" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

@@ -1281,6 +1281,7 @@ class MVAEInference:
         self.noise = NoiseSource(seed)
         self._sync = None
         self._graphs = {}
+        self._zeros = {}                       # batch size -> the all-zero eps of complete(sample=False)
         self._w_dtype = w_dtype(precision)     # packed GEMM operands
         self.refresh()
 
@@ -1373,13 +1374,13 @@ class MVAEInference:
                                                              training=False))
         return layers.heads_forward(self.P[key], h, self.pk[key[0] + "h"], cond=cond)[0]
 
-    def _forward(self, visual, tactile, pose, cond=None):
+    def _forward(self, visual, tactile, pose, cond=None, avail=None, sample=True):
         with self._index_scope():
-            return self._forward_scoped(visual, tactile, pose, cond)
+            return self._forward_scoped(visual, tactile, pose, cond, avail, sample)
 
-    def _forward_scoped(self, visual, tactile, pose, cond):
+    def _forward_scoped(self, visual, tactile, pose, cond, avail=None, sample=True):
         LN, L = self.lanes, self.L
-        ref = visual if visual is not None else (tactile if tactile is not None else pose)
+        ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
         B = ref.shape[0]
         heads = [None, None, None]
         LN.fork()
@@ -1393,12 +1394,22 @@ class MVAEInference:
             hp, _ = layers.pose_encoder_trunk_forward(self.P["pe"], pose)
             heads[2] = layers.heads_forward(self.P["pe"], hp, self.pk["ph"])[0]
         LN.join()
-        eps = self._draw_latent(B)
+        eps = self._draw_latent(B) if sample else self._zero_latent(B)
         mu, lv, z = (torch.empty(B, L, device=ref.device) for _ in range(3))
         p = {"mu": [None if h is None else h[:, :L] for h in heads], "lv": [None if h is None else h[:, L:] for h in heads],
              "dmu": [None] * 3, "dlv": [None] * 3, "ld": [2 * L] * 3}
-        ops.B.poe_fwd([p], eps, mu, lv, z, None, True, 1, B, L)
+        if avail is None:
+            ops.B.poe_fwd([p], eps, mu, lv, z, None, True, 1, B, L)
+        else:       # a mixed request: the same single launch, the experts of each row chosen by the row's word of the table
+            ops.B.poe_fwd_avail([p], [avail], eps, mu, lv, z, None, True, 1, B, L)
         return self._decode(z, cond) + (mu, lv)
+
+    def _zero_latent(self, B):
+        """eps = 0: z is the posterior mean.  Allocated and cleared once per batch size, outside any captured region."""
+        z = self._zeros.get(B)
+        if z is None:
+            z = self._zeros[B] = torch.zeros(B, self.L, device=self.dev)
+        return z
 
     def _decode(self, z, cond=None):
         LN = self.lanes
@@ -1459,8 +1470,25 @@ class MVAEInference:
             layers.ACT_DTYPE = prev_act
             layers.W_DTYPE = prev_w
 
+    def _availability(self, available, B):
+        """The request's availability as the kernels' uint8 [B][4] table on the engine's device (None stays None): a few
+        element-wise torch ops before the captured region; the table's contents are not looked at."""
+        if available is None:
+            return None
+        from .models.functional import availability_table
+        return availability_table(available, B, self.dev)
+
+    @staticmethod
+    def _batch_of(ins, available):
+        ref = next((t for t in ins if t is not None), None)
+        if ref is not None:
+            return ref.shape[0]
+        if available is None:
+            raise ValueError("a request needs at least one modality")
+        return len(available)                                  # a request of prior-only rows
+
     @torch.no_grad()
-    def forward(self, x, pose=None, condition=None):
+    def forward(self, x, pose=None, condition=None, available=None):
         """``MVAE.forward`` semantics: x = [visual | None, tactile | None]; returns (visual_recon, tactile_recon,
         pose_recon | None, means, log_var) -- logits, like the reference.  ``condition`` (conditional models; ValueError when it
         is missing, or given to an unconditional model): [B, condition_dim] real values, or class indices [B] / [B,1] of any
@@ -1468,23 +1496,35 @@ class MVAEInference:
         kind -- so a replay with a new condition of the same shape gives that condition's result.  An index outside
         [0, condition_dim) is served as an all-zero condition block and reported by :meth:`bad_condition`; forward itself does
         not synchronise.  The returned tensors are the graph's static outputs: copy them if they must survive the next call with
-        the same shapes."""
+        the same shapes.
+
+        ``available`` (optional): a MIXED request -- [B, 2] (visual, tactile: what the dataset yields per frame) or [B, 3]
+        (+ pose), any bool / integer / floating dtype, non-zero = present; with [B, 2] the pose is present wherever a pose tensor
+        is given; a modality passed as ``None`` is absent in every row.  Row b is served from the modalities row b holds (none:
+        the prior alone), bitwise as a whole-batch request of that subset would serve it; the tensors of an absent (row, modality)
+        may hold anything finite.  The table is one more static input of the captured graph: the key carries its presence, not
+        its contents, so one graph serves every mixture of a batch shape, with the launches of the joint request (the PoE launch
+        is replaced one for one).  The values are not inspected and nothing synchronises; wrong shape / dtype: ValueError."""
         visual, tactile = x
         c = lambda t: None if t is None else t.contiguous()
         ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        if all(t is None for t in ins):
+        if all(t is None for t in ins) and available is None:
             raise ValueError("forward needs at least one modality")
-        cond = self._condition(condition, next(t for t in ins if t is not None).shape[0])
+        B = self._batch_of(ins, available)
+        cond = self._condition(condition, B)
         key = ("fwd",) + tuple(None if t is None else tuple(t.shape) for t in ins) + (self._cond_key(cond),)
-        return self._run(key, self._forward, None, ins + [cond])
+        if available is None:
+            return self._run(key, self._forward, None, ins + [cond])
+        avail = self._availability(available, B)
+        return self._run(key + (("avail",) + tuple(avail.shape),), self._forward, None, ins + [cond, avail])
 
     __call__ = forward
 
-    def _score(self, self_target, visual, tactile, pose, tv, tt, tp, mask, cond=None):
+    def _score(self, self_target, visual, tactile, pose, tv, tt, tp, mask, cond=None, avail=None, tavail=None):
         """One forward of the given subset, then the per-sample terms of that pass: the row kernels on the logits, the pose
         reconstruction and the posterior the forward left on the device.  Tables (fp64 [2][B], zeroed by a fill that a captured
         graph replays): bce = (visual, tactile), mse = (pose, 0), kl = (KL, 0); the assembly adds the two rows of each table."""
-        v, t, pr, mu, lv = self._forward(visual, tactile, pose, cond)
+        v, t, pr, mu, lv = self._forward(visual, tactile, pose, cond, avail)
         if self_target:
             tv, tt, tp = visual, tactile, pose if self.use_pose else None
         B, L = mu.shape
@@ -1498,13 +1538,18 @@ class MVAEInference:
             ops.B.mse_rows_groups(pr, tp, mse, [0], B, tp.shape[1])
         ops.B.kl_rows(mu, lv, kl[0:1], 1, B, L)
         rows = torch.empty(B, device=mu.device)
-        ops.B.elbo_assemble_rows(bce, mse, kl, None, rows, None, 2, B, 1.0, self._pose_multiplier, self._klw, 1)
+        if tavail is None:
+            ops.B.elbo_assemble_rows(bce, mse, kl, None, rows, None, 2, B, 1.0, self._pose_multiplier, self._klw, 1)
+        else:       # the assembly's sibling: a (row, term) whose target is absent leaves the row sum and its table entry becomes 0
+            ops.B.elbo_assemble_rows_avail(bce, mse, kl, None, rows, None, tavail, [0, 1], [2, -1], 2, B, 1.0,
+                                           self._pose_multiplier, self._klw, 1)
         return {"rows": rows, "bce_visual": bce[0] if tv is not None else None, "bce_tactile": bce[1] if tt is not None else None,
                 "mse_pose": mse[0] if tp is not None else None, "kl": kl[0],
                 "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
 
     @torch.no_grad()
-    def score(self, x, pose=None, targets=None, loss_mask=None, kl_weight=1.0, pose_multiplier=1000.0, condition=None):
+    def score(self, x, pose=None, targets=None, loss_mask=None, kl_weight=1.0, pose_multiplier=1000.0, condition=None,
+              available=None, target_available=None):
         """Per-sample terms of ONE eval-mode forward of the modality subset ``x = [visual | None, tactile | None]`` (+ ``pose``)
         against ``targets = [visual | None, tactile | None, pose | None]`` (default: the inputs that were given): a dict of
         device tensors, all ``[B]`` -- ``bce_visual`` / ``bce_tactile`` (sum over (C, H, W) of BCE-with-logits; with ``loss_mask``
@@ -1513,13 +1558,19 @@ class MVAEInference:
         kl_weight * kl (fp32; a term without a target is left out and its entry is None) -- plus ``recon_x`` / ``means`` /
         ``log_var`` of the pass.  Captured and replayed under a key of its own like :meth:`forward`; the tensors are the graph's
         static outputs: copy them if they must survive the next call with the same shapes.  Forward only.  ``condition``: as in
-        :meth:`forward` (required by a conditional model)."""
+        :meth:`forward` (required by a conditional model).
+
+        ``available``: the inputs' per-row availability, as in :meth:`forward`.  ``target_available`` (same forms): which
+        targets exist per row; it defaults to ``available`` when the targets default to the inputs, and to "all present" when
+        explicit targets are given.  A (row, term) without an available target adds nothing to ``rows`` and its entry in
+        ``bce_visual`` / ``bce_tactile`` / ``mse_pose`` is 0 (the assembly launch does both; no launch is added); ``kl`` is
+        every row's own KL as before."""
         visual, tactile = x
         c = lambda t: None if t is None else t.contiguous()
         ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        if all(t is None for t in ins):
+        if all(t is None for t in ins) and available is None:
             raise ValueError("score needs at least one modality")
-        B = next(t for t in ins if t is not None).shape[0]
+        B = self._batch_of(ins, available)
         cond = self._condition(condition, B)
         self_target = targets is None
         tg = [None] * 3 if self_target else [c(t) for t in (list(targets) + [None] * 3)[:3]]
@@ -1543,7 +1594,48 @@ class MVAEInference:
         args = ins + tg + [loss_mask]
         key = ("score", self_target, self._pose_multiplier) + tuple(None if t is None else tuple(t.shape) for t in args)
         key, args = key + (self._cond_key(cond),), args + [cond]
-        return self._run(key, lambda *a: self._score(self_target, *a), None, args)
+        if available is None and target_available is None:
+            return self._run(key, lambda *a: self._score(self_target, *a), None, args)
+        avail = self._availability(available, B)
+        if target_available is None and self_target:
+            target_available = available
+        tavail = self._availability(target_available, B)
+        key = key + tuple(None if t is None else ("avail",) + tuple(t.shape) for t in (avail, tavail))
+        return self._run(key, lambda *a: self._score(self_target, *a), None, args + [avail, tavail])
+
+    def _complete(self, sample, visual, tactile, pose, cond, avail):
+        """One (mixed) forward, then one select launch per returned modality."""
+        v, t, pr, _, _ = self._forward(visual, tactile, pose, cond, avail, sample)
+        out_v, out_t = torch.empty_like(v), torch.empty_like(t)
+        ops.B.complete_select(visual, v, avail, 0, out_v, True)
+        ops.B.complete_select(tactile, t, avail, 1, out_t, True)
+        out_p = None
+        if self.use_pose:
+            out_p = torch.empty_like(pr)
+            ops.B.complete_select(pose, pr, avail, 2, out_p, False)
+        return out_v, out_t, out_p
+
+    @torch.no_grad()
+    def complete(self, x, pose=None, available=None, condition=None, sample=False):
+        """The completed request: ``(visual, tactile, pose | None)`` in [0, 1] image space.  Rows of a modality that the request
+        holds (``available`` as in :meth:`forward`; None: every given modality in every row) are the caller's inputs bit for bit;
+        absent rows -- and a modality passed as ``None`` -- are the model's reconstruction from whatever that row does hold: the
+        sigmoid of the decoder's logits for the images, the pose decoder's output for the pose.  ``sample=False`` decodes the
+        posterior mean (eps = 0); ``sample=True`` draws from the engine's Philox stream like :meth:`forward`.  Captured and
+        replayed under a key of its own: the launches of :meth:`forward` plus one select launch per returned modality.  The
+        tensors are the graph's static outputs; nothing synchronises."""
+        visual, tactile = x
+        c = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
+        if all(t is None for t in ins) and available is None:
+            raise ValueError("complete needs at least one modality")
+        B = self._batch_of(ins, available)
+        cond = self._condition(condition, B)
+        avail = self._availability(available, B)
+        sample = bool(sample)
+        key = ("complete", sample) + tuple(None if t is None else tuple(t.shape) for t in ins) + \
+            (self._cond_key(cond), None if avail is None else ("avail",) + tuple(avail.shape))
+        return self._run(key, lambda *a: self._complete(sample, *a), None, ins + [cond, avail])
 
     @torch.no_grad()
     def inference(self, n=1, c=None):

@@ -194,6 +194,55 @@ class PoEReparamFn(torch.autograd.Function):
         return (None, None) + tuple(ds)
 
 
+def availability_table(available, B, device):
+    """The per-row modality availability of a request as the kernels take it: uint8 [B][4] (visual, tactile, pose, spare) on
+    ``device``.  ``available``: [B, 2] (visual, tactile -- what the dataset yields per frame) or [B, 3] (+ pose), any bool /
+    integer / floating dtype; non-zero = present.  With [B, 2] the pose counts as present in every row (that is: wherever a pose
+    tensor is given).  The values are not inspected -- the table usually lives on the device and looking at it would synchronise.
+    A few torch element-wise ops, once per request, outside any captured region."""
+    if not torch.is_tensor(available):
+        try:
+            available = torch.as_tensor(available)
+        except Exception as e:
+            raise ValueError(f"available must be a [B, 2] or [B, 3] tensor: {e}")
+    if available.is_complex() or not (available.dtype == torch.bool or available.dtype.is_floating_point or
+                                      available.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)):
+        raise ValueError(f"available must hold bool, integer or floating values, got {available.dtype}")
+    if available.dim() != 2 or available.shape[0] != B or available.shape[1] not in (2, 3):
+        raise ValueError(f"available {tuple(available.shape)} is not [B={B}, 2] (visual, tactile) or [B={B}, 3] (+ pose)")
+    table = torch.zeros(B, ops.MAX_EXPERTS, dtype=torch.uint8, device=device)
+    table[:, 2] = 1
+    table[:, :available.shape[1]] = (available.to(device) != 0).to(torch.uint8)
+    return table
+
+
+class PoEReparamAvailFn(torch.autograd.Function):
+    """:class:`PoEReparamFn` for a mixed-modality batch: ``table`` (uint8 [B][4], :func:`availability_table`) says per row which
+    of the given heads take part (vae.py:139-159 run per row subset).  The gradient of a head row that did not take part is an
+    exact zero, written by the backward kernel."""
+
+    @staticmethod
+    def forward(ctx, eps_noise, L, table, *heads):
+        present = [h for h in heads if h is not None]
+        B = table.shape[0]
+        hs = [None if h is None else h.detach().contiguous() for h in heads]
+        ref = present[0] if present else eps_noise
+        mu, lv, z = (torch.empty(B, L, device=ref.device, dtype=ref.dtype) for _ in range(3))
+        ops.B.poe_fwd_avail([_pass(hs, None, L)], [table], eps_noise, mu, lv, z, None, True, 1, B, L)
+        ctx.hs, ctx.eps, ctx.L, ctx.B, ctx.table = hs, eps_noise, L, B, table
+        ctx.save_for_backward(mu, lv)
+        return mu, lv, z
+
+    @staticmethod
+    def backward(ctx, g_mu, g_lv, dz):
+        mu, lv = ctx.saved_tensors
+        ds = [None if h is None else torch.empty_like(h) for h in ctx.hs]          # every row is written, absent ones as zeros
+        c = lambda t: None if t is None else t.contiguous()
+        ops.B.poe_bwd_avail([_pass(ctx.hs, ds, ctx.L)], [ctx.table], ctx.eps, mu, lv, c(dz), c(g_mu), c(g_lv), 0.0, True, 1, ctx.B,
+                            ctx.L)
+        return (None, None, None) + tuple(ds)
+
+
 def _pass(hs, ds, L):
     n = len(hs)
     return {"mu": [None if h is None else h[:, :L] for h in hs],

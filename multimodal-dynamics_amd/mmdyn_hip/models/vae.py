@@ -479,15 +479,32 @@ class MVAE(Autoencoder):
                                         condition_dim=0, architecture="mlp")
         self.experts = ProductOfExperts()
 
-    def forward(self, x, pose=None, condition=None):
+    def forward(self, x, pose=None, condition=None, available=None):
+        """``available`` (optional): the per-row modality availability of a mixed batch -- [B, 2] (visual, tactile: what the
+        dataset yields per frame) or [B, 3] (+ pose), any bool / integer / floating dtype, non-zero = present; with [B, 2] the
+        pose is present wherever a pose tensor is given.  Row b's posterior is the product of the prior and the experts that row
+        holds (a row that holds none is the prior alone); a modality passed as ``None`` is absent in every row whatever the table
+        says.  Wrong shape or a non-numeric dtype: ValueError; the values are not inspected (no synchronisation).  Differentiable:
+        the head gradients of an absent (row, expert) are exact zeros.  In ``train()`` mode the images of absent rows still pass
+        through the encoders, and so through the batch statistics of their BatchNorm layers, as they do when the reference is
+        fed such a batch; in ``eval()`` mode rows are independent.  ``available=None`` is the whole-batch path, unchanged."""
         with _IndexGuard(self, condition):
-            return self._forward(x, pose, condition)
+            return self._forward(x, pose, condition, available)
 
-    def _forward(self, x, pose, condition):
+    def _forward(self, x, pose, condition, available=None):
         assert isinstance(x, list) or isinstance(x, tuple)
         visual, tactile = x
         ref = visual if visual is not None else (tactile if tactile is not None else pose)
-        batch_size = ref.size(0)
+        if ref is None and available is None:
+            raise ValueError("MVAE.forward needs at least one modality")
+        table = None
+        if available is not None:
+            batch_size = ref.size(0) if ref is not None else len(available)
+            table = Fn.availability_table(available, batch_size, ref.device if ref is not None else
+                                          next(self.parameters()).device)
+        else:
+            batch_size = ref.size(0)
+        dev = ref.device if ref is not None else table.device
         noise = _noise_of(self)
         L = self.latent_size
         heads = [None, None, None]
@@ -497,8 +514,11 @@ class MVAE(Autoencoder):
             heads[1] = self.tactile_encoder.forward_fused(tactile, noise, condition)
         if pose is not None and self._use_pose:
             heads[2] = self.pose_encoder.forward_fused(pose, noise, condition)
-        eps = noise.eps((batch_size, L), ref.device)
-        means, log_var, z = Fn.PoEReparamFn.apply(eps, L, *heads)
+        eps = noise.eps((batch_size, L), dev)
+        if table is None:
+            means, log_var, z = Fn.PoEReparamFn.apply(eps, L, *heads)
+        else:
+            means, log_var, z = Fn.PoEReparamAvailFn.apply(eps, L, table, *heads)
         visual_recon = self.visual_decoder(z, c=condition)
         tactile_recon = self.tactile_decoder(z, c=condition)
         pose_recon = self.pose_decoder(z, c=condition) if self._use_pose else None

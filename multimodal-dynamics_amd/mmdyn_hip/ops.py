@@ -896,6 +896,77 @@ class HipBackend:
                                                 _ptr(partials), P, B, float(kl_weight), float(pose_multiplier),
                                                 _ptr(kl_weight_dev), int(kl_mode), _stream()), "mmdyn_elbo_assemble_rows")
 
+    # ---- mixed-modality batches: per-row availability ----
+    @staticmethod
+    def _avail(table, B, name, like=None):
+        """Pointer of an availability table: uint8 [B][MAX_EXPERTS], contiguous, on the device of ``like``."""
+        if table is None:
+            return None
+        if table.dtype != torch.uint8 or tuple(table.shape) != (B, MAX_EXPERTS) or not table.is_contiguous():
+            raise ValueError(f"mmdyn_hip: {name}: the availability table must be a contiguous uint8 [B={B}][{MAX_EXPERTS}] tensor, "
+                             f"got {table.dtype} {tuple(table.shape)}")
+        if like is not None and table.device != like.device:
+            raise ValueError(f"mmdyn_hip: {name}: the availability table lives on {table.device}, the tensors on {like.device}")
+        return _ptr(table, torch.uint8)
+
+    def _avail_tables(self, avail, P, B, name, like):
+        """avail: None, or a list of P tables / None -> (the host array of P device pointers, or None)."""
+        if avail is None:
+            return None
+        if len(avail) != P:
+            raise ValueError(f"mmdyn_hip: {name}: {len(avail)} availability tables for {P} passes")
+        return (ctypes.c_void_p * MAX_PASSES)(*[self._avail(t, B, name, like) for t in avail])
+
+    def poe_fwd_avail(self, passes, avail, eps_noise, mu, logvar, z, kl_sum, with_prior, P, B, L):
+        """poe_fwd with one availability table per pass (``avail``: list of P uint8 [B][4] tensors / None, or None): expert m takes
+        part in row b iff the pass holds it and avail[p][b][m] != 0.  A table needs with_prior."""
+        arr = self._passes(passes)
+        tabs = self._avail_tables(avail, P, B, "poe_fwd_avail", mu)
+        check(self.lib.mmdyn_poe_fwd_avail(ctypes.cast(arr, ctypes.c_void_p), None if tabs is None else ctypes.addressof(tabs),
+                                           _ptr(eps_noise), _ptr(mu), _ptr(logvar), _ptr(z), _ptr(kl_sum, torch.float64),
+                                           int(with_prior), P, B, L, _stream()), "mmdyn_poe_fwd_avail")
+
+    def poe_bwd_avail(self, passes, avail, eps_noise, mu, logvar, dz, g_mu, g_lv, kl_scale, with_prior, P, B, L, kl_weight_dev=None):
+        """poe_bwd with the tables of poe_fwd_avail; the dmu / dlv row of an absent (row, expert) is written as zeros."""
+        arr = self._passes(passes)
+        tabs = self._avail_tables(avail, P, B, "poe_bwd_avail", mu)
+        check(self.lib.mmdyn_poe_bwd_avail(ctypes.cast(arr, ctypes.c_void_p), None if tabs is None else ctypes.addressof(tabs),
+                                           _ptr(eps_noise), _ptr(mu), _ptr(logvar), _ptr(dz), _ptr(g_mu), _ptr(g_lv), float(kl_scale),
+                                           int(with_prior), P, B, L, _ptr(kl_weight_dev), _stream()), "mmdyn_poe_bwd_avail")
+
+    def complete_select(self, x, recon, avail, modality, out, logits):
+        """out[b] = present(b) ? x[b] : (logits ? sigmoid(recon[b]) : recon[b]); x (may be None: no row present), recon, out: fp32
+        [B, ...] of one shape; avail: uint8 [B][4] or None (every row present); modality: the table column."""
+        B = recon.shape[0]
+        row_len = recon.numel() // max(B, 1)
+        if out.shape != recon.shape or (x is not None and x.shape != recon.shape):
+            raise ValueError(f"mmdyn_complete_select: x {None if x is None else tuple(x.shape)} / recon {tuple(recon.shape)} / out "
+                             f"{tuple(out.shape)} differ in shape")
+        if not 0 <= int(modality) < MAX_EXPERTS:
+            raise ValueError(f"mmdyn_complete_select: modality {modality} is not a column of the availability table")
+        check(self.lib.mmdyn_complete_select(_ptr(x), _ptr(recon), self._avail(avail, B, "complete_select", recon), int(modality),
+                                             _ptr(out), B, row_len, int(bool(logits)), _stream()), "mmdyn_complete_select")
+
+    def elbo_assemble_rows_avail(self, bce_rows, mse_rows, kl_rows, kl_sum, out, partials, avail, bce_modality, mse_modality, P, B,
+                                 kl_weight, pose_multiplier, kl_weight_dev=None, kl_mode=0):
+        """elbo_assemble_rows with the TARGET-availability table ``avail`` (uint8 [B][4]): slot p of bce_rows / mse_rows belongs to
+        the target modality bce_modality[p] / mse_modality[p] (negative: always counts); an entry whose target is absent in its row
+        is left out of the sums and overwritten with 0."""
+        for t, n, what in ((bce_rows, P * B, "bce_rows"), (mse_rows, P * B, "mse_rows"), (kl_rows, P * B, "kl_rows"),
+                           (kl_sum, P, "kl_sum"), (partials, P * B, "partials"), (out, B, "out")):
+            if t is not None and t.numel() < n:
+                raise ValueError(f"mmdyn_elbo_assemble_rows_avail: {what} holds {t.numel()} elements, needs {n}")
+        if len(bce_modality) != P or len(mse_modality) != P:
+            raise ValueError(f"mmdyn_elbo_assemble_rows_avail: the slot -> modality maps must hold P={P} entries")
+        bm = (ctypes.c_int * P)(*[int(v) for v in bce_modality])
+        mm = (ctypes.c_int * P)(*[int(v) for v in mse_modality])
+        check(self.lib.mmdyn_elbo_assemble_rows_avail(_ptr(bce_rows, torch.float64), _ptr(mse_rows, torch.float64),
+                                                      _ptr(kl_rows, torch.float64), _ptr(kl_sum, torch.float64), _ptr(out),
+                                                      _ptr(partials), self._avail(avail, B, "elbo_assemble_rows_avail", out),
+                                                      ctypes.addressof(bm), ctypes.addressof(mm), P, B, float(kl_weight),
+                                                      float(pose_multiplier), _ptr(kl_weight_dev), int(kl_mode), _stream()),
+              "mmdyn_elbo_assemble_rows_avail")
+
     def adam_step(self, p, g, m, v, state, lr, beta1, beta2, eps, grad_scale, guarded=False):
         """guarded: ``state`` has six doubles and a gradient holding inf / NaN skips the step (counted in state[4])."""
         if guarded and state.numel() < 6:

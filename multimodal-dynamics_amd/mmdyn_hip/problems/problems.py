@@ -559,6 +559,29 @@ class Reconstruction(Problem):
                 return self._model.inference(n=n, c=y)
             return self._model.inference(n=n)
 
+    def complete(self, x, sample=False):
+        """The completed frames of a mixed-modality batch (cnn-mvae): ``x`` is the dict ``parse_input`` returns; its
+        ``input_available_modals`` ([B, 2]: visual, tactile present per frame -- the dataset counts a constant image as missing)
+        goes to :meth:`mmdyn_hip.engine.MVAEInference.complete` with the images, the pose when the model has one and, for a
+        conditional model, ``x['shock']``.  Returns (visual, tactile, pose | None): present rows are the inputs, absent ones the
+        model's reconstruction from what the row holds.  The serving engine is built on first use from the model as it stands
+        (eval-mode arithmetic: running-estimate BatchNorm, no dropout) and re-packs the weights on every call."""
+        if self.parameters.get('model_name') != 'cnn-mvae':
+            raise ValueError(f"complete() serves cnn-mvae models, not {self.parameters.get('model_name')!r}")
+        if not isinstance(x, dict) or not isinstance(x.get('model_input'), (list, tuple)) or len(x['model_input']) != 2:
+            raise ValueError("complete() takes the dict parse_input returns for a visuotactile batch")
+        from ..engine import MVAEInference
+        eng = getattr(self, '_completer', None)
+        if eng is None or eng.model is not self._model:
+            eng = self._completer = MVAEInference(self._model)
+        else:
+            eng.refresh()
+        pose = x.get('input_object_pose')
+        pose = pose[0] if isinstance(pose, (list, tuple)) else pose
+        out = eng.complete(list(x['model_input']), pose=pose, available=x.get('input_available_modals'),
+                           condition=x.get('shock') if self._conditional else None, sample=sample)
+        return tuple(None if t is None else t.clone() for t in out)
+
     def parse_input(self, data, target):
         if not isinstance(data, list):
             return data.to(self._device), target.to(self._device)
