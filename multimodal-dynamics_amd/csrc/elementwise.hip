@@ -98,6 +98,9 @@ __device__ __forceinline__ void philox4(uint64_t seed, uint64_t ctr, uint32_t (&
   out[2] = c[2];
   out[3] = c[3];
 }
+// Uniform in (0, 1], not [0, 1): u01(0) = 2^-25, and x >> 8 = 2^24 - 1 gives exactly 1.0f (2^24 - 0.5 is no float and rounds to
+// even; for the same reason the largest value below 1 is 1 - 2^-23).  So -2 ln u lies in [0, 50 ln 2] and the Box-Muller radius
+// below in [0, 5.8871]: never NaN, never infinite.  Add, then multiply: nothing to contract, the value is the same on every target.
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 __global__ void random_masks_kernel(uint8_t* __restrict__ masks, int64_t n, float p_drop, uint64_t seed,
@@ -116,6 +119,9 @@ __global__ void random_masks_kernel(uint8_t* __restrict__ masks, int64_t n, floa
   }
 }
 
+// Element j is word j % 4 of counter offset (+ offset_dev[0]) + j / 4, key = seed; a launch of n elements uses ceil(n / 4)
+// counters.  Masks: element j = (u01(word) >= p_drop).  Normals: words 0, 1 of a counter give z0 = r cos(a), z1 = r sin(a) with
+// r = sqrt(-2 ln u01(w0)) <= 5.8871 and a = 2 pi u01(w1); words 2, 3 give z2, z3 the same way.
 __global__ void random_normal_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t offset,
                                      const uint64_t* __restrict__ offset_dev) {
   if (offset_dev) offset += offset_dev[0];

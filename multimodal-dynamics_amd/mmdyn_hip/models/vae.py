@@ -110,12 +110,22 @@ class NoiseSource:
 
     The stream position is ``offset`` (host, advanced per draw) + ``base`` (a device counter).  Eager code only
     moves ``offset``.  A captured HIP graph bakes its host offsets in; :meth:`commit` then enqueues a device-side
-    bump of ``base`` by everything drawn since the last commit, so every replay draws fresh numbers."""
+    bump of ``base`` by everything drawn since the last commit, so every replay draws fresh numbers.
+
+    Contract of the draws: element j is word j % 4 of Philox-4x32-10 counter ``base + offset + j // 4`` (a draw of n elements
+    uses ceil(n / 4) counters), keyed by ``seed`` for normals and ``seed ^ 0x5DEECE66D`` for masks.  The uniform of a word lies
+    in (0, 1] (smallest value 2^-25, 1.0 is reached); a mask is ``u >= p``; words 0, 1 of a counter give z0 = r cos(a),
+    z1 = r sin(a) with r = sqrt(-2 ln u0) at most 5.8871 and a = 2 pi u1, words 2, 3 give z2, z3 the same way."""
 
     def __init__(self, seed=0):
         self.seed, self.offset, self.base, self._mark = int(seed), 0, None, 0
 
     def _base(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            # "cuda" is the current device; a tensor's .device always carries the index, so without this the comparison below
+            # never matches and every draw starts a new counter at zero, dropping what commit() has moved into it
+            device = torch.device("cuda", torch.cuda.current_device())
         if self.base is None or self.base.device != device:
             self.base = torch.zeros(1, dtype=torch.int64, device=device)
         return self.base
