@@ -487,6 +487,51 @@ int mmdyn_elbo_assemble_rows_avail(double* bce_rows, double* mse_rows, const dou
                                    int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev, int kl_mode,
                                    void* stream);
 
+/* ---- gradients of the weighted per-sample ELBO (training with per-sample weights) -----------------------------------------------
+ * L = (1/B) sum_b w_b * row_b, where row_b is what mmdyn_elbo_assemble_rows returns for sample b: the reference's
+ * (w * rows).sum() / B on its reduce=False branch (problems.py:415-417, 451-456; kl_mode 0: the batch-total KL sits in every row,
+ * so it is weighted by sum_b w_b), or the same with each sample's own KL (kl_mode 1).  w: fp32 [B], any values; a weight is never
+ * inspected -- NaN / Inf propagate (0 * NaN = NaN).  The backward of the step starts from three seeds (BCE, MSE, KL); each of the
+ * launches below is the seed kernel with its scalar scale replaced by scale * weight-of-the-sample, the product formed as
+ * (unweighted gradient) * w so that w = 1 gives the unweighted kernel's gradient bit for bit.  The loss sums these launches produce
+ * are the UNWEIGHTED row tables of the section above; BatchNorm statistics are those of the unweighted batch.
+ *
+ * mmdyn_tconv_out3_bn_bce_rows with the gradient output: loss_rows / unmasked_rows as there (unweighted), dlogit [G*Bg][3][2Hi][2Wi]
+ * = ((sigmoid(l) - t) * grad_scale) * w_rec[b]  (with a mask: (mk * (sigmoid(mk l) - mk t) * grad_scale) * w_rec[b]); a discarded
+ * pass (slot < 0) gets a zero gradient and no loss.  w_rec [Bg] is read once per block.  dlogit and w_rec are required. */
+int mmdyn_tconv_out3_bn_bce_rows_grad(const void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                                      const float* w, float* logits, int logits_group, const float* target, const float* mask,
+                                      int mask_channels, float* dlogit, const float* w_rec, double* loss_rows, double* unmasked_rows,
+                                      const int* slot_of_group, int n_slots, float grad_scale, int G, int Bg, int Hi, int Wi, int b16,
+                                      void* stream);
+/* mmdyn_bce_logits_rows_groups with dlogit [G][Bg][chw] = ((sigmoid - t) * grad_scale) * w_rec[b] in the same pass over the logits
+ * (zeros for a pass with a negative slot); the target / mask row of a sample is read once for all G passes.  G * Bg * chw < 2^31
+ * (MMDYN_ERR_RANGE). */
+int mmdyn_bce_logits_rows_groups_grad(const float* logits, const float* target, const float* mask, int mask_channels, float* dlogit,
+                                      const float* w_rec, double* rows_out, double* unmasked_rows, const int* slot_of_group,
+                                      int n_slots, float grad_scale, int G, int Bg, int chw, int hw, void* stream);
+/* mmdyn_mse_rows_groups with dr [G][Bg][n] = (2 (r - t) * grad_scale) * w_rec[b]. */
+int mmdyn_mse_rows_groups_grad(const float* r, const float* t, float* dr, const float* w_rec, double* rows_out,
+                               const int* slot_of_group, int n_slots, float grad_scale, int G, int Bg, int n, void* stream);
+/* mmdyn_poe_bwd / mmdyn_reparam_bwd with the KL scale of row b = kl_scale * w_kl[b] (w_kl fp32 [B]; kl_weight_dev still multiplies).
+ * kl_mode 1 passes w_kl = w; kl_mode 0 passes the vector filled with sum_b w_b that mmdyn_elbo_assemble_weighted writes.  dz arrives
+ * weighted through the decoders and is not scaled again.  With w_kl = 1 the results equal the unweighted kernels' bit for bit. */
+int mmdyn_poe_bwd_weighted(const mmdyn_pass_experts* passes, const float* eps_noise, const float* mu, const float* logvar,
+                           const float* dz, const float* g_mu, const float* g_lv, float kl_scale, const float* w_kl, int with_prior,
+                           int P, int B, int L, const float* kl_weight_dev, void* stream);
+int mmdyn_reparam_bwd_weighted(const float* mu, const float* lv, const float* eps_noise, const float* dz, float kl_scale,
+                               const float* w_kl, float* dmu, float* dlv, int B, int L, int ld, void* stream);
+/* From the fp64 row tables [P][B] (any may be null = 0), kl_sum [P] and w [B]:
+ *   wpartials[p] = (sum_b w_b (bce[p][b] + pose_multiplier mse[p][b]) + kl_weight * (kl_mode ? sum_b w_b kl_rows[p][b]
+ *                                                                                           : (sum_b w_b) kl_sum[p])) / B,
+ *   loss[0] = sum_p wpartials[p]   (fp32; wpartials may be null),
+ * plus the unweighted out [B] / partials [P][B] of mmdyn_elbo_assemble_rows in the same kl_mode (either may be null) and, when
+ * w_sum_out is non-null, w_sum_out[b] = (float)sum_b w_b for every b.  fp64 accumulation in a fixed order by one block, no atomics:
+ * the same bits in every run.  P <= MMDYN_MAX_PASSES.  kl_weight_dev as in mmdyn_elbo_assemble. */
+int mmdyn_elbo_assemble_weighted(const double* bce_rows, const double* mse_rows, const double* kl_rows, const double* kl_sum,
+                                 const float* w, float* loss, float* wpartials, float* out, float* partials, float* w_sum_out, int P,
+                                 int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev, int kl_mode, void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call
  * (graph-replay safe); p/g/m/v: flat fp32 buffers of n elements; g is multiplied by grad_scale first */

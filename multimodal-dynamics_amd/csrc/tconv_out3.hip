@@ -9,6 +9,7 @@
 //   * the 1536 weights are wave-uniform: the compiler keeps them in SGPRs (s_load), no LDS/VGPR traffic;
 //   * each thread stores 8-byte pairs, a wave writes full 128-byte lines of the NCHW planes.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -53,11 +54,19 @@ struct Out3Loss {
 };
 // ROWS (a mode of LOSS, evaluation only): the grid is (tiles, sample), a block never spans two samples, so its sum can go to the
 // SAMPLE's entry of a [slots][Bg] table instead of the pass's slot -- the per-sample ELBO (problems.py:451-456, reduce=False).
-template <typename TA, bool FUSED = false, bool LOSS = false, bool ROWS = false>
+// LS = Out3LossW (ROWS with the gradient output: training with per-sample weights): the loss argument also carries one weight per
+// sample, read once per block (block-uniform), and dlogit = ((sigmoid - t) * grad_scale) * w_rec[sample] -- the product in that
+// order, so that w = 1 gives the unweighted dlogit bit for bit.  The sums stay unweighted.  An instantiation of its own: the
+// launches without weights keep their argument block and their code.
+struct Out3LossW : Out3Loss {
+  const float* w_rec;     // [Bg]: weight of the sample's reconstruction gradient
+};
+template <typename TA, bool FUSED = false, bool LOSS = false, bool ROWS = false, typename LS = Out3Loss>
 __global__ __launch_bounds__(256) void tconv_out3_kernel(const TA* __restrict__ a,         // [Bt][Hi][Wi][32]
                                                          const float* __restrict__ w,      // [32][3][4][4]
                                                          float* __restrict__ out,          // [Bt][3][2Hi][2Wi]
-                                                         int Hi, int Wi, const Out3Bn bn, const Out3Loss ls) {
+                                                         int Hi, int Wi, const Out3Bn bn, const LS ls) {
+  constexpr bool WEIGHTED = !std::is_same<LS, Out3Loss>::value;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* tile = reinterpret_cast<float*>(smem);           // [32][TH][PX_LD]
   const int tid = threadIdx.x;
@@ -160,6 +169,8 @@ __global__ __launch_bounds__(256) void tconv_out3_kernel(const TA* __restrict__ 
     const bool keep = out != nullptr && (ls.logit_group < 0 || ls.logit_group == grp);
     const int ob = ls.logit_group < 0 ? b : smp;
     float part = 0.f, part_u = 0.f;
+    float wr = 1.f;
+    if constexpr (WEIGHTED) wr = ls.w_rec[smp];
 #pragma unroll
     for (int co = 0; co < 3; ++co)
 #pragma unroll
@@ -181,6 +192,7 @@ __global__ __launch_bounds__(256) void tconv_out3_kernel(const TA* __restrict__ 
               part += l;
               part_u += lu;
               d[k] = mk[k] * (sg - tm) * ls.grad_scale;
+              if constexpr (WEIGHTED) d[k] *= wr;
             }
           } else {
 #pragma unroll
@@ -189,6 +201,7 @@ __global__ __launch_bounds__(256) void tconv_out3_kernel(const TA* __restrict__ 
               bce_elem(x[k], t[k], l, sg);
               part += l;
               d[k] = (sg - t[k]) * ls.grad_scale;
+              if constexpr (WEIGHTED) d[k] *= wr;
             }
           }
         }
@@ -311,6 +324,45 @@ extern "C" int mmdyn_tconv_out3_bn_bce_rows(const void* y, const float* mean, co
     hipLaunchKernelGGL((tconv_out3_kernel<bf16_t, true, true, true>), grid, dim3(256), smem, (hipStream_t)stream, (const bf16_t*)y, w, logits, Hi, Wi, bn, ls);
   else
     hipLaunchKernelGGL((tconv_out3_kernel<float, true, true, true>), grid, dim3(256), smem, (hipStream_t)stream, (const float*)y, w, logits, Hi, Wi, bn, ls);
+  MMDYN_LAUNCH_CHECK();
+}
+
+/* mmdyn_tconv_out3_bn_bce_rows WITH the gradient output, weighted per sample: the sums go to loss_rows / unmasked_rows unweighted
+ * as in the rows launch, dlogit = ((sigmoid - t) * grad_scale) * w_rec[b] (see Out3LossW).  See the header. */
+extern "C" int mmdyn_tconv_out3_bn_bce_rows_grad(const void* y, const float* mean, const float* rstd, const float* gamma,
+                                                 const float* beta, const float* w, float* logits, int logits_group,
+                                                 const float* target, const float* mask, int mask_channels, float* dlogit,
+                                                 const float* w_rec, double* loss_rows, double* unmasked_rows,
+                                                 const int* slot_of_group, int n_slots, float grad_scale, int G, int Bg, int Hi,
+                                                 int Wi, int b16, void* stream) {
+  if (!y || !mean || !rstd || !gamma || !beta || !w || !target || !dlogit || !w_rec || !loss_rows || !slot_of_group) return MMDYN_ERR_NULL;
+  const int64_t Bt = (int64_t)G * Bg;
+  if (G <= 0 || G > MMDYN_BCE_GROUPS_MAX || Bg <= 0 || Hi % TI || Wi % TI || Bt > 65535 || b16 < 0 || b16 > 2) return MMDYN_ERR_SHAPE;
+  if (logits_group < -1 || logits_group >= G || (mask && mask_channels != 1 && mask_channels != 3) || n_slots <= 0) return MMDYN_ERR_SHAPE;
+  if (Bt * Hi * Wi * 32 >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  dim3 grid((Hi / TI) * (Wi / TI), (unsigned)Bt);
+  size_t smem = (size_t)32 * CH_LD * sizeof(float);
+  const Out3Bn bn{mean, rstd, gamma, beta, Bg};
+  Out3LossW ls{};
+  ls.target = target;
+  ls.mask = mask;
+  ls.dlogit = dlogit;
+  ls.loss = loss_rows;
+  ls.unmasked = unmasked_rows;
+  for (int i = 0; i < G; ++i) {
+    if (slot_of_group[i] >= n_slots) return MMDYN_ERR_SHAPE;
+    ls.slot[i] = slot_of_group[i];
+  }
+  ls.mask_c = mask ? mask_channels : 1;
+  ls.logit_group = logits_group;
+  ls.grad_scale = grad_scale;
+  ls.w_rec = w_rec;
+  if (b16 == 2)
+    hipLaunchKernelGGL((tconv_out3_kernel<half_t, true, true, true, Out3LossW>), grid, dim3(256), smem, (hipStream_t)stream, (const half_t*)y, w, logits, Hi, Wi, bn, ls);
+  else if (b16 == 1)
+    hipLaunchKernelGGL((tconv_out3_kernel<bf16_t, true, true, true, Out3LossW>), grid, dim3(256), smem, (hipStream_t)stream, (const bf16_t*)y, w, logits, Hi, Wi, bn, ls);
+  else
+    hipLaunchKernelGGL((tconv_out3_kernel<float, true, true, true, Out3LossW>), grid, dim3(256), smem, (hipStream_t)stream, (const float*)y, w, logits, Hi, Wi, bn, ls);
   MMDYN_LAUNCH_CHECK();
 }
 

@@ -128,6 +128,12 @@ _SIGNATURES = {
     "mmdyn_poe_bwd_avail": "pppppppp" + "f" + "iiii" + "pp",
     "mmdyn_complete_select": "ppp" + "i" + "p" + "iii" + "p",
     "mmdyn_elbo_assemble_rows_avail": "ppppppppp" + "ii" + "ff" + "p" + "i" + "p",
+    "mmdyn_tconv_out3_bn_bce_rows_grad": "ppppppp" + "i" + "pp" + "i" + "ppppp" + "i" + "f" + "iiiii" + "p",
+    "mmdyn_bce_logits_rows_groups_grad": "ppp" + "i" + "ppppp" + "i" + "f" + "iiii" + "p",
+    "mmdyn_mse_rows_groups_grad": "pppppp" + "i" + "f" + "iii" + "p",
+    "mmdyn_poe_bwd_weighted": "ppppppp" + "f" + "p" + "iiii" + "pp",
+    "mmdyn_reparam_bwd_weighted": "pppp" + "f" + "ppp" + "iii" + "p",
+    "mmdyn_elbo_assemble_weighted": "pppppppppp" + "ii" + "ff" + "p" + "i" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

@@ -341,6 +341,7 @@ class MVAEStep:
             for b in model.buffers():
                 dist.broadcast(b, 0, group=process_group)
         self.last = {}
+        self.last_rows = None            # a step with sample_weight: the unweighted per-sample tables of its batch (dict, see forward)
         self.lanes = _Lanes(dev, two_lanes)
         # every weight repack of a step (conv tap-major packs, FC permutations / transposes, fused heads) as ONE
         # kernel launch over a device-resident plan; the emulation backend packs per stack instead
@@ -444,7 +445,23 @@ class MVAEStep:
             self.klw.fill_(float(kl_weight))
             self._klw_host = float(kl_weight)
 
-    def _begin(self, inputs, targets, kl_weight, train, loss_mask=None, condition=None):
+    def _check_weights(self, sample_weight, kl, B):
+        """The per-sample weights in the form the kernels take (fp32 [B], contiguous, on the step's device), or None."""
+        if kl not in ("batch", "sample"):
+            raise ValueError("kl must be 'batch' (the reference's row: the batch-total KL) or 'sample'")
+        if sample_weight is None:
+            return None
+        if self.pg is not None:
+            raise ValueError("sample_weight with a process group is not built: data-parallel weighting is out of scope")
+        if not torch.is_tensor(sample_weight) or sample_weight.numel() != B or sample_weight.dim() > 2 or \
+                not sample_weight.dtype.is_floating_point:
+            raise ValueError(f"sample_weight must be a floating-point tensor of B = {B} values")
+        for name in ("bce_logits_rows_groups_grad", "mse_rows_groups_grad", "poe_bwd_weighted", "elbo_assemble_weighted"):
+            ops.backend_op(name)         # a backend without the weighted ops: an error before anything is launched
+        return sample_weight.detach().reshape(B).to(device=self.params.flat.device, dtype=torch.float32).contiguous()
+
+    def _begin(self, inputs, targets, kl_weight, train, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
+        sample_weight = self._check_weights(sample_weight, kl, inputs[0].shape[0])
         self._set_kl_weight(kl_weight)
         if self.conditional:
             from .models.vae import _condition
@@ -478,7 +495,10 @@ class MVAEStep:
                     "pose": inputs[2].contiguous() if self.use_pose else None,
                     "pose_tg": targets[2].contiguous() if self.use_pose else None,
                     "kl_weight": float(kl_weight), "train": train, "pk": {}, "lmask": loss_mask, "cond": condition,
-                    "rows": None}                 # score_step: fp64 [4][P][B] per-sample bce / mse / kl / unmasked-bce tables
+                    "rows": None,                 # score_step: fp64 [4][P][B] per-sample bce / mse / kl / unmasked-bce tables
+                    # per-sample weights (fp32 [B]) of the training loss and the KL mode: the row tables are then allocated by the
+                    # pre-phase, the three gradient seeds take weight vectors, the assembly is the weighted one
+                    "w": sample_weight, "kl_mode": 1 if kl == "sample" else 0, "w_kl": None}
 
     def _passes_of(self, m):
         return self.pass_v if m == "v" else self.pass_t
@@ -499,6 +519,8 @@ class MVAEStep:
         c["mask"] = {"v": mv, "t": mt}
         LN.join()
         self.acc.zero_()
+        if c["w"] is not None:                    # (inside the captured region: a replay starts from cleared tables)
+            c["rows"] = torch.zeros(4, self.P, c["B"], dtype=torch.float64, device=c["dev"])
         if self._bad_index is not None:
             self._bad_index.zero_()
         if self._hg_grad is not None:
@@ -614,7 +636,7 @@ class MVAEStep:
                     mask_channels=1 if mk is None else mk.shape[1], acc_u=None if mk is None else self.acc[3])
         rows = c["rows"]
         if rows is not None:
-            spec.update(rows=rows[0], rows_u=None if mk is None else rows[3])
+            spec.update(rows=rows[0], rows_u=None if mk is None else rows[3], weights=c["w"])
         lg, c["d" + m] = yield from layers.decoder_forward_steps(FP.sub(dec), self._buffers(dec), zz, len(plist),
                                                                  packed=c["pk"].get("d" + m), cond=cond, loss=spec if FUSED_BCE else None,
                                                                  z_planes=c.get("zzpl" + m))
@@ -623,6 +645,13 @@ class MVAEStep:
             c["lg_joint_only" + m] = not self.keep_logits
             return
         c["lg_joint_only" + m] = False
+        if rows is not None and c["w"] is not None and c["train"]:
+            dl = torch.empty_like(lg)
+            ops.B.bce_logits_rows_groups_grad(lg, tg, dl, c["w"], rows[0], slots, B, tg[0].numel(), self.loss_scale / B, mask=mk,
+                                              hw=tg[0, 0].numel(), mask_channels=1 if mk is None else mk.shape[1],
+                                              unmasked_rows=None if mk is None else rows[3])
+            c["lg" + m], c["dl" + m] = lg, dl
+            return
         if rows is not None:
             ops.B.bce_logits_rows_groups(lg, tg, rows[0], slots, B, tg[0].numel(), mask=mk, hw=tg[0, 0].numel(),
                                          mask_channels=1 if mk is None else mk.shape[1],
@@ -646,7 +675,10 @@ class MVAEStep:
             pr, c["dp"] = layers.pose_decoder_forward(FP.sub("pose_decoder"), zp)
             dpr = torch.empty_like(pr) if c["train"] else None
             # every pose-bearing pass against the same target: one launch, one loss slot per pass
-            if c["rows"] is not None:
+            if c["rows"] is not None and c["w"] is not None and c["train"]:
+                ops.B.mse_rows_groups_grad(pr, c["pose_tg"], dpr, c["w"], c["rows"][1], list(self.pass_p), B, 7,
+                                           self.loss_scale * self.pose_multiplier / B)
+            elif c["rows"] is not None:
                 ops.B.mse_rows_groups(pr, c["pose_tg"], c["rows"][1], list(self.pass_p), B, 7)
             else:
                 ops.B.mse_groups(pr, c["pose_tg"], dpr, self.acc[1], list(self.pass_p), B * 7,
@@ -660,6 +692,20 @@ class MVAEStep:
             for k, used in ((0, True), (1, self.use_pose), (3, c["lmask"] is not None)):
                 if used:                          # (acc was zeroed by _ph_pre: an unused table's sums stay zero)
                     torch.sum(c["rows"][k], 1, out=self.acc[k][:self.P])
+        if c["w"] is not None:
+            # L = (1/B) sum_b w_b row_b and its per-pass parts; the unweighted rows / partials of the batch ride along
+            B, P, tab = c["B"], self.P, c["rows"]
+            out, partials = torch.empty(B, device=c["dev"]), torch.empty(P, B, device=c["dev"])
+            # kl="batch": the batch-total KL sits in every row, so its gradient is weighted by sum_b w_b -- written as a [B] vector
+            # by the same launch (nothing synchronises with the host); kl="sample": the weights themselves
+            c["w_kl"] = c["w"] if c["kl_mode"] else torch.empty(B, device=c["dev"])
+            ops.B.elbo_assemble_weighted(tab[0], tab[1] if self.use_pose else None, tab[2], self.acc[2], c["w"], self.loss,
+                                         self.partials, out, partials, None if c["kl_mode"] else c["w_kl"], P, B, 1.0,
+                                         self.pose_multiplier, self.klw, c["kl_mode"])
+            self.last_rows = {"rows": out, "partials": partials, "bce_rows": tab[0], "mse_rows": tab[1], "kl_rows": tab[2],
+                              "unmasked_bce_rows": tab[3] if c["lmask"] is not None else None,
+                              "kl": "sample" if c["kl_mode"] else "batch"}
+            return
         ops.B.elbo_assemble(self.acc[0], self.acc[1], self.acc[2], self.loss, self.partials, self.P, c["B"],
                             1.0, self.pose_multiplier, self.klw)
 
@@ -719,6 +765,10 @@ class MVAEStep:
         else:
             c["dov"], c["dot"] = torch.empty_like(c["ov"]), torch.empty_like(c["ot"])
             c["dop"] = torch.empty_like(c["op"]) if self.use_pose else None
+        if c["w"] is not None:
+            ops.B.poe_bwd_weighted(self._passes(c, B, [c["dov"], c["dot"], c["dop"]], blocks), c["eps"], c["mu"], c["lv"], None,
+                                   None, None, self.loss_scale / B, c["w_kl"], True, P, B, L, self.klw)
+            return
         ops.B.poe_bwd(self._passes(c, B, [c["dov"], c["dot"], c["dop"]], blocks), c["eps"], c["mu"], c["lv"], None, None,
                       None, self.loss_scale / B, True, P, B, L, self.klw)
 
@@ -773,21 +823,32 @@ class MVAEStep:
 
     # ------------------------------------------------------------------------------------------
     @_with_precision
-    def forward(self, inputs, targets, kl_weight, train=True, loss_mask=None, condition=None, rows=False):
+    def forward(self, inputs, targets, kl_weight, train=True, loss_mask=None, condition=None, rows=False, sample_weight=None,
+                kl="batch"):
         """Runs the forward schedule and the loss; with train=True also fills the loss gradients needed by
         :meth:`backward`.  Returns the device scalar loss (fp32).  ``loss_mask`` ([B][1 or C][H][W], models without pose):
         the reference's --mask-loss, multiplying logits and targets of every image term.  ``condition``: the condition of the
         --conditional models -- [B][condition_dim] real values (the shock force), or class indices [B] / [B,1] of any integer
-        dtype for a categorical model (an index out of range: :meth:`check_condition`)."""
-        self._begin(inputs, targets, kl_weight, train, loss_mask, condition)
+        dtype for a categorical model (an index out of range: :meth:`check_condition`).
+
+        ``sample_weight`` (fp32 [B], any finite values; None: the unweighted step, on exactly its launches): the loss becomes
+        L = (1/B) sum_b w_b * row_b, with row_b the per-sample ELBO of :meth:`score_step` in the same ``kl`` mode -- ``"batch"``: the
+        reference's ``(w * rows).sum() / B`` (problems.py:415-417, 451-456: the batch-total KL sits in every row and is weighted by
+        sum_b w_b); ``"sample"``: each sample's own KL (with w = 1 this is the unweighted loss).  With ``train=True`` the three
+        gradient seeds of :meth:`backward` (BCE, MSE, KL) are scaled per sample.  ``self.partials`` holds the weighted per-pass
+        parts, ``self.last_rows`` the unweighted per-sample tables (``rows``, ``partials``, ``bce_rows``, ``mse_rows``,
+        ``kl_rows``) as a by-product.  BatchNorm statistics are those of the UNWEIGHTED batch, as in the reference's autograd: a
+        zero weight does not remove a sample from them.  Weights are not inspected (NaN / Inf propagate)."""
+        self._begin(inputs, targets, kl_weight, train, loss_mask, condition, sample_weight, kl)
         with layers.bad_index_into(self._bad_index):
             return self._forward_schedule(rows, train)
 
     def _forward_schedule(self, rows, train):
         LN = self.lanes
         if rows:
-            if train:
-                raise ValueError("per-sample rows are an evaluation result (train=False): there is no gradient path")
+            if train or self.ctx["w"] is not None:
+                raise ValueError("rows=True is the evaluation schedule of score_step; a training step with per-sample rows takes "
+                                 "sample_weight (its rows are in self.last_rows)")
             self.ctx["rows"] = torch.zeros(4, self.P, self.ctx["B"], dtype=torch.float64, device=self.ctx["dev"])
         self._ph_pre()
         LN.fork()
@@ -895,17 +956,18 @@ class MVAEStep:
         return int(self.adam_state[4])
 
     @_with_precision
-    def train_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None):
+    def train_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
         """zero_grad -> forward -> backward -> (all-reduce) -> Adam, as problems.py:150-155.  Gradients are
-        overwritten, not accumulated, so no zero_grad pass is needed."""
-        loss = self.forward(inputs, targets, kl_weight, train=True, loss_mask=loss_mask, condition=condition)
+        overwritten, not accumulated, so no zero_grad pass is needed.  ``sample_weight`` / ``kl``: see :meth:`forward`."""
+        loss = self.forward(inputs, targets, kl_weight, train=True, loss_mask=loss_mask, condition=condition,
+                            sample_weight=sample_weight, kl=kl)
         handles = self.backward()
         self.optimizer_step(handles)
         return loss
 
     # ------------------------------------------------------------------------------------------
     @_with_precision
-    def train_step_graphed(self, inputs, targets, kl_weight, loss_mask=None, condition=None):
+    def train_step_graphed(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
         """Same as :meth:`train_step`, replayed from HIP graphs: the ~300 kernel launches of a step are captured
         once per batch shape (the KL weight is read from device memory).  Each phase is its OWN graph: the visual and the tactile phases are
         linear kernel chains that are launched concurrently on two streams (a single graph with parallel branches
@@ -913,10 +975,14 @@ class MVAEStep:
         Each lane captures into its own memory pool, so concurrently replayed graphs never share scratch memory.
         Inputs are copied into static buffers; random draws advance through a device-side counter and Adam's step
         count lives on the device, so every replay is a real optimiser step.  With more than one rank the gradient
-        all-reduce and Adam run after the graphs."""
+        all-reduce and Adam run after the graphs.  ``sample_weight`` / ``kl`` (see :meth:`forward`): the weights are one more static
+        input; the capture key carries "weighted" and the KL mode, so one captured step serves every weight vector of a shape."""
+        sample_weight = self._check_weights(sample_weight, kl, inputs[0].shape[0])
         if self._sync is not None and not self._sync_graph_ok:
-            return self.train_step(inputs, targets, kl_weight, loss_mask, condition)      # (gloo: collectives cannot be captured)
+            return self.train_step(inputs, targets, kl_weight, loss_mask, condition, sample_weight, kl)      # (gloo: collectives cannot be captured)
         key = tuple(tuple(x.shape) for x in inputs) + ((tuple(loss_mask.shape),) if loss_mask is not None else ())
+        if sample_weight is not None:
+            key += (("weighted", kl),)
         if condition is not None:
             from .models.vae import _condition
             condition = _condition(condition, True, self.categorical)
@@ -927,6 +993,7 @@ class MVAEStep:
             self._static_tg = [x.clone() for x in targets]
             self._static_mask = None if loss_mask is None else loss_mask.to(torch.float32).clone()
             self._static_cond = None if condition is None else condition.clone()
+            self._static_w, self._static_kl = None if sample_weight is None else sample_weight.clone(), kl
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             if self._sync is not None:
@@ -935,7 +1002,8 @@ class MVAEStep:
                 self._warm_works = []                          # (gradient buckets: _reduce_bucket)
             try:
                 with torch.cuda.stream(side):                  # warm-up outside capture (allocator, lazy init)
-                    self.train_step(self._static_in, self._static_tg, kl_weight, self._static_mask, self._static_cond)
+                    self.train_step(self._static_in, self._static_tg, kl_weight, self._static_mask, self._static_cond,
+                                    self._static_w, kl)
                 torch.cuda.current_stream().wait_stream(side)
                 if self.pg is not None:
                     self._drain_before_capture(key)
@@ -948,6 +1016,7 @@ class MVAEStep:
             mark = getattr(ops.B, "ticket_mark", None)
             if mark is not None:
                 mark()
+            warm_rows = self.last_rows if sample_weight is not None else None
             try:
                 captured = self._capture(kl_weight)
             except BaseException:
@@ -962,6 +1031,12 @@ class MVAEStep:
             # between rewrites self.loss_scale, the replayed gradients keep this one (the eager Adam of the data-parallel
             # replay divides by it)
             self._graph = (key, captured, self.loss_scale, slots)
+            if warm_rows is not None:
+                # last_rows now names the captured step's static outputs, which no replay has written yet: this call's rows are
+                # the warm-up step's
+                for k, t in self.last_rows.items():
+                    if torch.is_tensor(t):
+                        t.copy_(warm_rows[k])
             return self.loss             # the warm-up above WAS this call's optimiser step
         # the batch moves into the captured step's static buffers with ONE launch (six runtime copies before round 6)
         moves = list(zip(self._static_in + self._static_tg, list(inputs) + list(targets)))
@@ -969,6 +1044,8 @@ class MVAEStep:
             moves.append((self._static_mask, loss_mask.reshape(self._static_mask.shape)))
         if condition is not None:
             moves.append((self._static_cond, condition))
+        if sample_weight is not None:
+            moves.append((self._static_w, sample_weight))
         if COPY_MANY and all(d.dtype == s_.dtype and s_.is_cuda and s_.is_contiguous() for d, s_ in moves):
             ops.B.copy_many(moves)
         else:                        # (a batch that arrives in another type / layout / on the host: the runtime's converting copy)
@@ -1113,7 +1190,8 @@ class MVAEStep:
         bad_scope = layers.bad_index_into(self._bad_index)
         bad_scope.__enter__()
         try:
-            self._begin(self._static_in, self._static_tg, kl_weight, True, self._static_mask, self._static_cond)
+            self._begin(self._static_in, self._static_tg, kl_weight, True, self._static_mask, self._static_cond,
+                        getattr(self, "_static_w", None), getattr(self, "_static_kl", "batch"))
             for stage in stages:
                 row = []
                 for lane, fn in stage:
@@ -1211,8 +1289,10 @@ class MVAEStep:
 
     @torch.no_grad()
     @_with_precision
-    def eval_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None):
-        loss = self.forward(inputs, targets, kl_weight, train=False, loss_mask=loss_mask, condition=condition)
+    def eval_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
+        """``sample_weight`` / ``kl``: the weighted loss of :meth:`forward` without gradients (rows in ``self.last_rows``)."""
+        loss = self.forward(inputs, targets, kl_weight, train=False, loss_mask=loss_mask, condition=condition,
+                            sample_weight=sample_weight, kl=kl)
         self.ctx = None
         return loss
 

@@ -918,7 +918,8 @@ def decoder_forward_steps(P, buf, z, G=1, repeat=1, logits=True, packed=None, co
     """z: [Bt, L] -> logits NCHW [Bt,3,S,S]; returns (logits, ctx).  ``logits=False`` stops after the last
     BatchNorm (used only to reproduce the running statistics of the reference's unused decoder passes).
     ``loss`` (fused engine): dict(target [Bg,3,S,S], slots [G], acc (fp64 loss slots), grad_scale, want_grad, keep (group whose logits
-    are published, or None: all), mask, mask_channels, acc_u) -- where the last layer is the direct fused kernel, the BCE term of
+    are published, or None: all), mask, mask_channels, acc_u; rows / rows_u: fp64 [slots][Bg] per-sample tables instead of acc; weights:
+    fp32 [Bg] per-sample weights of the gradient, with rows and want_grad) -- where the last layer is the direct fused kernel, the BCE term of
     problems.py:433-437 rides in its epilogue: ctx["dl"] = dlogits (or None), ctx["loss_fused"] = True, and the returned logits hold
     group ``keep`` only ([Bg,3,S,S]).  Otherwise ctx["loss_fused"] is False and the caller runs the loss kernel."""
     Bt, L0 = z.shape
@@ -980,7 +981,12 @@ def decoder_forward_steps(P, buf, z, G=1, repeat=1, logits=True, packed=None, co
             bn_args = (t["y"], t["m"], t["r"], t["bn"].gamma, t["bn"].beta, P[f"hallucinate.{last}.weight"], out,
                        -1 if keep is None else keep, loss["target"])
             mk = dict(mask=loss.get("mask"), mask_channels=loss.get("mask_channels", 1))
-            if loss.get("rows") is not None:
+            if loss.get("rows") is not None and loss.get("weights") is not None and loss["want_grad"]:
+                # training with per-sample weights: the rows epilogue WITH the gradient output, dlogit scaled by the sample's weight
+                c["dl"] = _new(z, Bt, 3, S, S)
+                ops.B.tconv_out3_bn_bce_rows_grad(*bn_args, c["dl"], loss["weights"], loss["rows"], loss["slots"], loss["grad_scale"],
+                                                  G, Bg, H, H, unmasked_rows=loss.get("rows_u"), **mk)
+            elif loss.get("rows") is not None:
                 # per-sample scoring (evaluation only): the same epilogue, one sum per sample -> loss["rows"] [slots][Bg]
                 c["dl"] = None
                 ops.B.tconv_out3_bn_bce_rows(*bn_args, loss["rows"], loss["slots"], G, Bg, H, H, unmasked_rows=loss.get("rows_u"), **mk)

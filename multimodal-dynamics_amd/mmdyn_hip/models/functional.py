@@ -378,6 +378,95 @@ def mse_rows_add(rows, r, t):
     ops.B.mse_rows_groups(rr, tt, rows, [0], rr.shape[0], rr.numel() // rr.shape[0])
 
 
+class BCERowsFn(torch.autograd.Function):
+    """torch.sum(F.binary_cross_entropy_with_logits(x, t, reduce=False), (1, 2, 3)) with the optional loss mask of
+    problems.py:445-447 (problems.py:409-416, 445-452) -> fp64 [B].  The backward is the weighted seed kernel with the upstream
+    gradient as the per-sample weight: dlogit[b] = (sigmoid - t) * grad_output[b], one pass over the logits."""
+
+    @staticmethod
+    def forward(ctx, logits, target, mask):
+        x, t = logits.detach().contiguous(), target.detach().contiguous()
+        B = x.shape[0]
+        chw, hw = x.numel() // B, x.shape[-1] * x.shape[-2]
+        mk, mc = (None, 1) if mask is None else _loss_mask(mask, x)
+        rows = torch.zeros(1, B, dtype=torch.float64, device=x.device)
+        ops.B.bce_logits_rows_groups(x, t, rows, [0], B, chw, mask=mk, hw=hw, mask_channels=mc)
+        ctx.x, ctx.t, ctx.mk, ctx.geom = x, t, mk, (B, chw, hw, mc)
+        return rows[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        B, chw, hw, mc = ctx.geom
+        w = g.detach().to(torch.float32).contiguous()
+        d = torch.empty_like(ctx.x)
+        scratch = torch.zeros(1, B, dtype=torch.float64, device=d.device)
+        ops.backend_op("bce_logits_rows_groups_grad")(ctx.x, ctx.t, d, w, scratch, [0], B, chw, 1.0, mask=ctx.mk, hw=hw,
+                                                      mask_channels=mc)
+        return d, None, None
+
+
+class MSERowsFn(torch.autograd.Function):
+    """torch.sum(F.mse_loss(r, t, reduce=False), 1) (problems.py:439-452) -> fp64 [B]; backward: dr[b] = 2 (r - t) * grad_output[b]."""
+
+    @staticmethod
+    def forward(ctx, r, t):
+        rr, tt = r.detach().contiguous(), t.detach().contiguous()
+        B = rr.shape[0]
+        rows = torch.zeros(1, B, dtype=torch.float64, device=rr.device)
+        ops.B.mse_rows_groups(rr, tt, rows, [0], B, rr.numel() // B)
+        ctx.r, ctx.t = rr, tt
+        return rows[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        rr = ctx.r
+        B = rr.shape[0]
+        w = g.detach().to(torch.float32).contiguous()
+        d = torch.empty_like(rr)
+        scratch = torch.zeros(1, B, dtype=torch.float64, device=d.device)
+        ops.backend_op("mse_rows_groups_grad")(rr, ctx.t, d, w, scratch, [0], B, rr.numel() // B, 1.0)
+        return d, None
+
+
+class ElboRowsFn(torch.autograd.Function):
+    """The per-sample ELBO of ONE pass from its row tables (problems.py:415-417, 451-456): bce_rows + pose_multiplier * mse_rows +
+    kl_weight * KL -> fp32 [B], nothing divided by B.  ``kl_mode`` 0: KL is the total over the batch, in every row (the
+    reference); 1: each sample's own KL.  Backward with upstream gradient g [B]: d bce_rows = g, d mse_rows = pose_multiplier * g,
+    and the KL gradient of row b through the weighted latent kernel with scale kl_weight * (kl_mode ? g[b] : sum_b g_b)."""
+
+    @staticmethod
+    def forward(ctx, bce_rows, mse_rows, means, log_var, kl_weight, pose_multiplier, kl_mode):
+        B, L = means.shape
+        m, v = means.detach().contiguous(), log_var.detach().contiguous()
+        tab = lambda t: None if t is None else t.detach().reshape(1, B).contiguous()
+        kl_sum = kl_rows = None
+        if kl_mode:
+            kl_rows = torch.empty(1, B, dtype=torch.float64, device=m.device)
+            ops.B.kl_rows(m, v, kl_rows, 1, B, L)
+        else:
+            kl_sum = torch.zeros(1, dtype=torch.float64, device=m.device)
+            ops.B.reparam_fwd(m, v, None, None, kl_sum, B, L, L)
+        out = torch.empty(B, dtype=torch.float32, device=m.device)
+        ops.B.elbo_assemble_rows(tab(bce_rows), tab(mse_rows), kl_rows, kl_sum, out, None, 1, B, kl_weight, pose_multiplier,
+                                 kl_mode=int(kl_mode))
+        ctx.m, ctx.v, ctx.kw, ctx.pm, ctx.kl_mode = m, v, float(kl_weight), float(pose_multiplier), int(kl_mode)
+        ctx.has_bce, ctx.has_mse = bce_rows is not None, mse_rows is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        m, v = ctx.m, ctx.v
+        B, L = m.shape
+        g32 = g.detach().to(torch.float32).contiguous()
+        g64 = g32.to(torch.float64)
+        dm = dv = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            w_kl = g32 if ctx.kl_mode else g32.sum().expand(B).contiguous()
+            dm, dv = torch.empty_like(m), torch.empty_like(v)
+            ops.backend_op("reparam_bwd_weighted")(m, v, None, None, ctx.kw, w_kl, dm, dv, B, L, L)
+        return (g64 if ctx.has_bce else None), (g64 * ctx.pm if ctx.has_mse else None), dm, dv, None, None, None
+
+
 def elbo_rows(bce_rows, mse_rows, means, log_var, kl_weight, pose_multiplier):
     """The reference's per-sample ELBO of ONE pass (problems.py:415-417, 451-456): recon rows + kl_weight * KL, where KL is the sum
     over the WHOLE batch -- that one scalar goes into every row, and nothing is divided by B.  -> fp32 [B], no autograd node."""

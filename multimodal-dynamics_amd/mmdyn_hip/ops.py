@@ -967,6 +967,98 @@ class HipBackend:
                                                       float(pose_multiplier), _ptr(kl_weight_dev), int(kl_mode), _stream()),
               "mmdyn_elbo_assemble_rows_avail")
 
+    # ---- weighted per-sample ELBO: the gradient seeds with a per-sample scale ----
+    @staticmethod
+    def _weights(w, B, name):
+        """Pointer of a per-sample weight vector: fp32 [B], contiguous."""
+        if w is None or w.dtype != torch.float32 or w.numel() != B or not w.is_contiguous():
+            raise ValueError(f"mmdyn_hip: {name}: the weights must be a contiguous fp32 vector of B={B} elements")
+        return _ptr(w)
+
+    def tconv_out3_bn_bce_rows_grad(self, y, mean, rstd, gamma, beta, w, logits, logits_group, target, dlogit, w_rec, loss_rows,
+                                    slot_of_group, grad_scale, G, Bg, Hi, Wi, mask=None, mask_channels=1, unmasked_rows=None):
+        """tconv_out3_bn_bce_rows with the gradient output: dlogit = ((sigmoid - t) * grad_scale) * w_rec[b]; the rows stay
+        unweighted."""
+        py, y16 = _aptr(y)
+        name = "tconv_out3_bn_bce_rows_grad"
+        if len(slot_of_group) != G or tuple(target.shape) != (Bg, 3, 2 * Hi, 2 * Wi):
+            raise ValueError(f"mmdyn_hip: {name}: one slot per group and a [Bg][3][2Hi][2Wi] target")
+        if logits is not None and logits.numel() != (G if logits_group < 0 else 1) * Bg * 3 * 4 * Hi * Wi:
+            raise ValueError(f"mmdyn_hip: {name}: logits buffer of the wrong size")
+        if dlogit is None or dlogit.numel() != G * Bg * 3 * 4 * Hi * Wi:
+            raise ValueError(f"mmdyn_hip: {name}: dlogit buffer of the wrong size")
+        if mask is not None and tuple(mask.shape) != (Bg, mask_channels, 2 * Hi, 2 * Wi):
+            raise ValueError(f"mmdyn_hip: {name}: mask {tuple(mask.shape)} is not [Bg][{mask_channels}][2Hi][2Wi]")
+        n_slots = self._row_slots(loss_rows, Bg, name)
+        if unmasked_rows is not None and self._row_slots(unmasked_rows, Bg, name) != n_slots:
+            raise ValueError(f"mmdyn_hip: {name}: unmasked_rows and loss_rows differ in shape")
+        slots = (ctypes.c_int * G)(*[int(s) for s in slot_of_group])
+        check(self.lib.mmdyn_tconv_out3_bn_bce_rows_grad(py, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(w), _ptr(logits),
+                                                         int(logits_group), _ptr(target), _ptr(mask), int(mask_channels),
+                                                         _ptr(dlogit), self._weights(w_rec, Bg, name),
+                                                         _ptr(loss_rows, torch.float64), _ptr(unmasked_rows, torch.float64),
+                                                         ctypes.addressof(slots), n_slots, float(grad_scale), G, Bg, Hi, Wi, y16,
+                                                         _stream()), "mmdyn_" + name)
+
+    def bce_logits_rows_groups_grad(self, logits, target, dlogit, w_rec, rows_out, slot_of_group, Bg, chw, grad_scale, mask=None,
+                                    hw=0, mask_channels=1, unmasked_rows=None):
+        """bce_logits_rows_groups with dlogit [G*Bg*chw] = ((sigmoid - t) * grad_scale) * w_rec[b] (zeros for a negative slot)."""
+        G = len(slot_of_group)
+        name = "bce_logits_rows_groups_grad"
+        n_slots = self._row_slots(rows_out, Bg, name)
+        if logits.numel() != G * Bg * chw or target.numel() != Bg * chw or dlogit is None or dlogit.numel() != G * Bg * chw:
+            raise ValueError(f"mmdyn_{name}: logits / dlogit / target do not match [G={G}][Bg={Bg}][chw={chw}]")
+        if mask is not None and (hw <= 0 or mask.numel() != Bg * mask_channels * hw):
+            raise ValueError(f"mmdyn_{name}: mask of {mask.numel()} elements does not match [Bg={Bg}][{mask_channels}][hw={hw}]")
+        if unmasked_rows is not None and self._row_slots(unmasked_rows, Bg, name) != n_slots:
+            raise ValueError(f"mmdyn_{name}: unmasked_rows and rows_out differ in shape")
+        slots = (ctypes.c_int * G)(*[int(s) for s in slot_of_group])
+        check(self.lib.mmdyn_bce_logits_rows_groups_grad(_ptr(logits), _ptr(target), _ptr(mask), int(mask_channels), _ptr(dlogit),
+                                                         self._weights(w_rec, Bg, name), _ptr(rows_out, torch.float64),
+                                                         _ptr(unmasked_rows, torch.float64), ctypes.addressof(slots), n_slots,
+                                                         float(grad_scale), G, Bg, chw, hw, _stream()), "mmdyn_" + name)
+
+    def mse_rows_groups_grad(self, r, t, dr, w_rec, rows_out, slot_of_group, Bg, n, grad_scale):
+        """mse_rows_groups with dr [G*Bg*n] = (2 (r - t) * grad_scale) * w_rec[b]."""
+        G = len(slot_of_group)
+        name = "mse_rows_groups_grad"
+        n_slots = self._row_slots(rows_out, Bg, name)
+        if r.numel() != G * Bg * n or t.numel() != Bg * n or dr is None or dr.numel() != G * Bg * n:
+            raise ValueError(f"mmdyn_{name}: r / dr / t do not match [G={G}][Bg={Bg}][n={n}]")
+        slots = (ctypes.c_int * G)(*[int(s) for s in slot_of_group])
+        check(self.lib.mmdyn_mse_rows_groups_grad(_ptr(r), _ptr(t), _ptr(dr), self._weights(w_rec, Bg, name),
+                                                  _ptr(rows_out, torch.float64), ctypes.addressof(slots), n_slots, float(grad_scale),
+                                                  G, Bg, n, _stream()), "mmdyn_" + name)
+
+    def poe_bwd_weighted(self, passes, eps_noise, mu, logvar, dz, g_mu, g_lv, kl_scale, w_kl, with_prior, P, B, L,
+                         kl_weight_dev=None):
+        """poe_bwd with the KL scale of row b = kl_scale * w_kl[b] (w_kl: fp32 [B])."""
+        arr = self._passes(passes)
+        check(self.lib.mmdyn_poe_bwd_weighted(ctypes.cast(arr, ctypes.c_void_p), _ptr(eps_noise), _ptr(mu), _ptr(logvar), _ptr(dz),
+                                              _ptr(g_mu), _ptr(g_lv), float(kl_scale), self._weights(w_kl, B, "poe_bwd_weighted"),
+                                              int(with_prior), P, B, L, _ptr(kl_weight_dev), _stream()), "mmdyn_poe_bwd_weighted")
+
+    def reparam_bwd_weighted(self, mu, lv, eps_noise, dz, kl_scale, w_kl, dmu, dlv, B, L, ld):
+        check(self.lib.mmdyn_reparam_bwd_weighted(mu.data_ptr(), lv.data_ptr(), _ptr(eps_noise), _ptr(dz), float(kl_scale),
+                                                  self._weights(w_kl, B, "reparam_bwd_weighted"), dmu.data_ptr(), dlv.data_ptr(),
+                                                  B, L, ld, _stream()), "mmdyn_reparam_bwd_weighted")
+
+    def elbo_assemble_weighted(self, bce_rows, mse_rows, kl_rows, kl_sum, w, loss, wpartials, out, partials, w_sum_out, P, B,
+                               kl_weight, pose_multiplier, kl_weight_dev=None, kl_mode=0):
+        """loss [1] / wpartials [P]: the weighted scalar (1/B) sum_b w_b row_b and its per-pass parts; out [B] / partials [P][B]:
+        the unweighted rows of elbo_assemble_rows; w_sum_out [B] (optional): filled with sum_b w_b.  Deterministic."""
+        for t, n, what in ((bce_rows, P * B, "bce_rows"), (mse_rows, P * B, "mse_rows"), (kl_rows, P * B, "kl_rows"),
+                           (kl_sum, P, "kl_sum"), (partials, P * B, "partials"), (out, B, "out"), (wpartials, P, "wpartials"),
+                           (w_sum_out, B, "w_sum_out"), (loss, 1, "loss")):
+            if t is not None and t.numel() < n:
+                raise ValueError(f"mmdyn_elbo_assemble_weighted: {what} holds {t.numel()} elements, needs {n}")
+        check(self.lib.mmdyn_elbo_assemble_weighted(_ptr(bce_rows, torch.float64), _ptr(mse_rows, torch.float64),
+                                                    _ptr(kl_rows, torch.float64), _ptr(kl_sum, torch.float64),
+                                                    self._weights(w, B, "elbo_assemble_weighted"), _ptr(loss), _ptr(wpartials),
+                                                    _ptr(out), _ptr(partials), _ptr(w_sum_out), P, B, float(kl_weight),
+                                                    float(pose_multiplier), _ptr(kl_weight_dev), int(kl_mode), _stream()),
+              "mmdyn_elbo_assemble_weighted")
+
     def adam_step(self, p, g, m, v, state, lr, beta1, beta2, eps, grad_scale, guarded=False):
         """guarded: ``state`` has six doubles and a gradient holding inf / NaN skips the step (counted in state[4])."""
         if guarded and state.numel() < 6:
@@ -1007,3 +1099,12 @@ def set_backend(b):
     global B
     old, B = B, b
     return old
+
+
+def backend_op(name):
+    """The op ``name`` of the active backend.  A backend that does not have it (one written before the op was added) is an error
+    that names the op, never a fallback: a ``RuntimeError``, which is also what autograd raises for a result without a graph."""
+    op = getattr(B, name, None)
+    if op is None:
+        raise RuntimeError(f"the active backend ({type(B).__name__}) has no op {name!r}; there is no fallback path")
+    return op

@@ -324,6 +324,47 @@ class Problem:
             _, rows = self._evaluate_model(inputs, targets, reduce=False)
         return rows
 
+    _rows_kl_mode = 0        # KL of the reduce=False rows: 0 the reference's (batch total in every row); train_batch may set 1
+
+    def train_batch(self, data_input, data_target, sample_weight=None, kl="sample"):
+        """One optimiser step on one batch in the loader's format with per-sample weights: ``parse_input``, then the gradient of
+        L = (1/B) sum_b w_b * row_b, where row_b is the per-sample ELBO (``kl="sample"``: with the sample's own KL -- with w = 1 the
+        ordinary loss; ``kl="batch"``: the reference's reduce=False row, ``(w * rows).sum() / B``).  ``sample_weight``: [B] floats
+        (None: ones) -- hard-example weights from :meth:`score`, importance or class-balance weights.  The fused engine runs where
+        it takes the batch, the module path otherwise.  BatchNorm statistics are those of the unweighted batch.  Returns
+        ``{"loss": the weighted scalar (device tensor), "rows": fp32 [B], the unweighted per-sample losses of this batch}``."""
+        if kl not in ("batch", "sample"):
+            raise ValueError("kl must be 'batch' (the reference's row: the batch-total KL) or 'sample'")
+        if not isinstance(self, Reconstruction):
+            raise ValueError("train_batch weights the per-sample ELBO rows of the reconstruction problems")
+        self._model.train()
+        inputs, targets = self.parse_input(data_input, data_target)
+        if self._step is not None and self._fused_applicable(inputs):
+            xs, ts = self._fused_io(inputs, targets)
+            B = xs[0].shape[0]
+            w = torch.ones(B, device=self._device) if sample_weight is None else sample_weight
+            run = self._step.train_step_graphed if self._device.type == 'cuda' else self._step.train_step
+            loss = run(xs, ts, self._kl_weight, loss_mask=self._fused_mask(targets),
+                       condition=inputs.get('shock') if self._conditional else None, sample_weight=w, kl=kl)
+            return {"loss": loss.detach().clone().reshape(()), "rows": self._step.last_rows["rows"].clone()}
+        self._optimizer.zero_grad()
+        self._rows_kl_mode = 1 if kl == "sample" else 0
+        try:
+            _, rows = self._evaluate_model(inputs, targets, reduce=False, _train_rows=True)
+        finally:
+            self._rows_kl_mode = 0
+        B = rows.shape[0]
+        if sample_weight is None:
+            w = torch.ones(B, device=rows.device)
+        else:
+            if not torch.is_tensor(sample_weight) or sample_weight.numel() != B or not sample_weight.dtype.is_floating_point:
+                raise ValueError(f"sample_weight must be a floating-point tensor of B = {B} values")
+            w = sample_weight.detach().reshape(B).to(device=rows.device, dtype=torch.float32)
+        loss = (w * rows).sum() / B
+        loss.backward()
+        self._optimizer.step()
+        return {"loss": loss.detach(), "rows": rows.detach()}
+
     # ---- fused-engine plumbing -------------------------------------------------------------------
     def _fused_applicable(self, inputs):
         return isinstance(inputs, dict) and isinstance(inputs.get('model_input'), list)
@@ -457,12 +498,14 @@ class Reconstruction(Problem):
     def _elbo_loss(self, recon_x, x, means, log_var, loss_mask=None, reduce=None, reduction='sum'):
         """(BCE_sum + kl_weight * KL) / B for VAE / CVAE (problems.py:401-419).  ``reduce=False``: the reference's per-sample
         branch (:415-417), a fp32 ``[B]`` tensor ``sum(BCE, (1, 2, 3)) + kl_weight * KL`` where KL is the total over the batch
-        (not divided by B).  That branch is forward only: the result carries no autograd graph, ``.backward()`` on it raises."""
+        (not divided by B).  The rows are an ordinary autograd tensor, as in the reference: ``rows.backward(w)`` and
+        ``(w * rows).sum().backward()`` give the gradients of the weighted loss (the seed kernels with a per-sample scale); under
+        ``torch.no_grad()`` the result carries no graph.  On a backend without the weighted seed ops the forward is unchanged and
+        the backward raises ``RuntimeError`` (``ops.backend_op``): there is no fallback."""
         self._check_reduce(reduce, reduction)
         if reduce is not None:
-            rows = torch.zeros(1, x.size(0), dtype=torch.float64, device=x.device)
-            Fn.bce_with_logits_rows_add(rows, recon_x.view(x.size()), x, loss_mask)
-            return Fn.elbo_rows(rows, None, means, log_var, self._kl_weight, self._pose_multiplier)
+            rows = Fn.BCERowsFn.apply(recon_x.view(x.size()), x, loss_mask)
+            return Fn.ElboRowsFn.apply(rows, None, means, log_var, self._kl_weight, self._pose_multiplier, self._rows_kl_mode)
         batch_size = x.size(0)
         KLD = Fn.KLFn.apply(means, log_var)
         BCE = Fn.BCEWithLogitsSumFn.apply(recon_x.view(x.size()), x, loss_mask)
@@ -471,24 +514,23 @@ class Reconstruction(Problem):
     def _mvae_elbo_loss(self, recon_x, x, means, log_var, loss_mask=None, reduce=None, reduction='sum'):
         """Sum over modalities of BCE (images) / pose_multiplier * MSE (pose) + kl_weight * KL, over B
         (problems.py:421-458).  ``reduce=False``: the reference's per-sample branch (:451-456), a fp32 ``[B]`` tensor of the
-        reconstruction terms of each sample plus ``kl_weight`` times the KL of the WHOLE batch, nothing divided by B.  Forward only:
-        the result carries no autograd graph, ``.backward()`` on it raises."""
+        reconstruction terms of each sample plus ``kl_weight`` times the KL of the WHOLE batch, nothing divided by B.  An ordinary
+        autograd tensor, as in the reference (see :meth:`_elbo_loss`); no graph under ``torch.no_grad()``."""
         self._check_reduce(reduce, reduction)
         assert len(recon_x) == len(x)
         if reduce is not None:
-            B, dev = x[0].size(0), x[0].device
-            bce, mse = torch.zeros(1, B, dtype=torch.float64, device=dev), None
+            bce = mse = None
             for i in range(len(recon_x)):
                 if len(recon_x[i].size()) > 2:
-                    Fn.bce_with_logits_rows_add(bce, recon_x[i].view(x[i].size()), x[i], loss_mask)
+                    r = Fn.BCERowsFn.apply(recon_x[i].view(x[i].size()), x[i], loss_mask)
+                    bce = r if bce is None else bce + r
                 else:
                     if loss_mask is not None:
                         raise ValueError("loss_mask is image-shaped and cannot multiply the (B, 7) pose term "
                                          "(the reference raises here too: problems.py:445-447)")
-                    if mse is None:
-                        mse = torch.zeros(1, B, dtype=torch.float64, device=dev)
-                    Fn.mse_rows_add(mse, recon_x[i], x[i])
-            return Fn.elbo_rows(bce, mse, means, log_var, self._kl_weight, self._pose_multiplier)
+                    r = Fn.MSERowsFn.apply(recon_x[i], x[i])
+                    mse = r if mse is None else mse + r
+            return Fn.ElboRowsFn.apply(bce, mse, means, log_var, self._kl_weight, self._pose_multiplier, self._rows_kl_mode)
         batch_size = x[0].size(0)
         recon_error = 0
         kl_divergence = Fn.KLFn.apply(means, log_var)
@@ -630,7 +672,8 @@ class SeqModeling(Reconstruction):
         loss_mask = targets['loss_mask'] if self.parameters['mask_loss'] else None
         if 'mvae' in self.parameters['model_name']:
             xs, ts = self._fused_io(x, targets)
-            if reduce is False and getattr(self, '_step', None) is not None and self._fused_applicable(x):
+            if reduce is False and getattr(self, '_step', None) is not None and self._fused_applicable(x) \
+                    and not kwargs.get('_train_rows'):
                 # the fused engine's evaluation schedule ending in the row kernels (the reference's rows: batch-total KL)
                 res = self._step.score_step(xs, ts, self._kl_weight, loss_mask=loss_mask,
                                             condition=x.get('shock') if self._conditional else None, kl="batch")
