@@ -632,6 +632,19 @@ int mmdyn_bn_swish_fwd_planes(const float* y, const float* mean, const float* rs
 int mmdyn_bn_swish_bwd_apply_planes(const float* da, const float* y, const float* mean, const float* rstd, const float* gamma,
                                     const float* beta, const float* sums, float* dy, void* dy_planes, int G, int rows_per_group,
                                     int C, int da_is_du, void* stream);
+/* Backward of EVAL-mode nn.BatchNorm2d + Swish (vae.py:200-208, 268-276 under module.eval(): F.batch_norm(training=False), whose
+ * autograd the reference gets for free) in ONE pass over [G * rows_per_group][C], fp32, shapes as the kernels above.  The forward
+ * is u = gamma * (y - mean) * rstd + beta, a = swish(u), with mean / rstd [G][C] the running estimates (mmdyn_bn_eval_stats):
+ * constants, so there are no batch-mean terms:  du = da_is_du ? da : da * swish'(u),  dy = du * gamma * rstd.
+ *   dy (fp32) and / or dy_planes (the plane tensor of mmdyn_bn_swish_bwd_apply_planes): at least one is required;
+ *   partial (nullable) [G][T][2][C], T = mmdyn_colstats_tiles(rows_per_group): per tile sum du and sum du * xhat -- the layout and
+ *   meaning of mmdyn_bn_swish_bwd_reduce's output, so mmdyn_bn_bwd_finalize turns it into dgamma / dbeta; written by the same pass
+ *   from the values in registers, in a fixed order (no atomics);
+ *   with da_is_du = 1 and partial == NULL neither u nor xhat is needed: y is not read and may be NULL.
+ * Added without touching an existing signature or workspace: the revision stays 6. */
+int mmdyn_bn_eval_swish_bwd(const float* da, const float* y, const float* mean, const float* rstd, const float* gamma,
+                            const float* beta, float* dy, void* dy_planes, float* partial, int G, int rows_per_group, int C,
+                            int da_is_du, void* stream);
 int mmdyn_bn_swish_fwd_b16(const uint16_t* y, const float* mean, const float* rstd, const float* gamma,
                            const float* beta, uint16_t* a, int G, int rows_per_group, int C, int half, void* stream);
 int mmdyn_bn_swish_bwd_reduce_b16(const uint16_t* da, const uint16_t* y, const float* mean, const float* rstd,

@@ -416,6 +416,107 @@ __global__ void bn_swish_bwd_apply_planes_kernel(const float* __restrict__ da, c
   }
 }
 
+// Eval-mode BatchNorm + Swish backward (nn.BatchNorm2d with training=False: mean / rstd are the running estimates, constants of the
+// pass): dy = du * gamma * rstd with no batch-mean terms, so the reduce -> finalize -> apply sequence of the train mode is ONE pass.
+// One block = one tile of rows of one group (the tiling of colreduce_kernel: the partial table has its layout), one thread = 8
+// channels of every RL-th row of the tile: two 16-byte loads per input and row, dy as two 16-byte stores and / or three 16-byte
+// plane stores.  PARTIAL: the tile's column sums (sum du, sum du * xhat) -> partial[g][t][2][C] from the values already in
+// registers: per-thread accumulation + one LDS pass in a fixed order (no atomics, deterministic).  NEED_Y = !da_is_du || PARTIAL:
+// without it y, mean and beta are not read.
+template <bool NEED_Y, bool PARTIAL>
+__global__ __launch_bounds__(256) void bn_eval_swish_bwd_kernel(const float* __restrict__ da, const float* __restrict__ y, BnParams bp,
+                                                                float* __restrict__ dy, bf16_t* __restrict__ dyp,
+                                                                float* __restrict__ partial, int rows_per_group, int C, int T,
+                                                                int tile_rows, int da_is_du) {
+  __shared__ float red[PARTIAL ? 256 * 16 : 1];
+  const int tid = threadIdx.x;
+  const int g = blockIdx.y, t = blockIdx.x;
+  const int CV = C >> 3;        // 8-channel columns (4..32)
+  const int RL = 256 / CV;      // row lanes (RL * CV == 256: C / 8 divides 256 for every C bn_shape_ok admits)
+  const int rl = tid / CV, cv = tid - rl * CV;
+  const int r_begin = t * tile_rows;
+  const int r_end = min(rows_per_group, r_begin + tile_rows);
+  f32x4 sc[2], mean4[2], rstd4[2], gam4[2], bet4[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c0 = cv * 8 + q * 4;
+    rstd4[q] = *reinterpret_cast<const f32x4*>(bp.rstd + (size_t)g * C + c0);
+    gam4[q] = *reinterpret_cast<const f32x4*>(bp.gamma + c0);
+    sc[q] = gam4[q] * rstd4[q];
+    if (NEED_Y) {
+      mean4[q] = *reinterpret_cast<const f32x4*>(bp.mean + (size_t)g * C + c0);
+      bet4[q] = *reinterpret_cast<const f32x4*>(bp.beta + c0);
+    }
+  }
+  f32x4 s0[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, s1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  const size_t base = (size_t)g * rows_per_group;
+  // 2 rows per iteration: 4 (da alone) or 8 independent 16-byte loads in flight per thread
+  for (int r = r_begin + rl; r < r_end; r += 2 * RL) {
+    f32x4 d[2][2], v[2][2];
+#pragma unroll
+    for (int u2 = 0; u2 < 2; ++u2) {
+      const int rr = r + u2 * RL;
+      const size_t off = (base + (rr < r_end ? rr : r)) * C + cv * 8;
+      ldv_nt<float>(da + off, &d[u2][0]);
+      ldv_nt<float>(da + off + 4, &d[u2][1]);
+      if (NEED_Y) {
+        ldv_nt<float>(y + off, &v[u2][0]);
+        ldv_nt<float>(y + off + 4, &v[u2][1]);
+      }
+    }
+#pragma unroll
+    for (int u2 = 0; u2 < 2; ++u2) {
+      const int rr = r + u2 * RL;
+      if (rr >= r_end) continue;
+      f32x4 o[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float du = d[u2][q][k];
+          if (NEED_Y) {
+            const float xh = (v[u2][q][k] - mean4[q][k]) * rstd4[q][k];
+            if (!da_is_du) du *= swish_gradf_(gam4[q][k] * xh + bet4[q][k]);
+            if (PARTIAL) {
+              s0[q][k] += du;
+              s1[q][k] += du * xh;
+            }
+          }
+          o[q][k] = du * sc[q][k];
+        }
+      }
+      const size_t row = base + rr;
+      if (dy) {
+        stv_nt<float>(dy + row * C + cv * 8, o);
+        stv_nt<float>(dy + row * C + cv * 8 + 4, o + 1);
+      }
+      if (dyp) store_planes8(dyp + row * 3 * (size_t)C + cv * 8, C, o[0], o[1]);
+    }
+  }
+  if (PARTIAL) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        red[tid * 16 + q * 4 + k] = s0[q][k];
+        red[tid * 16 + 8 + q * 4 + k] = s1[q][k];
+      }
+    }
+    __syncthreads();
+    if (tid < C) {
+      const int cv2 = tid >> 3, k = tid & 7;
+      float a = 0.f, b = 0.f;
+      for (int l = 0; l < RL; ++l) {
+        a += red[(l * CV + cv2) * 16 + k];
+        b += red[(l * CV + cv2) * 16 + 8 + k];
+      }
+      const size_t o = ((size_t)(g * T + t) * 2) * C + tid;
+      partial[o] = a;
+      partial[o + C] = b;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int mmdyn_colstats_tiles(int rows_per_group) { return ceil_div(rows_per_group, tile_rows_for(rows_per_group)); }
@@ -640,5 +741,29 @@ extern "C" int mmdyn_bn_swish_bwd_apply_planes(const float* da, const float* y, 
   const int64_t total8 = (int64_t)G * rows_per_group * (C / 8);
   hipLaunchKernelGGL(bn_swish_bwd_apply_planes_kernel, dim3(ew_grid(total8)), dim3(256), 0, (hipStream_t)stream, da, y, bp, sums, dy,
                      reinterpret_cast<bf16_t*>(dy_planes), total8, rows_per_group, C, da_is_du);
+  MMDYN_LAUNCH_CHECK();
+}
+
+/* Eval-mode nn.BatchNorm2d + Swish backward in one pass (mean / rstd from mmdyn_bn_eval_stats): see the header. */
+extern "C" int mmdyn_bn_eval_swish_bwd(const float* da, const float* y, const float* mean, const float* rstd, const float* gamma,
+                                       const float* beta, float* dy, void* dy_planes, float* partial, int G, int rows_per_group,
+                                       int C, int da_is_du, void* stream) {
+  const bool need_y = !da_is_du || partial;
+  if (!da || !mean || !rstd || !gamma || !beta || (!dy && !dy_planes) || (need_y && !y)) return MMDYN_ERR_NULL;
+  if (!bn_shape_ok(G, rows_per_group, C)) return MMDYN_ERR_SHAPE;
+  const int TR = tile_rows_for(rows_per_group), T = ceil_div(rows_per_group, TR);
+  BnParams bp{mean, rstd, gamma, beta};
+  bf16_t* dyp = reinterpret_cast<bf16_t*>(dy_planes);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(T, G), block(256);
+  if (partial)
+    hipLaunchKernelGGL((bn_eval_swish_bwd_kernel<true, true>), grid, block, 0, st, da, y, bp, dy, dyp, partial, rows_per_group, C, T,
+                       TR, da_is_du);
+  else if (need_y)
+    hipLaunchKernelGGL((bn_eval_swish_bwd_kernel<true, false>), grid, block, 0, st, da, y, bp, dy, dyp, partial, rows_per_group, C, T,
+                       TR, da_is_du);
+  else
+    hipLaunchKernelGGL((bn_eval_swish_bwd_kernel<false, false>), grid, block, 0, st, da, y, bp, dy, dyp, partial, rows_per_group, C,
+                       T, TR, da_is_du);
   MMDYN_LAUNCH_CHECK();
 }

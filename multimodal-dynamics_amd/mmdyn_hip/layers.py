@@ -347,9 +347,31 @@ def _apply_out(y, planes_out):
     return torch.empty_like(y), None
 
 
-def bn_swish_backward(da, y, mean, rstd, bn, dgamma, dbeta, G, rows_per_group, C, planes_out=False):
-    """Returns dL/dy -- as an ops.Planes (and only so) with ``planes_out``: the GEMMs that consume it take plane operands."""
+def _eval_mode_check():
+    if SYNC is not None:
+        raise RuntimeError("mmdyn_hip: the eval-mode backward normalises with the local running estimates; it does not run under "
+                           "a synchronised BatchNorm (layers.SYNC must be None)")
+
+
+def _bn_eval_param_grads(y, partial, T, dgamma, dbeta, G, C):
+    """dgamma / dbeta of an eval-mode BatchNorm from the tile sums (sum du, sum du * xhat): the train mode's finalize launch; the
+    [G][2][C] sums it also writes have no reader here (dy = du * gamma * rstd has no batch-mean terms)."""
+    ops.B.bn_bwd_finalize(partial, _new(y, G, 2, C), dgamma, dbeta, _new(y, 32, G, 2, C, dtype=torch.float64), G, T, C, 0.0)
+
+
+def bn_swish_backward(da, y, mean, rstd, bn, dgamma, dbeta, G, rows_per_group, C, planes_out=False, eval_mode=False):
+    """Returns dL/dy -- as an ops.Planes (and only so) with ``planes_out``: the GEMMs that consume it take plane operands.
+    ``eval_mode`` (mean / rstd are the running estimates): one bn_eval_swish_bwd launch writes dL/dy and -- when ``dgamma`` or
+    ``dbeta`` is wanted (not None) -- the tile sums, which bn_bwd_finalize turns into the two parameter gradients."""
     T = ops.B.colstats_tiles(rows_per_group)
+    if eval_mode:
+        _eval_mode_check()
+        partial = _new(y, G, T, 2, C) if (dgamma is not None or dbeta is not None) else None
+        dy, dyp = _apply_out(y, planes_out)
+        ops.backend_op("bn_eval_swish_bwd")(da, y, mean, rstd, bn.gamma, bn.beta, dy, partial, G, rows_per_group, C, False, planes=dyp)
+        if partial is not None:
+            _bn_eval_param_grads(y, partial, T, dgamma, dbeta, G, C)
+        return dy if dyp is None else dyp
     partial = _new(y, G, T, 2, C)
     ops.B.bn_swish_bwd_reduce(da, y, mean, rstd, bn.gamma, bn.beta, partial, G, rows_per_group, C)
     sums = _bn_backward_sums(y, partial, T, dgamma, dbeta, G, C)
@@ -361,12 +383,17 @@ def bn_swish_backward(da, y, mean, rstd, bn, dgamma, dbeta, G, rows_per_group, C
     return dy
 
 
-def dgrad_bn_swish_backward(x, Wp, mode, G, Bg, Hi, Cin, Ho, N, stride, offset, y, mean, rstd, bn, dgamma, dbeta, planes_out=False):
+def dgrad_bn_swish_backward(x, Wp, mode, G, Bg, Hi, Cin, Ho, N, stride, offset, y, mean, rstd, bn, dgamma, dbeta, planes_out=False,
+                            eval_mode=False):
     """Input-gradient GEMM of the layer ABOVE fused with this layer's BatchNorm+Swish backward: the GEMM epilogue
     turns dL/da into du = dL/da * swish'(.) and emits the per-tile sums, so only finalize + apply remain.
     Returns dL/dy (gradient w.r.t. this layer's conv output) -- as an ops.Planes (and only so) with ``planes_out``: the apply pass
-    writes the operand of the plane launches that consume it already split."""
+    writes the operand of the plane launches that consume it already split.
+    ``eval_mode``: the GEMM is the same launch (it writes du and its tile sums); the sums go to bn_bwd_finalize only when
+    ``dgamma`` or ``dbeta`` is wanted, and dL/dy = du * gamma * rstd is one bn_eval_swish_bwd launch that reads du alone."""
     rows_per_group = Bg * Ho * Ho
+    if eval_mode:
+        _eval_mode_check()
     if y.dtype == torch.float32 and mode != IM2COL3:
         x, Wp = split_operands(x, Wp, mode, G, Bg, Hi, Cin, Ho, N)
     if isinstance(x, ops.Planes):
@@ -377,6 +404,12 @@ def dgrad_bn_swish_backward(x, Wp, mode, G, Bg, Hi, Cin, Ho, N, stride, offset, 
     partial = _new(y, G, T, 2, N)
     ops.B.igemm_nt_dgrad_bn(x, Wp, du, partial, y, mean, rstd, bn.gamma, bn.beta, mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N,
                             stride, offset)
+    if eval_mode:
+        if dgamma is not None or dbeta is not None:
+            _bn_eval_param_grads(y, partial, T, dgamma, dbeta, G, N)
+        dy, dyp = _apply_out(y, planes_out)
+        ops.backend_op("bn_eval_swish_bwd")(du, None, mean, rstd, bn.gamma, bn.beta, dy, None, G, rows_per_group, N, True, planes=dyp)
+        return dy if dyp is None else dyp
     sums = _bn_backward_sums(y, partial, T, dgamma, dbeta, G, N)
     dy, dyp = _apply_out(y, planes_out)
     if dyp is not None:
@@ -817,7 +850,7 @@ def encoder_trunk_forward_steps(P, buf, x, G=1, repeat=1, packed=None, training=
     if tuple(x.shape[1:]) != (3, S, S):
         raise ValueError(f"mmdyn_hip: this encoder takes [B,3,{S},{S}] images, got {tuple(x.shape)}")
     pk = packed if packed is not None else pack_now(encoder_pack_specs(P))
-    c = {"Bt": Bt, "G": G, "Bg": Bg, "pk": pk, "S": S}
+    c = {"Bt": Bt, "G": G, "Bg": Bg, "pk": pk, "S": S, "training": bool(training)}
     H = S // 2
     W1p = pk["W1p"]                                                          # [32][64], cols 48.. zero
     u1, a1 = _act(x, Bt * H * H, 32), _act(x, Bt * H * H, 32)
@@ -856,37 +889,55 @@ def encoder_trunk_backward(*a, **k):
     return run(encoder_trunk_backward_steps(*a, **k))
 
 
-def encoder_trunk_backward_steps(P, c, dh, grads, dh_is_du=False, dh_planes=None):
+def _wanted(need):
+    """need: the set of parameter keys whose gradient the caller wants (None: all)."""
+    return (lambda k: True) if need is None else (lambda k: k in need)
+
+
+def encoder_trunk_backward_steps(P, c, dh, grads, dh_is_du=False, dh_planes=None, need=None, need_dx=False):
     """dh: [Bt,512]; writes every weight gradient of the trunk into ``grads[key]`` (canonical layout).
+    A ctx of an eval-mode forward (``training=False``: c["training"]) takes the eval-mode BatchNorm backward.
+    ``need``: the parameter keys whose gradient is wanted (default: all) -- a weight-gradient, column-sum or finalize launch whose
+    outputs are all outside it is not issued, and ``grads`` need not hold those keys.
+    ``need_dx``: also return dL/dx [Bt,3,S,S], the gradient w.r.t. the input image (else None): Conv2d(3,32,4,2,1)'s input gradient
+    is the transposed convolution with the same canonical [32][3][4][4] weight -- the decoder's last layer, its direct kernel.
     ``dh_is_du``: the caller has already taken dh through the FC layer's Swish (c["u5"]), e.g. in its dropout backward.
     ``dh_planes`` (with dh_is_du): the same tensor as an ops.Planes -- the FC layer's input gradient then runs on the plane-ring
     kernel where it serves the launch."""
     Bt, G, Bg, pk, S, st = c["Bt"], c["G"], c["Bg"], c["pk"], c["S"], c["stages"]
     n = len(st)
+    want, ev = _wanted(need), not c.get("training", True)
     du5 = act_backward(dh, c["u5"], ACT_SWISH) if not dh_is_du else dh
-    wgrad(du5, st[-1]["a"], grads["fc_net.0.weight"], DENSE, Bt, 1, 512, 1, FEAT, perm=1)
-    ops.B.colsum(du5, grads["fc_net.0.bias"], Bt, 512, 0, 0.0)
+    if want("fc_net.0.weight"):
+        wgrad(du5, st[-1]["a"], grads["fc_net.0.weight"], DENSE, Bt, 1, 512, 1, FEAT, perm=1)
+    if want("fc_net.0.bias"):
+        ops.B.colsum(du5, grads["fc_net.0.bias"], Bt, 512, 0, 0.0)
     da, _ = dense(du5, pk["WfT"], None, Bt, 512, FEAT, out_dtype=ACT_DTYPE,  # WfT: [hw*256+c][512]
                   A_planes=dh_planes if dh_is_du else None)
     yield
 
     def bn_keys(t):
-        return grads[f"conv_net.{t['i'] + 1}.weight"], grads[f"conv_net.{t['i'] + 1}.bias"]
+        kw, kb = f"conv_net.{t['i'] + 1}.weight", f"conv_net.{t['i'] + 1}.bias"
+        return grads[kw] if want(kw) else None, grads[kb] if want(kb) else None
+
+    def conv_wgrad(dy, t, stride, offset):
+        if want(f"conv_net.{t['i']}.weight"):
+            wgrad(dy, t["a_in"], grads[f"conv_net.{t['i']}.weight"], CONV, Bt, t["Ho"], t["cout"], t["Hi"], t["cin"], stride, offset)
 
     # the k4 s1 p0 stage (8 -> 5): its input gradient is the tap-skipping transposed convolution
     # (fp32x3: a dL/dy whose input-gradient launch takes plane operands is written by its apply pass ONLY as ops.Planes; the weight
     #  gradient takes it so as well)
     t = st[n - 1]
     dy = bn_swish_backward(da, t["y"], t["m"], t["r"], t["bn"], *bn_keys(t), G, Bg * t["Ho"] ** 2, t["cout"],
-                           planes_out=planes_served(TCONV_S1P0, 1, Bt, 5, t["cout"], 8, t["cin"]))
-    wgrad(dy, t["a_in"], grads[f"conv_net.{t['i']}.weight"], CONV, Bt, t["Ho"], t["cout"], t["Hi"], t["cin"], 1, 0)
+                           planes_out=planes_served(TCONV_S1P0, 1, Bt, 5, t["cout"], 8, t["cin"]), eval_mode=ev)
+    conv_wgrad(dy, t, 1, 0)
     da = tconv_s1p0(dy, pk[f"W{n + 1}s"], 1, Bt, t["cout"], t["cin"])[0]     # W{n+1}s: [16][Cin][Cout]
     yield
     t = st[n - 2]
     dy = bn_swish_backward(da, t["y"], t["m"], t["r"], t["bn"], *bn_keys(t), G, Bg * t["Ho"] ** 2, t["cout"],
                            planes_out=planes_served(TCONV_S2P1, G if n >= 3 else 1, Bg if n >= 3 else Bt, t["Ho"], t["cout"], t["Hi"],
-                                                    t["cin"]))
-    wgrad(dy, t["a_in"], grads[f"conv_net.{t['i']}.weight"], CONV, Bt, t["Ho"], t["cout"], t["Hi"], t["cin"], 2, -1)
+                                                    t["cin"]), eval_mode=ev)
+    conv_wgrad(dy, t, 2, -1)
     yield
     for k in range(n - 3, -1, -1):
         # input gradient of stage k+1 with stage k's BatchNorm+Swish backward in its epilogue
@@ -894,14 +945,20 @@ def encoder_trunk_backward_steps(P, c, dh, grads, dh_is_du=False, dh_planes=None
         dy = dgrad_bn_swish_backward(dy, pk[f"W{k + 3}s"], TCONV_S2P1, G, Bg, up["Ho"], up["cout"], up["Hi"], up["cin"], 1, 0,
                                      t["y"], t["m"], t["r"], t["bn"], *bn_keys(t),
                                      planes_out=planes_served(TCONV_S2P1, G if k > 0 else 1, Bg if k > 0 else Bt, t["Ho"], t["cout"],
-                                                              t["Hi"], t["cin"]))
-        wgrad(dy, t["a_in"], grads[f"conv_net.{t['i']}.weight"], CONV, Bt, t["Ho"], t["cout"], t["Hi"], t["cin"], 2, -1)
+                                                              t["Hi"], t["cin"]), eval_mode=ev)
+        conv_wgrad(dy, t, 2, -1)
         if k > 0:
             yield
     t = st[0]
     du1 = dgrad_act(dy, pk["W2s"], TCONV_S2P1, 1, Bt, t["Ho"], t["cout"], t["Hi"], t["cin"], c["u1"], ACT_SWISH)
     yield
-    wgrad(du1, c["x"], grads["conv_net.0.weight"], IM2COL3, Bt, S // 2, 32, S, 64, cg_canon=48)
+    if want("conv_net.0.weight"):
+        wgrad(du1, c["x"], grads["conv_net.0.weight"], IM2COL3, Bt, S // 2, 32, S, 64, cg_canon=48)
+    if not need_dx:
+        return None
+    dx = _new(c["x"], Bt, 3, S, S)
+    ops.B.tconv_out3_fwd(du1, P["conv_net.0.weight"], dx, Bt, S // 2, S // 2)      # du1: [Bt * (S/2)^2][32] channels-last
+    return dx
 
 
 # ------------------------------------------------------------------------------------------------
@@ -930,7 +987,8 @@ def decoder_forward_steps(P, buf, z, G=1, repeat=1, logits=True, packed=None, co
     L = _pad32(Lc)
     if cond is not None or L != L0:
         z = concat_condition(z, cond, L, Lc - L0)          # [z | c | 0]  (vae.py:286-291)
-    c = {"Bt": Bt, "G": G, "Bg": Bg, "L": L, "L0": L0, "Lc": Lc, "z": z, "pk": pk, "S": S, "last": last}
+    c = {"Bt": Bt, "G": G, "Bg": Bg, "L": L, "L0": L0, "Lc": Lc, "z": z, "pk": pk, "S": S, "last": last,
+         "training": bool(training)}
     # rows -> hw*256+c.  bf16 storage mode: the activated output is the first transposed convolution's operand and is stored
     # as such (the matrix cores round it to bf16 either way); the pre-activation stays fp32 for the backward
     c0 = P[f"hallucinate.{convs[0]}.weight"].shape[0]
@@ -1011,17 +1069,22 @@ def decoder_backward(*a, **k):
     return run(decoder_backward_steps(*a, **k))
 
 
-def decoder_backward_steps(P, c, dlogits, grads, need_dz=True, defer=None):
-    """dlogits: NCHW [Bt,3,S,S] -> dz [Bt, L]; weight gradients into ``grads`` (``defer``: queued, see wgrad)."""
+def decoder_backward_steps(P, c, dlogits, grads, need_dz=True, defer=None, need=None):
+    """dlogits: NCHW [Bt,3,S,S] -> dz [Bt, L]; weight gradients into ``grads`` (``defer``: queued, see wgrad).
+    Eval-mode ctx (c["training"] False) and ``need``: as in :func:`encoder_trunk_backward_steps`."""
     Bt, G, Bg, L, pk, S, st = c["Bt"], c["G"], c["Bg"], c["L"], c["pk"], c["S"], c["stages"]
     n = len(st)
+    want, ev = _wanted(need), not c.get("training", True)
 
     def bn_keys(t):
-        return grads[f"hallucinate.{t['i'] + 1}.weight"], grads[f"hallucinate.{t['i'] + 1}.bias"]
+        kw, kb = f"hallucinate.{t['i'] + 1}.weight", f"hallucinate.{t['i'] + 1}.bias"
+        return grads[kw] if want(kw) else None, grads[kb] if want(kb) else None
 
     # last layer backward: both GEMMs gather the k4 s2 p1 window of the NCHW logit gradient on the fly
     t = st[n - 1]
-    if t["a"] is None:            # (the activated tensor of the last BatchNorm was never stored: recomputed on the fetch)
+    if not want(f"hallucinate.{c['last']}.weight"):
+        pass
+    elif t["a"] is None:          # (the activated tensor of the last BatchNorm was never stored: recomputed on the fetch)
         wgrad_out3_bn(t["y"], t["m"], t["r"], t["bn"], dlogits, grads[f"hallucinate.{c['last']}.weight"], G, Bg, S // 2, defer=defer)
     else:
         wgrad(t["a"], dlogits, grads[f"hallucinate.{c['last']}.weight"], IM2COL3, Bt, S // 2, 32, S, 64, cg_canon=48, defer=defer)
@@ -1034,22 +1097,27 @@ def decoder_backward_steps(P, c, dlogits, grads, need_dz=True, defer=None):
         return planes_served(CONV, 1, Bt, 8, st[0]["cout"], 5, st[0]["cin"])
 
     dy = dgrad_bn_swish_backward(dlogits, pk[f"W{n + 1}p"], IM2COL3, G, Bg, S, 64, S // 2, 32, 1, 0, t["y"], t["m"], t["r"],
-                                 t["bn"], *bn_keys(t), planes_out=next_takes_planes(n - 1))
+                                 t["bn"], *bn_keys(t), planes_out=next_takes_planes(n - 1), eval_mode=ev)
     yield
     for k in range(n - 1, 0, -1):
         up, t = st[k], st[k - 1]
-        wgrad(up["a_in"], dy, grads[f"hallucinate.{up['i']}.weight"], CONV, Bt, up["Hi"], up["cin"], up["Ho"], up["cout"], 2, -1,
-              defer=defer)
+        if want(f"hallucinate.{up['i']}.weight"):
+            wgrad(up["a_in"], dy, grads[f"hallucinate.{up['i']}.weight"], CONV, Bt, up["Hi"], up["cin"], up["Ho"], up["cout"], 2, -1,
+                  defer=defer)
         dy = dgrad_bn_swish_backward(dy, pk[f"W{k + 1}k"], CONV, G, Bg, up["Ho"], up["cout"], up["Hi"], up["cin"], 2, -1,
-                                     t["y"], t["m"], t["r"], t["bn"], *bn_keys(t), planes_out=next_takes_planes(k - 1))
+                                     t["y"], t["m"], t["r"], t["bn"], *bn_keys(t), planes_out=next_takes_planes(k - 1),
+                                     eval_mode=ev)
         yield
     t = st[0]
-    wgrad(t["a_in"], dy, grads[f"hallucinate.{t['i']}.weight"], CONV, Bt, 5, t["cin"], 8, t["cout"], 1, 0, defer=defer)
+    if want(f"hallucinate.{t['i']}.weight"):
+        wgrad(t["a_in"], dy, grads[f"hallucinate.{t['i']}.weight"], CONV, Bt, 5, t["cin"], 8, t["cout"], 1, 0, defer=defer)
     # input gradient of the k4 s1 p0 layer with the FC layer's Swish backward in its epilogue (FC level: fp32)
     du0 = dgrad_act(dy, pk["W1k"], CONV, 1, Bt, 8, t["cout"], 5, t["cin"], c["u0"], ACT_SWISH, 1, 0)
     yield
-    wgrad(du0, c["z"], grads["upsample.0.weight"], DENSE, Bt, 1, FEAT, 1, L, cg_canon=c["Lc"], perm=2, defer=defer)
-    ops.B.colsum(du0, grads["upsample.0.bias"], Bt, FEAT, 2, 0.0)
+    if want("upsample.0.weight"):
+        wgrad(du0, c["z"], grads["upsample.0.weight"], DENSE, Bt, 1, FEAT, 1, L, cg_canon=c["Lc"], perm=2, defer=defer)
+    if want("upsample.0.bias"):
+        ops.B.colsum(du0, grads["upsample.0.bias"], Bt, FEAT, 2, 0.0)
     if not need_dz:
         return None
     dz, _ = dense(du0, pk["WuT"], None, Bt, FEAT, L)                         # WuT: [L][hw*256+c]

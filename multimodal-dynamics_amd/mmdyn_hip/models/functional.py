@@ -22,23 +22,35 @@ def _dict(keys, tensors):
     return {k: t for k, t in zip(keys, tensors)}
 
 
+def _needed(ctx, first):
+    """Eval-mode backward: the keys whose parameter requires grad (the schedules skip every launch that serves the others).
+    Train mode: None -- every gradient, exactly the launches of the train-mode schedule."""
+    if ctx.c.get("training", True):
+        return None
+    return {k for k, f in zip(ctx.keys, ctx.needs_input_grad[first:]) if f}
+
+
 class ImageEncoderTrunkFn(torch.autograd.Function):
-    """conv_net + fc_net (before dropout).  ``holder`` carries the BatchNorm buffers."""
+    """conv_net + fc_net (before dropout).  ``holder`` carries the BatchNorm buffers; ``holder.training`` False (a module in
+    ``eval()`` with differentiable eval switched on, models/vae.py ``eval_grad``): BatchNorm on the running estimates, forward and
+    backward.  The gradient w.r.t. the image is produced when the image requires grad, in both modes."""
 
     @staticmethod
     def forward(ctx, x, holder, *params):
         keys = holder.param_keys()
         P = _dict(keys, [p.detach() for p in params])
-        h, c = layers.encoder_trunk_forward(P, holder.bn_buffers(), x.detach().contiguous(), G=1)
+        h, c = layers.encoder_trunk_forward(P, holder.bn_buffers(), x.detach().contiguous(), G=1,
+                                            training=bool(getattr(holder, "training", True)))
         ctx.P, ctx.c, ctx.keys = P, c, keys
         return h
 
     @staticmethod
     def backward(ctx, dh):
-        grads = {k: torch.empty_like(ctx.P[k]) for k in ctx.keys}
-        layers.encoder_trunk_backward(ctx.P, ctx.c, dh.contiguous(), grads)
+        need = _needed(ctx, 2)
+        grads = {k: torch.empty_like(ctx.P[k]) for k in ctx.keys if need is None or k in need}
+        dx = layers.encoder_trunk_backward(ctx.P, ctx.c, dh.contiguous(), grads, need=need, need_dx=ctx.needs_input_grad[0])
         ctx.c = None
-        return (None, None) + tuple(grads[k] for k in ctx.keys)
+        return (dx, None) + tuple(grads.get(k) for k in ctx.keys)
 
 
 class ImageDecoderFn(torch.autograd.Function):
@@ -46,16 +58,18 @@ class ImageDecoderFn(torch.autograd.Function):
     def forward(ctx, z, holder, *params):
         keys = holder.param_keys()
         P = _dict(keys, [p.detach() for p in params])
-        out, c = layers.decoder_forward(P, holder.bn_buffers(), z.detach().contiguous(), G=1, cond=holder._cond)
+        out, c = layers.decoder_forward(P, holder.bn_buffers(), z.detach().contiguous(), G=1, cond=holder._cond,
+                                        training=bool(getattr(holder, "training", True)))
         ctx.P, ctx.c, ctx.keys = P, c, keys
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        grads = {k: torch.empty_like(ctx.P[k]) for k in ctx.keys}
-        dz = layers.decoder_backward(ctx.P, ctx.c, dout.contiguous(), grads, need_dz=ctx.needs_input_grad[0])
+        need = _needed(ctx, 2)
+        grads = {k: torch.empty_like(ctx.P[k]) for k in ctx.keys if need is None or k in need}
+        dz = layers.decoder_backward(ctx.P, ctx.c, dout.contiguous(), grads, need_dz=ctx.needs_input_grad[0], need=need)
         ctx.c = None
-        return (dz, None) + tuple(grads[k] for k in ctx.keys)
+        return (dz, None) + tuple(grads.get(k) for k in ctx.keys)
 
 
 class HeadsFn(torch.autograd.Function):

@@ -220,6 +220,33 @@ class Autoencoder(nn.Module):
     def inference(self, n=1):
         raise NotImplementedError
 
+    def eval_grad(self, mode=True):
+        """Differentiable ``eval()`` for every Encoder / Decoder below this module (see :func:`set_eval_grad`).  Returns self."""
+        return set_eval_grad(self, mode)
+
+
+def set_eval_grad(module, mode=True):
+    """Opt in to (or out of) autograd through ``eval()``-mode cnn Encoders / Decoders under ``module``.  By default an eval-mode
+    forward is graph-free (its outputs never require grad).  With the flag set, a module in ``eval()`` called with grad mode enabled
+    records a graph: the forward issues the same launches (bit-identical outputs, BatchNorm on the running estimates, buffers
+    untouched, dropout the identity), the backward differentiates through the frozen BatchNorm and produces gradients for the
+    inputs and for the parameters that require grad only.  Under ``torch.no_grad()``, in ``train()`` mode, or with the flag unset,
+    every call is what it was.  Returns ``module``."""
+    for m in module.modules():
+        if isinstance(m, (Encoder, Decoder)):
+            m._eval_grad = bool(mode)
+    return module
+
+
+def _eval_grad_active(module):
+    """True when an eval-mode call of this Encoder / Decoder goes through autograd."""
+    if module.training or not module._eval_grad or not torch.is_grad_enabled():
+        return False
+    if layers.ACT_DTYPE != torch.float32:
+        raise NotImplementedError("mmdyn_hip: the eval-mode backward (bn_eval_swish_bwd) is fp32 only; it does not run in the 16-bit "
+                                  f"activation-storage modes (layers.ACT_DTYPE = {layers.ACT_DTYPE})")
+    return True
+
 
 def _check_supported(architecture, conditional, categorical_conditions=False):
     """Real-valued and categorical (one-hot, vae.py:337-344) conditions are both built; the one refusal left is the conditional
@@ -319,6 +346,10 @@ class Encoder(nn.Module):
             self.linear_means = LinearParams(layer_sizes[-1], latent_size)
             self.linear_log_var = LinearParams(layer_sizes[-1], latent_size)
         self.noise = None
+        self._eval_grad = False
+
+    def eval_grad(self, mode=True):
+        return set_eval_grad(self, mode)
 
     def bn_buffers(self):
         return {f"conv_net.{i}.{n}": getattr(self.conv_net[i], n) for i in range(3, 3 * (4 + self.extra), 3)
@@ -329,10 +360,10 @@ class Encoder(nn.Module):
 
     def trunk(self, x):
         """Everything before the dropout: [B,512] features.  ``model.eval()``: BatchNorm uses the running estimates
-        (forward only: the result carries no autograd graph)."""
+        (forward only: the result carries no autograd graph, unless ``eval_grad()`` has switched the differentiable form on)."""
         if self.architecture == 'cnn':
             sd = dict(self.named_parameters())
-            if not self.training:
+            if not self.training and not _eval_grad_active(self):
                 with torch.no_grad():
                     P = {k: sd[k].detach() for k in self.param_keys()}
                     return layers.run(layers.encoder_trunk_forward_steps(P, self.bn_buffers(), x.detach().contiguous(),
@@ -377,6 +408,7 @@ class Decoder(nn.Module):
         _check_supported(architecture, conditional, categorical_conditions)
         cond_w = (condition_dim or 0) if conditional else 0
         self._cond = None
+        self._eval_grad = False
         if architecture == 'cnn':
             if latent_size % 32:
                 raise NotImplementedError("mmdyn_hip: latent_size must be a multiple of 32 (MFMA K-step)")
@@ -392,6 +424,9 @@ class Decoder(nn.Module):
         else:
             layer_sizes = [latent_size + cond_w] + layer_sizes + [output_dim]
             self.deconv_net = mlp(layer_sizes)
+
+    def eval_grad(self, mode=True):
+        return set_eval_grad(self, mode)
 
     def bn_buffers(self):
         return {f"hallucinate.{i}.{n}": getattr(self.hallucinate[i], n) for i in range(1, 3 * (3 + self.extra), 3)
@@ -409,7 +444,8 @@ class Decoder(nn.Module):
     def _forward(self, z, c):
         sd = dict(self.named_parameters())
         cat = self.categorical_conditions
-        if self.architecture == 'cnn' and not self.training:   # eval: running-estimate BatchNorm, forward only
+        # eval: running-estimate BatchNorm, forward only (eval_grad(): through ImageDecoderFn below, which reads self.training)
+        if self.architecture == 'cnn' and not self.training and not _eval_grad_active(self):
             with torch.no_grad():
                 P = {k: sd[k].detach() for k in self.param_keys()}
                 return layers.run(layers.decoder_forward_steps(P, self.bn_buffers(), z.detach().contiguous(),

@@ -663,6 +663,24 @@ class HipBackend:
         check(self.lib.mmdyn_bn_swish_bwd_apply(pd, py, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(sums), po, G,
                                                 rows_per_group, C, int(da_is_du), _stream()), "mmdyn_bn_swish_bwd_apply")
 
+    def bn_eval_swish_bwd(self, da, y, mean, rstd, gamma, beta, dy, partial, G, rows_per_group, C, da_is_du=False, planes=None):
+        """Backward of eval-mode BatchNorm + Swish in one pass: dy = du * gamma * rstd -> ``dy`` (fp32) and / or ``planes`` (a
+        Planes); ``partial`` (nullable) [G][colstats_tiles][2][C]: the tile sums bn_bwd_finalize turns into dgamma / dbeta.  With
+        ``da_is_du`` and no ``partial``, ``y`` is not read and may be None.  fp32 only."""
+        if planes is not None and (planes.rows != G * rows_per_group or planes.C != C):
+            raise ValueError("mmdyn_hip: bn_eval_swish_bwd: plane tensor of the wrong shape")
+        n = G * rows_per_group * C
+        for t in (da, y, dy):
+            if t is not None and t.numel() != n:
+                raise ValueError("mmdyn_hip: bn_eval_swish_bwd: da / y / dy must hold G * rows_per_group * C elements")
+        if partial is not None and partial.numel() != G * self.colstats_tiles(rows_per_group) * 2 * C:
+            raise ValueError("mmdyn_hip: bn_eval_swish_bwd: partial must be [G][colstats_tiles(rows_per_group)][2][C]")
+        if mean.numel() != G * C or rstd.numel() != G * C or gamma.numel() != C or beta.numel() != C:
+            raise ValueError("mmdyn_hip: bn_eval_swish_bwd: mean / rstd are [G][C], gamma / beta [C]")
+        check(self.lib.mmdyn_bn_eval_swish_bwd(_ptr(da), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(dy),
+                                               None if planes is None else planes.t.data_ptr(), _ptr(partial), G, rows_per_group, C,
+                                               int(da_is_du), _stream()), "mmdyn_bn_eval_swish_bwd")
+
     # ---- element-wise ----
     def act_fwd(self, u, h, act):
         check(self.lib.mmdyn_act_fwd(_ptr(u), _ptr(h), u.numel(), act, _stream()), "mmdyn_act_fwd")
