@@ -16,6 +16,36 @@
  *     (sample, y, x); the reference's NCHW tensors appear only at the image input / logits output;
  *   - "groups": a batch of G*Bg samples made of G independent sub-batches (one per modality-subset
  *     pass of _evaluate_mvae, problems.py:473-546); train-mode BatchNorm statistics are per group.
+ *
+ * Buffer roles -- what a non-const pointer may hold when a launch starts (callers hand over torch.empty memory: the previous
+ * step's activations, gradients, NaNs).  Every writable pointer is one of
+ *   OUTPUT       every element of the declared extent is written, none is read first; prior contents (NaN / Inf included) never
+ *                reach a result.  This is the default: a writable pointer without another word below is an output.  In particular
+ *                  - C / C_act of the GEMMs: all rows x N columns (with ldc > N the columns N..ldc of a row are LEFT UNTOUCHED);
+ *                  - stats [G][T][2][N] and the `partial` tables of mmdyn_colstats / mmdyn_bn_swish_bwd_reduce /
+ *                    mmdyn_bn_eval_swish_bwd: all T tiles, a tile without rows as zeros (consumers sum over T);
+ *                  - partial [chunks][taps][Cd][Cg] of the weight gradients: every chunk, a chunk that starts past the last row
+ *                    as zeros (rows_per_chunk is rounded up to the 32-row K-step, so late chunks can be empty);
+ *                  - ws [splitk][rows][N] of a split-K launch: every slice;
+ *                  - the third plane of a plane tensor; the dmu / dlv rows of the experts PRESENT in a pass (mmdyn_poe_bwd; the
+ *                    rows of an expert whose pointers are null in the pass are not touched, mmdyn_poe_bwd_avail writes zeros for
+ *                    an absent (row, expert) pair); dlogit of a discarded pass (slot < 0): written as zeros;
+ *                  - `out += beta * out` forms (mmdyn_wgrad_reduce canon, mmdyn_colsum out, mmdyn_linear_small_bwd dW / db,
+ *                    dgamma / dbeta with beta_acc): with beta == 0 the destination is an OUTPUT and is not read (0 * NaN must not
+ *                    survive); with beta != 0 it is an accumulator.
+ *   SCRATCH      written before it is read inside the launch (or the launch pair), contents irrelevant before and after: the fp64
+ *                `scratch` of the BatchNorm finalizers, the `scratch` of mmdyn_colsum, the slab workspace `ws` of a launch that
+ *                is not split over K.
+ *   ACCUMULATOR  read-modify-write, the CALLER initialises: the fp64 loss / KL sums and row tables (loss_sum, loss_slots,
+ *                unmasked_slots, kl_sum, rows_out, ...: atomicAdd in arrival order, so equal to rounding, not bit for bit, between
+ *                runs), running_mean / running_var / num_batches_tracked, optimiser parameters, moments and state, counters.
+ *   STATE        tickets and arrival flags: zero when the launch starts, left zero.
+ *   LEFT UNTOUCHED  elements outside the block a launch addresses: the columns cols_out..ld_out of mmdyn_repack2d_ld (inside the
+ *                block the padding rows_in..rows_out / cols_in..cols_out IS written, as zeros), rows of another group behind an
+ *                offset pointer, canon has exactly Cd * cg_canon * taps elements (the gathered columns cg_canon..Cg are dropped, not
+ *                written anywhere).
+ * tests/test_dirty_memory_gpu.py holds the kernels to this: the same launch on zero-, NaN- and junk-filled destinations gives the
+ * same bits.
  */
 #ifndef MMDYN_HIP_H
 #define MMDYN_HIP_H
@@ -83,6 +113,8 @@ int mmdyn_abi_version(void);
  *            fix-up launch stay.  NULL: slabs + the fix-up launch in either build.
  * Requirements: Cin % 32 == 0, N % 32 == 0.  v_mfma_f32_32x32x2_f32, fp32 in / fp32 accumulate. */
 #define MMDYN_IGEMM_FLAG_WORDS 8192
+/* Buffers: C / C_act and stats are OUTPUTS (every row x N column; every one of the T tiles, a tile without rows as zeros); ws is an
+ * OUTPUT with splitk > 1 (every slice) and SCRATCH otherwise; none of them is read before it is written. */
 int mmdyn_igemm_nt(const float* A, const float* Bp, const float* bias, float* C, float* C_act,
                    float* stats, float* ws, int mode, int G, int Bg, int Hi, int Wi, int Cin,
                    int Ho, int Wo, int N, int ldc, int stride, int offset, int act, int splitk,
@@ -147,6 +179,7 @@ int mmdyn_igemm_slab_floats_mx(int mode, int G, int Bg, int Hi, int Wi, int Cin,
  * flags: as mmdyn_igemm_nt_mx (0 = fp32 everywhere).  K % 32 == 0, N % 32 == 0. */
 int mmdyn_igemm_nt_grouped(const void* A, const void* Bp, const float* bias, void* C, void* C_act, const void* u, int G,
                            int rows, int K, int N, int act, int flags, void* stream);
+/* C / C_act: OUTPUTS (ws is read only). */
 int mmdyn_splitk_reduce(const float* ws, const float* bias, float* C, float* C_act, int splitk,
                         int rows, int N, int act, void* stream);
 
@@ -161,6 +194,8 @@ int mmdyn_splitk_reduce(const float* ws, const float* bias, float* C, float* C_a
  *   perm 2: linear with permuted rows,    cd = hw*256+c -> canon[c*25+hw][cg]  (Decoder upsample.0)
  *   cg_canon <= Cg drops zero-padded gathered columns (the 48 -> 64 padded first/last layers).
  * Requirements: Cd % 32 == 0, Cg % 32 == 0. */
+/* partial: OUTPUT, every chunk -- a chunk that starts past the last row (rows_per_chunk is rounded up to the 32-row K-step) is
+ * written as zeros, so the caller need not clear it.  Same for the _bf16 / _f16 / _mx / _grouped / mmdyn_wgrad_out3_bn forms. */
 int mmdyn_wgrad_tn(const float* D, const float* Gt, float* partial, int mode, int Bt, int Hr, int Wr,
                    int Cd, int Hi, int Wi, int Cg, int stride, int offset, int chunks, void* stream);
 /* bf16 matrix cores (v_mfma_f32_32x32x8_bf16), fp32 accumulate; see mmdyn_igemm_nt_bf16 */
@@ -187,6 +222,8 @@ int mmdyn_wgrad_chunks(int mode, int rows, int Cd, int Cg);
 /* ... for the kernel the flags of mmdyn_wgrad_tn_mx select (both operands 16-bit in HBM: the all-16-bit kernels' tiles; bit 7
  * alone: the three-term-split kernels, whose LDS planes let fewer blocks share a CU) */
 int mmdyn_wgrad_chunks_mx(int mode, int rows, int Cd, int Cg, int flags);
+/* canon has exactly Cd * cg_canon * taps elements: OUTPUT with beta == 0 (not read: a stale NaN must not survive 0 * NaN),
+ * ACCUMULATOR with beta != 0.  The gathered columns cg_canon..Cg are dropped, written nowhere. */
 int mmdyn_wgrad_reduce(const float* partial, float* canon, int chunks, int taps, int Cd, int Cg,
                        int cg_canon, int perm, float beta, void* stream);
 
@@ -204,6 +241,8 @@ int mmdyn_repack2d(const float* in, float* out, int rows_in, int cols_in, int ro
                    int mode, void* stream);
 
 /* mmdyn_repack2d writing a rows_out x cols_out block into a wider matrix (row stride ld_out >= cols_out) */
+/* Inside the block the padding rows_in..rows_out / cols_in..cols_out is written (zeros); the columns cols_out..ld_out of each row are
+ * LEFT UNTOUCHED. */
 int mmdyn_repack2d_ld(const float* in, float* out, int rows_in, int cols_in, int rows_out, int cols_out,
                       int ld_out, int mode, void* stream);
 /* the same two packs with a 16-bit destination (RNE; half = 0: bf16, half = 1: IEEE half): in the 16-bit storage modes
@@ -268,11 +307,13 @@ int mmdyn_tconv_out3_bn_bce_rows(const void* y, const float* mean, const float* 
 
 /* ---- train-mode BatchNorm2d + Swish, channels-last, per group (vae.py:201-208, 269-276) ----- */
 /* column sums of y and y*y over row chunks -> partial[G][T][2][C], T = mmdyn_colstats_tiles(rows_per_group) */
+/* partial: OUTPUT, all T tiles (also for mmdyn_bn_swish_bwd_reduce and the partial of mmdyn_bn_eval_swish_bwd). */
 int mmdyn_colstats(const float* y, float* partial, int G, int rows_per_group, int C, void* stream);
 int mmdyn_colstats_tiles(int rows_per_group);
 /* partial -> mean/rstd [G][C]; running stats EMA (momentum 0.1, unbiased var) applied for the groups in
  * order, `repeat` times each (the reference re-runs identical encoder trunks: SURVEY.md 3.2);
  * num_batches_tracked (int64) += G*repeat.  running_* may be null. */
+/* mean / rstd: OUTPUTS; scratch: SCRATCH (written before it is read); running_* / num_batches_tracked: ACCUMULATORS; ticket: STATE. */
 int mmdyn_bn_finalize(const float* partial, float* mean, float* rstd, float* running_mean,
                       float* running_var, int64_t* num_batches_tracked, double* scratch /* [32][G][2][C] */,
                       int G, int T, int C, int rows_per_group, float eps, float momentum, int repeat,
@@ -289,6 +330,7 @@ int mmdyn_bn_swish_fwd(const float* y, const float* mean, const float* rstd, con
 int mmdyn_bn_swish_bwd_reduce(const float* da, const float* y, const float* mean, const float* rstd,
                               const float* gamma, const float* beta, float* partial, int G,
                               int rows_per_group, int C, void* stream);
+/* sums: OUTPUT; dgamma / dbeta: OUTPUTS with beta_acc == 0 (not read), ACCUMULATORS otherwise; scratch: SCRATCH. */
 int mmdyn_bn_bwd_finalize(const float* partial, float* sums, float* dgamma, float* dbeta,
                           double* scratch /* [32][G][2][C] */, int G, int T, int C, float beta_acc,
                           uint32_t* ticket, void* stream);
@@ -335,6 +377,7 @@ int mmdyn_random_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, c
 int mmdyn_counter_add(uint64_t* counter, uint64_t inc, void* stream);
 /* out[c] (+)= sum_r x[r][c]   (bias gradients); deterministic two-stage sum, scratch holds
  * mmdyn_colsum_chunks(rows) * C floats; perm 2 = the upsample-bias permutation hw*256+c -> c*25+hw; C % 4 == 0 */
+/* out: OUTPUT with beta == 0 (not read), ACCUMULATOR otherwise; scratch: SCRATCH. */
 int mmdyn_colsum(const float* x, float* out, float* scratch, int rows, int C, int perm, float beta, uint32_t* ticket,
                  void* stream);
 int mmdyn_colsum_chunks(int rows);
@@ -355,6 +398,7 @@ int mmdyn_sum_blocks(const float* x, float* out, int P, int64_t n, void* stream)
 /* tiny Linear layers of the 7-DoF pose MLP (K or N == 7; vae.py:117-123): y = x W^T + b */
 int mmdyn_linear_small_fwd(const float* x, const float* W, const float* b, float* y, int rows, int K,
                            int N, int act, void* stream);
+/* dx: OUTPUT; dW / db: OUTPUTS with beta == 0 (not read), ACCUMULATORS otherwise. */
 int mmdyn_linear_small_bwd(const float* dy, const float* x, const float* W, float* dx, float* dW,
                            float* db, int rows, int K, int N, float beta, void* stream);
 
@@ -380,10 +424,12 @@ typedef struct {
 /* P passes of [B][L].  with_prior=1 adds the universal N(0,1) expert first (vae.py:139, 321-328).
  * Outputs mu/logvar [P][B][L]; optional z = eps*exp(logvar/2)+mu; optional kl_sum[p] (double)
  * += -0.5*sum(1+lv-mu^2-e^lv).  eps added twice to each variance, as the reference does. */
+/* mu / logvar / z (zdst, zpl): OUTPUTS; kl_sum: ACCUMULATOR (the caller zeroes it). */
 int mmdyn_poe_fwd(const mmdyn_pass_experts* passes, const float* eps_noise, float* mu, float* logvar,
                   float* z, double* kl_sum, int with_prior, int P, int B, int L, void* stream);
 /* upstream gradients: dz [P][B][L] (through z), g_mu / g_lv [P][B][L] (directly on the fused mu/logvar),
  * any may be null; kl_scale = kl_weight / B adds the KL term's gradient. */
+/* dmu / dlv of the experts present in a pass: OUTPUTS (all B rows); an expert whose pointers are null in the pass is not touched. */
 int mmdyn_poe_bwd(const mmdyn_pass_experts* passes, const float* eps_noise, const float* mu,
                   const float* logvar, const float* dz, const float* g_mu, const float* g_lv, float kl_scale,
                   int with_prior, int P, int B, int L, const float* kl_weight_dev, void* stream);
@@ -398,6 +444,7 @@ int mmdyn_reparam_bwd(const float* mu, const float* lv, const float* eps_noise, 
  * (sigmoid(x) - t) * grad_scale.  With `mask` ([B][mask_channels][H][W]; mask_channels = 1: broadcast over the
  * channels, = C: elementwise, the dataset's 3-channel segmentation mask) both logits and targets are multiplied by it
  * first (problems.py:445-447); any other channel count is MMDYN_ERR_SHAPE. */
+/* dlogit: OUTPUT (a discarded pass of the grouped forms: zeros); loss_sum / loss_slots / unmasked_slots: ACCUMULATORS. */
 int mmdyn_bce_logits(const float* logits, const float* target, const float* mask, float* dlogit,
                      double* loss_sum, int64_t n, int chw, int hw, int mask_channels, float grad_scale, void* stream);
 /* The unmasked term for G decoder passes that share one target, in ONE launch: logits / dlogit [G][n], target [n];
