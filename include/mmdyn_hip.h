@@ -83,7 +83,8 @@ const char* mmdyn_version(void);
  * the `ws` argument of mmdyn_igemm_nt_dgrad_act / _dgrad_bn and the slab workspace of large launches: revision 4; round 5 the
  * plane-packed weight kinds of the pack plan: revision 5; round 6 the `zdst` field of mmdyn_pass_experts, the arrival-flag words in
  * front of the slab workspace (mmdyn_igemm_slab_floats*) and new entry points: revision 6; the per-sample
- * ELBO entry points (mmdyn_*_rows*) were added without touching an existing signature or workspace and keep revision 6).  A binding checks mmdyn_abi_version() == MMDYN_ABI_VERSION right after
+ * ELBO entry points (mmdyn_*_rows*) and the importance-weighted bound (mmdyn_iw_*) were added without touching an existing signature or
+ * workspace and keep revision 6).  A binding checks mmdyn_abi_version() == MMDYN_ABI_VERSION right after
  * loading the library (mmdyn_hip/_lib.py does) so that a caller built against an older header fails at load time instead of
  * passing its stream handle where the library now expects a workspace pointer. */
 #define MMDYN_ABI_VERSION 6
@@ -578,6 +579,40 @@ int mmdyn_reparam_bwd_weighted(const float* mu, const float* lv, const float* ep
 int mmdyn_elbo_assemble_weighted(const double* bce_rows, const double* mse_rows, const double* kl_rows, const double* kl_sum,
                                  const float* w, float* loss, float* wpartials, float* out, float* partials, float* w_sum_out, int P,
                                  int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev, int kl_mode, void* stream);
+
+/* ---- importance-weighted K-sample bound (evaluation only; no reference op: the reference scores a sample with one draw and the
+ * analytic KL, problems.py:401-458) -------------------------------------------------------------------------------------------------
+ * L_K(x) = log (1/K) sum_k p(x|z_k) p(z_k) / q(z_k|x), z_k ~ q(z|x) (Burda et al., "Importance Weighted Autoencoders"), per request
+ * row b from K draws of ONE posterior: the ELBO at K = 1, tightening towards log p(x) as K grows.  The two entry points bracket the
+ * decoders (run on K * B rows) and the row kernels above (G = K passes against one target, slots 0..K-1 of [K][B] tables).
+ *
+ * The K draws of every row and the density ratio of each:
+ *   z[k][b][l]  = eps[k][b][l] * exp(lv[b][l] / 2) + mu[b][l]   -- the fp32 expression of mmdyn_poe_fwd / mmdyn_reparam_fwd, in the
+ *                 same order: the same mu, lv, eps give the same bits;
+ *   ratio[k][b] = log q(z_k|x) - log p(z_k) = sum_l 0.5 * (z^2 - eps^2 - lv)   (the 2 pi terms cancel), evaluated in fp64 from the fp32
+ *                 z, eps and lv, so it belongs to the z the decoders read.  E_q[ratio] is the analytic KL of mmdyn_kl_rows.
+ * mu / lv: rows of stride ld >= L (the [B][L] outputs of mmdyn_poe_fwd, or the [B][2L] heads of a VAE); eps: [K][B][L], read;
+ * z: [K][B][L], OUTPUT; ratio: [K][B] double, OUTPUT (written, not accumulated: no zeroing).  One wavefront per (k, b) row, 16-byte
+ * lane accesses when L % 4 == 0, ld % 4 == 0 and the four pointers are 16-byte aligned; the fp64 sum runs in a fixed order without
+ * atomics: the same bits in every run.  K * B * L >= 2^31: MMDYN_ERR_RANGE. */
+int mmdyn_iw_latent(const float* mu, const float* lv, int ld, const float* eps, float* z, double* ratio, int K, int B, int L,
+                    void* stream);
+/* The bound from the row tables:
+ *   log_w[k][b] = -(bce_rows[0][k][b] + bce_rows[1][k][b] + pose_multiplier * mse_rows[k][b]) - kl_weight * ratio[k][b],
+ *   out[b]      = -(logsumexp_k log_w[k][b] - log K)            a loss, the sign of mmdyn_elbo_assemble_rows' out; at K = 1 exactly
+ *                                                               the fp32 rounding of rec_0 + kl_weight * ratio_0,
+ *   ess[b]      = exp(2 lse_k(log_w) - lse_k(2 log_w))          the effective sample size of the weights, in [1, K].
+ * bce_rows: [n_bce][K][B] double, n_bce <= 2 (slot 0 = visual, 1 = tactile), may be null; mse_rows: [K][B] double or null; ratio:
+ * [K][B] double, required.  tavail (may be null): a TARGET-availability table as in mmdyn_elbo_assemble_rows_avail -- bce slot s
+ * belongs to modality s, mse_rows to modality 2; a (row, term) whose target is absent adds nothing to any log_w[k][b] and its K table
+ * entries are overwritten with 0 (so bce_rows / mse_rows are OUTPUTS for those entries and read-only elsewhere).  out: [B] float,
+ * OUTPUT; ess: [B] float, OUTPUT, may be null; log_w: [K][B] double, OUTPUT, may be null.  Max-subtracted log-sum-exp in fp64, one
+ * thread per row b walking k.  A log_w of -inf is a zero weight; a row whose weights are all zero gets out = +inf and ess = NaN; NaN
+ * propagates to out and ess; nothing is inspected on the host.  kl_weight_dev as in mmdyn_elbo_assemble.  n_bce outside [0, 2] or a
+ * misaligned table: MMDYN_ERR_SHAPE. */
+int mmdyn_iw_assemble_rows(double* bce_rows, double* mse_rows, const double* ratio, const uint8_t* tavail, float* out, float* ess,
+                           double* log_w, int n_bce, int K, int B, float pose_multiplier, float kl_weight, const float* kl_weight_dev,
+                           void* stream);
 
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call

@@ -135,6 +135,8 @@ _SIGNATURES = {
     "mmdyn_poe_bwd_weighted": "ppppppp" + "f" + "p" + "iiii" + "pp",
     "mmdyn_reparam_bwd_weighted": "pppp" + "f" + "ppp" + "iii" + "p",
     "mmdyn_elbo_assemble_weighted": "pppppppppp" + "ii" + "ff" + "p" + "i" + "p",
+    "mmdyn_iw_latent": "pp" + "i" + "ppp" + "iii" + "p",
+    "mmdyn_iw_assemble_rows": "ppppppp" + "iii" + "ff" + "pp",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

@@ -18,6 +18,7 @@ summation order (tests/test_engine_*.py).  BatchNorm running statistics: encoder
 4 EMA updates as in the reference; decoder buffers receive the live passes' updates only (the
 reference also folds in the discarded passes) unless ``exact_running_stats=True``.
 """
+import numbers
 import os
 import torch
 
@@ -1459,9 +1460,15 @@ class MVAEInference:
             return self._forward_scoped(visual, tactile, pose, cond, avail, sample)
 
     def _forward_scoped(self, visual, tactile, pose, cond, avail=None, sample=True):
-        LN, L = self.lanes, self.L
         ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
         B = ref.shape[0]
+        heads = self._heads(visual, tactile, pose, cond)
+        mu, lv, z = self._poe(heads, avail, self._draw_latent(B) if sample else self._zero_latent(B), B, ref.device)
+        return self._decode(z, cond) + (mu, lv)
+
+    def _heads(self, visual, tactile, pose, cond):
+        """The fused (means | log_var) head outputs [B][2L] of the modalities given, None for the others."""
+        LN = self.lanes
         heads = [None, None, None]
         LN.fork()
         if visual is not None:
@@ -1474,15 +1481,21 @@ class MVAEInference:
             hp, _ = layers.pose_encoder_trunk_forward(self.P["pe"], pose)
             heads[2] = layers.heads_forward(self.P["pe"], hp, self.pk["ph"])[0]
         LN.join()
-        eps = self._draw_latent(B) if sample else self._zero_latent(B)
-        mu, lv, z = (torch.empty(B, L, device=ref.device) for _ in range(3))
+        return heads
+
+    def _poe(self, heads, avail, eps, B, device):
+        """The product-of-experts launch on the heads: (mu, lv, z), each [B][L]; ``eps`` None: the posterior alone, z is not
+        written and comes back as None."""
+        L = self.L
+        mu, lv = (torch.empty(B, L, device=device) for _ in range(2))
+        z = None if eps is None else torch.empty(B, L, device=device)
         p = {"mu": [None if h is None else h[:, :L] for h in heads], "lv": [None if h is None else h[:, L:] for h in heads],
              "dmu": [None] * 3, "dlv": [None] * 3, "ld": [2 * L] * 3}
         if avail is None:
             ops.B.poe_fwd([p], eps, mu, lv, z, None, True, 1, B, L)
         else:       # a mixed request: the same single launch, the experts of each row chosen by the row's word of the table
             ops.B.poe_fwd_avail([p], [avail], eps, mu, lv, z, None, True, 1, B, L)
-        return self._decode(z, cond) + (mu, lv)
+        return mu, lv, z
 
     def _zero_latent(self, B):
         """eps = 0: z is the posterior mean.  Allocated and cleared once per batch size, outside any captured region."""
@@ -1627,9 +1640,50 @@ class MVAEInference:
                 "mse_pose": mse[0] if tp is not None else None, "kl": kl[0],
                 "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
 
+    def _iw_score(self, K, self_target, visual, tactile, pose, tv, tt, tp, mask, cond=None, avail=None, tavail=None):
+        """The importance-weighted bound of K draws per row: the encoders, the heads and the PoE launch ONCE (z not requested), one
+        [K][B][L] draw, one iw_latent launch (z_k and the density ratio of each draw), the decoders on the K * B rows, the row
+        kernels with G = K passes against the one target (slots 0..K-1 of [K][B] tables; MMDYN_BCE_GROUPS_MAX passes per launch)
+        and one assembly launch.  Tables: fp64 [3][K][B] = (visual, tactile, pose), zeroed by one fill that a captured graph
+        replays."""
+        iw_latent, iw_assemble_rows = ops.backend_op("iw_latent"), ops.backend_op("iw_assemble_rows")
+        with self._index_scope():
+            ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
+            B, L, dev = ref.shape[0], self.L, ref.device
+            mu, lv, _ = self._poe(self._heads(visual, tactile, pose, cond), avail, None, B, dev)
+            eps = self.noise.eps((K, B, L), dev)
+            self.noise.commit()
+            z, ratio = torch.empty(K, B, L, device=dev), torch.empty(K, B, dtype=torch.float64, device=dev)
+            iw_latent(mu, lv, eps, z, ratio, K, B, L)
+            # the condition rows in [K][B] order, like z
+            cond_k = None if cond is None else cond.repeat((K,) + (1,) * (cond.dim() - 1))
+            v, t, pr = self._decode(z.view(K * B, L), cond_k)
+        if self_target:
+            tv, tt, tp = visual, tactile, pose if self.use_pose else None
+        tab = torch.zeros(3, K, B, dtype=torch.float64, device=dev)
+        kl = torch.empty(1, B, dtype=torch.float64, device=dev)
+        chw, hw = v[0].numel(), v[0, 0].numel()
+        mc = 1 if mask is None else mask.shape[1]
+        for g0 in range(0, K, ops.ROW_GROUPS_MAX):
+            slots = list(range(g0, min(K, g0 + ops.ROW_GROUPS_MAX)))
+            rows_of = slice(g0 * B, (slots[-1] + 1) * B)
+            for slot, (lg, tg) in enumerate(((v, tv), (t, tt))):
+                if tg is not None:
+                    ops.B.bce_logits_rows_groups(lg[rows_of], tg, tab[slot], slots, B, chw, mask=mask, hw=hw, mask_channels=mc)
+            if tp is not None:
+                ops.B.mse_rows_groups(pr[rows_of], tp, tab[2], slots, B, tp.shape[1])
+        ops.B.kl_rows(mu, lv, kl, 1, B, L)
+        rows, ess = torch.empty(B, device=dev), torch.empty(B, device=dev)
+        log_w = torch.empty(K, B, dtype=torch.float64, device=dev)
+        iw_assemble_rows(tab[:2] if tv is not None or tt is not None else None, tab[2] if tp is not None else None, ratio, tavail,
+                         rows, ess, log_w, K, B, self._pose_multiplier, 1.0, self._klw)
+        return {"rows": rows, "ess": ess, "log_w": log_w, "ratio": ratio, "bce_visual": tab[0] if tv is not None else None,
+                "bce_tactile": tab[1] if tt is not None else None, "mse_pose": tab[2] if tp is not None else None, "kl": kl[0],
+                "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
+
     @torch.no_grad()
     def score(self, x, pose=None, targets=None, loss_mask=None, kl_weight=1.0, pose_multiplier=1000.0, condition=None,
-              available=None, target_available=None):
+              available=None, target_available=None, samples=None):
         """Per-sample terms of ONE eval-mode forward of the modality subset ``x = [visual | None, tactile | None]`` (+ ``pose``)
         against ``targets = [visual | None, tactile | None, pose | None]`` (default: the inputs that were given): a dict of
         device tensors, all ``[B]`` -- ``bce_visual`` / ``bce_tactile`` (sum over (C, H, W) of BCE-with-logits; with ``loss_mask``
@@ -1644,13 +1698,35 @@ class MVAEInference:
         targets exist per row; it defaults to ``available`` when the targets default to the inputs, and to "all present" when
         explicit targets are given.  A (row, term) without an available target adds nothing to ``rows`` and its entry in
         ``bce_visual`` / ``bce_tactile`` / ``mse_pose`` is 0 (the assembly launch does both; no launch is added); ``kl`` is
-        every row's own KL as before."""
+        every row's own KL as before.
+
+        ``samples`` (None: everything above, launch for launch): an int K >= 1 asks for the importance-weighted bound of K draws
+        per row, ``rows[b] = -(logsumexp_k log_w[k][b] - log K)`` with ``log_w_k = -rec_k - kl_weight * ratio_k``: z_k = eps_k *
+        exp(log_var / 2) + means for ONE [K][B][L] draw, ratio_k = log q(z_k|x) - log p(z_k) = sum 0.5 (z^2 - eps^2 - log_var)
+        (its mean over draws is ``kl``), rec_k the reconstruction terms of draw k.  A loss like ``rows`` above -- equal in
+        expectation at K = 1, a tighter bound on -log p(x) as K grows.  The encoders run once, the decoders on K * B rows; the
+        launch count does not depend on K up to MMDYN_BCE_GROUPS_MAX = 8 draws (beyond: one more launch per term and 8 draws).
+        The dict then holds ``rows`` and ``ess`` (the effective sample size of the weights, in [1, K]: how far ``rows`` can be
+        trusted), both fp32 [B]; ``log_w``, ``ratio``, ``bce_visual``, ``bce_tactile``, ``mse_pose``: fp64 [K][B] (None without a
+        target, an absent (row, term) 0 in all K entries); ``kl``: the analytic KL, fp64 [B]; ``means`` / ``log_var``; ``recon_x``:
+        the logits of the K * B rows, draw-major.  Captured and replayed under a key that carries K; everything else as above.
+        ValueError: K < 1 or no integer, or K * B rows of the largest decoder activation reaching 2^31 elements."""
         visual, tactile = x
         c = lambda t: None if t is None else t.contiguous()
         ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
         if all(t is None for t in ins) and available is None:
             raise ValueError("score needs at least one modality")
         B = self._batch_of(ins, available)
+        if samples is not None:
+            if isinstance(samples, bool) or not isinstance(samples, numbers.Integral) or samples < 1:
+                raise ValueError(f"samples must be an integer >= 1 (the number of latent draws per row), got {samples!r}")
+            samples = int(samples)
+            # the decoders index their activations with 32-bit element offsets; the largest is the last hidden layer's
+            # [K * B][32][S / 2][S / 2] (32 * 32 * 32 per row at the reference's 64 x 64)
+            per_row = 32 * (self.model.visual_decoder.image_size // 2) ** 2
+            if samples * B * per_row >= 1 << 31:
+                raise ValueError(f"samples = {samples} draws of B = {B} rows make a decoder activation of {samples * B} x {per_row} "
+                                 f"elements, past 2^31; the largest samples for B = {B} is {((1 << 31) - 1) // (B * per_row)}")
         cond = self._condition(condition, B)
         self_target = targets is None
         tg = [None] * 3 if self_target else [c(t) for t in (list(targets) + [None] * 3)[:3]]
@@ -1674,14 +1750,18 @@ class MVAEInference:
         args = ins + tg + [loss_mask]
         key = ("score", self_target, self._pose_multiplier) + tuple(None if t is None else tuple(t.shape) for t in args)
         key, args = key + (self._cond_key(cond),), args + [cond]
+        if samples is None:
+            fn = lambda *a: self._score(self_target, *a)
+        else:
+            fn = lambda *a: self._iw_score(samples, self_target, *a)
         if available is None and target_available is None:
-            return self._run(key, lambda *a: self._score(self_target, *a), None, args)
+            return self._run(key if samples is None else key + (("samples", samples),), fn, None, args)
         avail = self._availability(available, B)
         if target_available is None and self_target:
             target_available = available
         tavail = self._availability(target_available, B)
         key = key + tuple(None if t is None else ("avail",) + tuple(t.shape) for t in (avail, tavail))
-        return self._run(key, lambda *a: self._score(self_target, *a), None, args + [avail, tavail])
+        return self._run(key if samples is None else key + (("samples", samples),), fn, None, args + [avail, tavail])
 
     def _complete(self, sample, visual, tactile, pose, cond, avail):
         """One (mixed) forward, then one select launch per returned modality."""

@@ -19,6 +19,7 @@ from ._lib import PassExperts, MAX_PASSES, MAX_EXPERTS, check
 
 ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
 DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0 = 0, 1, 2, 3, 4
+ROW_GROUPS_MAX = 8         # MMDYN_BCE_GROUPS_MAX: the passes one launch of a *_groups kernel walks over its target
 
 
 def _ptr(t, dtype=torch.float32):
@@ -984,6 +985,60 @@ class HipBackend:
                                                       ctypes.addressof(bm), ctypes.addressof(mm), P, B, float(kl_weight),
                                                       float(pose_multiplier), _ptr(kl_weight_dev), int(kl_mode), _stream()),
               "mmdyn_elbo_assemble_rows_avail")
+
+    # ---- importance-weighted K-sample bound (evaluation only) ----
+    @staticmethod
+    def _iw_tables(name, *specs):
+        """Pointers of contiguous GPU tables, each given as (tensor | None, shape, what, dtype): every shape and dtype is checked
+        (ValueError) before the first pointer is taken (a CPU tensor: RuntimeError); None stays None."""
+        for t, shape, what, dtype in specs:
+            if t is not None and (t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+                raise ValueError(f"mmdyn_hip: {name}: {what} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+        return [_ptr(t, dtype) for t, _, _, dtype in specs]
+
+    def iw_latent(self, mu, lv, eps_noise, z, ratio, K, B, L):
+        """mu / lv: fp32 [B, L] rows (may be column views of a fused heads output: unit inner stride, one row stride for both);
+        eps_noise: fp32 [K][B][L], read; z: fp32 [K][B][L] = eps * exp(lv / 2) + mu, written; ratio: fp64 [K][B] =
+        sum_L 0.5 * (z^2 - eps^2 - lv), written (no zeroing needed)."""
+        K, B, L = int(K), int(B), int(L)
+        if K < 1 or B < 1 or L < 1:
+            raise ValueError(f"mmdyn_iw_latent: K = {K}, B = {B}, L = {L} must all be positive")
+        for t, what in ((mu, "mu"), (lv, "lv")):
+            if t.dtype != torch.float32 or tuple(t.shape) != (B, L) or t.stride(1) != 1:
+                raise ValueError(f"mmdyn_iw_latent: {what} must be fp32 [B={B}, L={L}] with unit inner stride, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+        ld = mu.stride(0) if B > 1 else max(mu.stride(0), L)
+        if (B > 1 and lv.stride(0) != ld) or ld < L:
+            raise ValueError(f"mmdyn_iw_latent: mu and lv must share one row stride >= L (got {mu.stride(0)} and {lv.stride(0)})")
+        f32, f64 = torch.float32, torch.float64
+        e, zp, rp = self._iw_tables("iw_latent", (eps_noise, (K, B, L), "eps", f32), (z, (K, B, L), "z", f32), (ratio, (K, B), "ratio", f64))
+        if not (mu.is_cuda and lv.is_cuda):
+            raise RuntimeError("mmdyn_hip: the HIP path needs GPU tensors (got a CPU tensor); there is no CPU fallback")
+        check(self.lib.mmdyn_iw_latent(mu.data_ptr(), lv.data_ptr(), ld, e, zp, rp, K, B, L, _stream()), "mmdyn_iw_latent")
+
+    def iw_assemble_rows(self, bce_rows, mse_rows, ratio, tavail, out, ess, log_w, K, B, pose_multiplier, kl_weight=1.0,
+                         kl_weight_dev=None):
+        """bce_rows: fp64 [n_bce <= 2][K][B] (visual, tactile) or None; mse_rows: fp64 [K][B] or None; ratio: fp64 [K][B]; tavail:
+        the target-availability table (uint8 [B][4]) or None; out: fp32 [B] = -(logsumexp_k log_w - log K) with log_w[k][b] =
+        -(bce + pose_multiplier * mse) - kl_weight * ratio; ess: fp32 [B] or None; log_w: fp64 [K][B] or None.  The K table entries
+        of a (row, term) whose target is absent are overwritten with 0."""
+        K, B = int(K), int(B)
+        if K < 1 or B < 1:
+            raise ValueError(f"mmdyn_iw_assemble_rows: K = {K} and B = {B} must be positive")
+        n_bce = 0
+        if bce_rows is not None:
+            if bce_rows.dim() != 3 or not 1 <= bce_rows.shape[0] <= 2:
+                raise ValueError(f"mmdyn_iw_assemble_rows: bce_rows must be fp64 [1 or 2][K={K}][B={B}], got {tuple(bce_rows.shape)}")
+            n_bce = bce_rows.shape[0]
+        name, f32, f64 = "iw_assemble_rows", torch.float32, torch.float64
+        tp = self._avail(tavail, B, name, out)
+        bp, mp, rp, op, ep, lp = self._iw_tables(name, (bce_rows, (n_bce, K, B), "bce_rows", f64), (mse_rows, (K, B), "mse_rows", f64),
+                                                 (ratio, (K, B), "ratio", f64), (out, (B,), "out", f32), (ess, (B,), "ess", f32),
+                                                 (log_w, (K, B), "log_w", f64))
+        check(self.lib.mmdyn_iw_assemble_rows(bp, mp, rp, tp, op, ep, lp, n_bce, K, B,
+                                              float(pose_multiplier), float(kl_weight), _ptr(kl_weight_dev), _stream()),
+              "mmdyn_iw_assemble_rows")
 
     # ---- weighted per-sample ELBO: the gradient seeds with a per-sample scale ----
     @staticmethod

@@ -624,6 +624,36 @@ class Reconstruction(Problem):
                            condition=x.get('shock') if self._conditional else None, sample=sample)
         return tuple(None if t is None else t.clone() for t in out)
 
+    def iw_score(self, data_input, data_target, samples=16):
+        """The importance-weighted bound of one batch in the loader's format (cnn-mvae): ``parse_input``, then
+        :meth:`mmdyn_hip.engine.MVAEInference.score` with ``samples`` draws per frame on the joint subset, with the problem's KL
+        weight, pose multiplier and (``--mask-loss``) loss mask.  Returns ``{"rows": fp32 [B], "ess": fp32 [B]}``: a loss per frame
+        that tightens towards -log p(x) as ``samples`` grows -- the number to compare checkpoints or rank frames by -- and the
+        effective sample size of its weights.  Eval-mode arithmetic: the model is put in ``eval()`` for the call and goes back to
+        the mode it was in; the serving engine is built on first use and re-packs the weights on every call (training changes
+        them)."""
+        if 'mvae' not in str(self.parameters.get('model_name')):
+            raise ValueError(f"iw_score() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
+        inputs, targets = self.parse_input(data_input, data_target)
+        if not self._fused_applicable(inputs):
+            raise ValueError("iw_score() takes a visuotactile batch in the loader's format (a list of tensors)")
+        from ..engine import MVAEInference
+        was_training = self._model.training
+        self._model.eval()
+        try:
+            eng = getattr(self, '_iw_scorer', None)
+            if eng is None or eng.model is not self._model:
+                eng = self._iw_scorer = MVAEInference(self._model)
+            else:
+                eng.refresh()
+            xs, ts = self._fused_io(inputs, targets)
+            res = eng.score(list(xs[:2]), pose=xs[2] if len(xs) > 2 else None, targets=list(ts), loss_mask=self._fused_mask(targets),
+                            kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier,
+                            condition=inputs.get('shock') if self._conditional else None, samples=samples)
+            return {"rows": res["rows"].clone(), "ess": res["ess"].clone()}
+        finally:
+            self._model.train(was_training)
+
     def parse_input(self, data, target):
         if not isinstance(data, list):
             return data.to(self._device), target.to(self._device)
