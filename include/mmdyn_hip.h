@@ -614,6 +614,34 @@ int mmdyn_iw_assemble_rows(double* bce_rows, double* mse_rows, const double* rat
                            double* log_w, int n_bce, int K, int B, float pose_multiplier, float kl_weight, const float* kl_weight_dev,
                            void* stream);
 
+/* ---- multi-step rollout of the one-step dynamics model (replaces, in a loop, MVAE.forward, vae.py:126-165, followed by the
+ * sigmoid that takes the image logits to image space, problems.py:616-626: the reference never feeds a prediction back) ---------
+ * One launch turns the decoder outputs of step t into the inputs of step t + 1, for up to MMDYN_FEED_GROUPS tensors (visual
+ * image, tactile image, pose) at once:
+ *   out[g][b][i] = (obs[g] && (!obs_avail || obs_avail[b][column[g]])) ? obs[g][b][i]
+ *                                                                    : (logits[g] ? 1 / (1 + expf(-r)) : r),  r = recon[g][b][i],
+ * every tensor fp32 [B][row_len[g]].  obs_avail: an availability table as above (uint8 [B][MMDYN_MAX_EXPERTS], 4-byte aligned,
+ * MMDYN_ERR_SHAPE otherwise; null = every row of every given obs is observed); column[g] is the table byte of group g.  An observed
+ * row is copied bit for bit; the side that is not taken is not loaded and may hold NaN / Inf.  Each group's output has the bits of
+ * mmdyn_complete_select(obs[g], recon[g], obs_avail, column[g], out[g], B, row_len[g], logits[g]) -- same expression, same access
+ * scheme: 16-byte accesses where the three pointers of the group are 16-byte aligned, element by element otherwise, any row_len
+ * (a quad that straddles two rows selects per element).  A block works on one group and the grid is divided between the groups
+ * by their quad counts.  No LDS, no atomics, no workspace.
+ * Checked on the host before the launch: groups, or recon / out of a group < G, null: MMDYN_ERR_NULL; G outside
+ * [1, MMDYN_FEED_GROUPS], B < 1, a row_len < 1, a column outside [0, MMDYN_MAX_EXPERTS), a misaligned table, or an out[g] that
+ * overlaps recon[g] or obs[g]: MMDYN_ERR_SHAPE; B * row_len[g] >= 2^31: MMDYN_ERR_RANGE.  The struct is read during the call only.
+ * Added without touching an existing signature or workspace: the revision stays 6. */
+#define MMDYN_FEED_GROUPS 4
+typedef struct {
+  const float* recon[MMDYN_FEED_GROUPS];  /* [B][row_len[g]]: the step's decoder output (image logits / pose decoder output) */
+  const float* obs[MMDYN_FEED_GROUPS];    /* observed next frame, same shape; null: nothing observed in this group */
+  float* out[MMDYN_FEED_GROUPS];          /* next state = trajectory slot, same shape */
+  int row_len[MMDYN_FEED_GROUPS];
+  int logits[MMDYN_FEED_GROUPS];          /* != 0: recon holds logits, the state is their sigmoid */
+  int column[MMDYN_FEED_GROUPS];          /* availability-table byte of the group */
+} mmdyn_feed_groups;
+int mmdyn_rollout_feed(const mmdyn_feed_groups* groups, int G, const uint8_t* obs_avail, int B, void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call
  * (graph-replay safe); p/g/m/v: flat fp32 buffers of n elements; g is multiplied by grad_scale first */

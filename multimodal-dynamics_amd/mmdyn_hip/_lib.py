@@ -24,8 +24,14 @@ class PackEntry(ctypes.Structure):
                 ("cols_out", _I), ("ld_out", _I), ("dst_bf16", _I)]
 
 
+class FeedGroups(ctypes.Structure):
+    """mmdyn_feed_groups (include/mmdyn_hip.h)."""
+    _fields_ = [("recon", _P * 4), ("obs", _P * 4), ("out", _P * 4), ("row_len", _I * 4), ("logits", _I * 4), ("column", _I * 4)]
+
+
 MAX_PASSES = 8
 MAX_EXPERTS = 4
+FEED_GROUPS = 4           # MMDYN_FEED_GROUPS
 ABI_VERSION = 6          # MMDYN_ABI_VERSION of the include/mmdyn_hip.h this table was written against
 
 # name -> argument type codes, in header order: p pointer, i int, l int64, f float, Q uint64
@@ -137,6 +143,7 @@ _SIGNATURES = {
     "mmdyn_elbo_assemble_weighted": "pppppppppp" + "ii" + "ff" + "p" + "i" + "p",
     "mmdyn_iw_latent": "pp" + "i" + "ppp" + "iii" + "p",
     "mmdyn_iw_assemble_rows": "ppppppp" + "iii" + "ff" + "pp",
+    "mmdyn_rollout_feed": "p" + "i" + "p" + "i" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

@@ -1483,11 +1483,11 @@ class MVAEInference:
         LN.join()
         return heads
 
-    def _poe(self, heads, avail, eps, B, device):
+    def _poe(self, heads, avail, eps, B, device, out=None):
         """The product-of-experts launch on the heads: (mu, lv, z), each [B][L]; ``eps`` None: the posterior alone, z is not
-        written and comes back as None."""
+        written and comes back as None.  ``out``: the (mu, lv) tensors to write instead of new ones."""
         L = self.L
-        mu, lv = (torch.empty(B, L, device=device) for _ in range(2))
+        mu, lv = out if out is not None else (torch.empty(B, L, device=device) for _ in range(2))
         z = None if eps is None else torch.empty(B, L, device=device)
         p = {"mu": [None if h is None else h[:, :L] for h in heads], "lv": [None if h is None else h[:, L:] for h in heads],
              "dmu": [None] * 3, "dlv": [None] * 3, "ld": [2 * L] * 3}
@@ -1620,8 +1620,17 @@ class MVAEInference:
         v, t, pr, mu, lv = self._forward(visual, tactile, pose, cond, avail)
         if self_target:
             tv, tt, tp = visual, tactile, pose if self.use_pose else None
-        B, L = mu.shape
+        B = mu.shape[0]
         bce, mse, kl = torch.zeros(3, 2, B, dtype=torch.float64, device=mu.device)
+        rows = self._score_tail(v, t, pr, mu, lv, tv, tt, tp, mask, tavail, bce, mse, kl)
+        return {"rows": rows, "bce_visual": bce[0] if tv is not None else None, "bce_tactile": bce[1] if tt is not None else None,
+                "mse_pose": mse[0] if tp is not None else None, "kl": kl[0],
+                "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
+
+    def _score_tail(self, v, t, pr, mu, lv, tv, tt, tp, mask, tavail, bce, mse, kl, rows=None):
+        """The row kernels and the assembly of one pass into the (zeroed) fp64 [2][B] tables of :meth:`_score`; ``rows``: the fp32 [B]
+        tensor to write instead of a new one.  Returns the rows."""
+        B, L = mu.shape
         chw, hw = v[0].numel(), v[0, 0].numel()
         mc = 1 if mask is None else mask.shape[1]
         for slot, (lg, tg) in enumerate(((v, tv), (t, tt))):
@@ -1630,15 +1639,14 @@ class MVAEInference:
         if tp is not None:
             ops.B.mse_rows_groups(pr, tp, mse, [0], B, tp.shape[1])
         ops.B.kl_rows(mu, lv, kl[0:1], 1, B, L)
-        rows = torch.empty(B, device=mu.device)
+        if rows is None:
+            rows = torch.empty(B, device=mu.device)
         if tavail is None:
             ops.B.elbo_assemble_rows(bce, mse, kl, None, rows, None, 2, B, 1.0, self._pose_multiplier, self._klw, 1)
         else:       # the assembly's sibling: a (row, term) whose target is absent leaves the row sum and its table entry becomes 0
             ops.B.elbo_assemble_rows_avail(bce, mse, kl, None, rows, None, tavail, [0, 1], [2, -1], 2, B, 1.0,
                                            self._pose_multiplier, self._klw, 1)
-        return {"rows": rows, "bce_visual": bce[0] if tv is not None else None, "bce_tactile": bce[1] if tt is not None else None,
-                "mse_pose": mse[0] if tp is not None else None, "kl": kl[0],
-                "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
+        return rows
 
     def _iw_score(self, K, self_target, visual, tactile, pose, tv, tt, tp, mask, cond=None, avail=None, tavail=None):
         """The importance-weighted bound of K draws per row: the encoders, the heads and the PoE launch ONCE (z not requested), one
@@ -1796,6 +1804,146 @@ class MVAEInference:
         key = ("complete", sample) + tuple(None if t is None else tuple(t.shape) for t in ins) + \
             (self._cond_key(cond), None if avail is None else ("avail",) + tuple(avail.shape))
         return self._run(key, lambda *a: self._complete(sample, *a), None, ins + [cond, avail])
+
+    def _rollout(self, T, sample, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
+        """T forwards in a row, each followed by ONE feed launch that writes the next state into its trajectory slot, where the
+        next step's encoders read it; with targets, the tail of :meth:`_score` per step on tables [T][3][2][B] that one fill
+        clears.  Step 0 serves the request's subset / table, every later step is the joint request."""
+        feed = ops.backend_op("rollout_feed")
+        ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
+        B, L, dev, S = ref.shape[0], self.L, ref.device, self.model.visual_decoder.image_size
+        traj = [torch.empty(T, B, 3, S, S, device=dev), torch.empty(T, B, 3, S, S, device=dev),
+                torch.empty(T, B, 7, device=dev) if self.use_pose else None]
+        means, log_var = torch.empty(T, B, L, device=dev), torch.empty(T, B, L, device=dev)
+        scoring = any(t is not None for t in (tv, tt, tp))
+        if scoring:
+            tab = torch.zeros(T, 3, 2, B, dtype=torch.float64, device=dev)
+            rows = torch.empty(T, B, device=dev)
+        state = [visual, tactile, pose]
+        step_of = lambda t, i: None if t is None else t[i]
+        with self._index_scope():
+            for i in range(T):
+                c_i = step_of(cond, i) if per_step_cond else cond
+                heads = self._heads(state[0], state[1], state[2], c_i)
+                eps = self._draw_latent(B) if sample else self._zero_latent(B)
+                mu, lv, z = self._poe(heads, avail if i == 0 else None, eps, B, dev, out=(means[i], log_var[i]))
+                v, t, pr = self._decode(z, c_i)
+                if scoring:         # before the correction below: what the model predicted for frame i + 1
+                    self._score_tail(v, t, pr, mu, lv, step_of(tv, i), step_of(tt, i), step_of(tp, i), None, step_of(tav, i),
+                                     tab[i, 0], tab[i, 1], tab[i, 2], rows=rows[i])
+                groups = [{"recon": v, "obs": step_of(ov, i), "out": traj[0][i], "logits": True, "column": 0},
+                          {"recon": t, "obs": step_of(ot, i), "out": traj[1][i], "logits": True, "column": 1}]
+                if self.use_pose:
+                    groups.append({"recon": pr, "obs": step_of(op, i), "out": traj[2][i], "logits": False, "column": 2})
+                feed(groups, step_of(oav, i), B)
+                state = [traj[0][i], traj[1][i], traj[2][i] if self.use_pose else None]
+        res = {"visual": traj[0], "tactile": traj[1], "pose": traj[2], "means": means, "log_var": log_var,
+               "bce_visual": None, "bce_tactile": None, "mse_pose": None, "kl": None, "rows": None}
+        if scoring:
+            res.update(bce_visual=tab[:, 0, 0] if tv is not None else None, bce_tactile=tab[:, 0, 1] if tt is not None else None,
+                       mse_pose=tab[:, 1, 0] if tp is not None else None, kl=tab[:, 2, 0], rows=rows)
+        return res
+
+    def _step_tensors(self, name, given, T, B):
+        """``observed`` / ``targets`` = [visual | None, tactile | None, pose | None], each [T, B, ...] -> three contiguous fp32
+        tensors / None on the engine's device; ValueError for a wrong leading (T, B), a wrong row shape, or a pose for a model
+        without one."""
+        if given is None:
+            return [None] * 3
+        if not isinstance(given, (list, tuple)) or len(given) > 3:
+            raise ValueError(f"{name} must be a list [visual | None, tactile | None, pose | None]")
+        given = (list(given) + [None] * 3)[:3]
+        if given[2] is not None and not self.use_pose:
+            raise ValueError(f"{name} holds a pose, the model has none")
+        S = self.model.visual_decoder.image_size
+        out = []
+        for t, shape, what in zip(given, ((T, B, 3, S, S), (T, B, 3, S, S), (T, B, 7)), ("visual", "tactile", "pose")):
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape):
+                raise ValueError(f"{name}: {what} must be a tensor of shape [T={T}, B={B}, ...] = {shape}, got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            out.append(None if t is None else t.to(device=self.dev, dtype=torch.float32).contiguous())
+        return out
+
+    def _step_availability(self, name, available, T, B):
+        """[T, B, 2 or 3] in the forms ``available`` takes -> the kernels' tables uint8 [T][B][4] (None stays None)."""
+        if available is None:
+            return None
+        try:
+            available = torch.as_tensor(available)
+        except Exception as e:
+            raise ValueError(f"{name} must be a [T, B, 2] or [T, B, 3] tensor: {e}")
+        if available.dim() != 3 or tuple(available.shape[:2]) != (T, B):
+            raise ValueError(f"{name} {tuple(available.shape)} is not [T={T}, B={B}, 2 or 3]")
+        return self._availability(available.reshape(T * B, available.shape[2]), T * B).view(T, B, -1)
+
+    @torch.no_grad()
+    def rollout(self, x, pose=None, steps=1, available=None, condition=None, sample=False, observed=None, observed_available=None,
+                targets=None, target_available=None, kl_weight=1.0, pose_multiplier=1000.0):
+        """The one-step dynamics model applied to its own output ``steps`` = T times, as ONE captured graph.  With s_0 the request
+        (``x``, ``pose``, ``available`` as in :meth:`forward`), for t = 0 .. T-1: the eval-mode forward of s_t (step 0 on the
+        request's subset / availability table, later steps on every modality); the prediction p_{t+1} = (sigmoid(visual logits),
+        sigmoid(tactile logits), pose decoder output); s_{t+1}[m][b] = ``observed[m][t][b]`` where ``observed_available[t][b][m]``
+        is set, p_{t+1}[m][b] otherwise (filtering: a row that takes an observed modality keeps the predicted frames of its
+        others).  One launch per step writes s_{t+1} into its slot of the returned trajectory, and the next step's encoders read
+        that slot.
+
+        ``sample=False`` decodes every step's posterior mean; ``sample=True`` draws a fresh [B, L] per step from the engine's
+        Philox stream.  ``condition``: as in :meth:`forward`, held for all steps, or one per step ([T, B, condition_dim];
+        categorical: indices [T, B]); :meth:`bad_condition` covers the whole call.  ``observed`` = [visual | None, tactile | None,
+        pose | None], each [T, B, ...]; ``observed_available``: [T, B, 2 or 3] in the forms ``available`` takes (None: every
+        given modality in every row and step; with [.., 2] the pose is observed wherever a pose tensor is given).  Default:
+        nothing observed (open loop).  ``targets``: the layout of ``observed``; the terms of step t are those of :meth:`score` on
+        the logits, pose output and posterior of step t against ``targets[m][t]``, before step t's observation is taken -- a fully
+        observed rollout scores one-step-ahead error, an open-loop one open-loop error.  ``target_available``: as
+        ``observed_available``, default all present; a (step, row, term) without a target is 0 and left out of ``rows``.
+
+        Returns a dict of the graph's static outputs (copy what must survive the next call of the same shapes): ``visual`` /
+        ``tactile`` [T, B, 3, S, S] in [0, 1] and ``pose`` [T, B, 7] (None without a pose model), slot t = s_{t+1}, observed rows
+        bit for bit; ``means`` / ``log_var`` [T, B, L]; and, None without targets, ``bce_visual`` / ``bce_tactile`` / ``mse_pose``
+        / ``kl`` (fp64 [T, B]; each step's own KL) and ``rows`` (fp32 [T, B]) = bce_visual + bce_tactile + pose_multiplier *
+        mse_pose + kl_weight * kl.  The KL weight is read from device memory: one graph serves every weight.  Nothing
+        synchronises.  ValueError: ``steps`` no integer >= 1, a wrong leading (T, B), ``observed_available`` without ``observed``
+        (``target_available`` without ``targets``), a pose for a model without one, a trajectory tensor of 2^31 elements or more."""
+        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or steps < 1:
+            raise ValueError(f"steps must be an integer >= 1 (the number of model applications), got {steps!r}")
+        T, sample = int(steps), bool(sample)
+        visual, tactile = x
+        c = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
+        if all(t is None for t in ins) and available is None:
+            raise ValueError("rollout needs at least one modality")
+        B = self._batch_of(ins, available)
+        S = self.model.visual_decoder.image_size
+        if T * B * 3 * S * S >= 1 << 31:
+            raise ValueError(f"steps = {T} of B = {B} rows make a trajectory tensor of {T * B} x {3 * S * S} elements, past 2^31; "
+                             f"the largest steps for B = {B} is {((1 << 31) - 1) // (B * 3 * S * S)}")
+        per_step_cond = False
+        if self.conditional and torch.is_tensor(condition):
+            per_step_cond = condition.dim() == 3 or (self.categorical and condition.dim() == 2 and tuple(condition.shape) != (B, 1))
+        if per_step_cond:
+            if tuple(condition.shape[:2]) != (T, B):
+                raise ValueError(f"a per-step condition is [T={T}, B={B}, ...], got {tuple(condition.shape)}")
+            cond = self._condition(condition.reshape((T * B,) + tuple(condition.shape[2:])), T * B)
+            cond = cond.view((T, B) + tuple(cond.shape[1:]))
+        else:
+            cond = self._condition(condition, B)
+        if observed is None and observed_available is not None:
+            raise ValueError("observed_available was given without observed")
+        if targets is None and target_available is not None:
+            raise ValueError("target_available was given without targets")
+        obs = self._step_tensors("observed", observed, T, B)
+        oav = self._step_availability("observed_available", observed_available, T, B)
+        tg = self._step_tensors("targets", targets, T, B)
+        tav = self._step_availability("target_available", target_available, T, B)
+        if getattr(self, "_klw", None) is None:
+            self._klw = torch.zeros(1, device=self.dev)         # read from device memory: one captured graph serves every weight
+        self._klw.fill_(float(kl_weight))
+        self._pose_multiplier = float(pose_multiplier)
+        avail = self._availability(available, B)
+        args = ins + [cond, avail] + obs + [oav] + tg + [tav]
+        key = ("rollout", T, sample, self._pose_multiplier, per_step_cond, None if cond is None else self._cond_key(cond)) + \
+            tuple(None if t is None else (str(t.dtype),) + tuple(t.shape) for t in args)
+        return self._run(key, lambda *a: self._rollout(T, sample, per_step_cond, *a), None, args)
 
     @torch.no_grad()
     def inference(self, n=1, c=None):

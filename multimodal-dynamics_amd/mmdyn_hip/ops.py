@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import PassExperts, MAX_PASSES, MAX_EXPERTS, check
+from ._lib import PassExperts, FeedGroups, MAX_PASSES, MAX_EXPERTS, FEED_GROUPS, check
 
 ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
 DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0 = 0, 1, 2, 3, 4
@@ -985,6 +985,41 @@ class HipBackend:
                                                       ctypes.addressof(bm), ctypes.addressof(mm), P, B, float(kl_weight),
                                                       float(pose_multiplier), _ptr(kl_weight_dev), int(kl_mode), _stream()),
               "mmdyn_elbo_assemble_rows_avail")
+
+    # ---- multi-step rollout: the step's decoder outputs -> the next step's inputs ----
+    def rollout_feed(self, groups, obs_avail, B):
+        """One launch for up to FEED_GROUPS tensors: ``groups`` is a list of dicts {recon, obs | None, out, logits, column};
+        out[b] = observed(b) ? obs[b] : (logits ? sigmoid(recon[b]) : recon[b]) with observed(b) = obs is given and (obs_avail is
+        None or obs_avail[b][column] != 0).  recon / obs / out: contiguous fp32 [B, ...] of one shape on one device; obs_avail:
+        uint8 [B][4] or None.  Each group's result has the bits of :meth:`complete_select` on the same operands."""
+        name, B = "rollout_feed", int(B)
+        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
+            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
+                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
+        if B < 1:
+            raise ValueError(f"mmdyn_hip: {name}: B = {B} must be positive")
+        arg = FeedGroups()
+        like = groups[0]["recon"]
+        for g, grp in enumerate(groups):
+            recon, obs, out = grp["recon"], grp.get("obs"), grp["out"]
+            for t, what in ((recon, "recon"), (obs, "obs"), (out, "out")):
+                if t is None and what == "obs":
+                    continue
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.shape[0] != B:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor of B={B} rows, got "
+                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+                if t.shape != recon.shape or t.device != like.device:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} {tuple(t.shape)} on {t.device} does not match recon "
+                                     f"{tuple(recon.shape)} on {like.device}")
+            if recon.numel() == 0:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: empty rows")
+            if not 0 <= int(grp["column"]) < MAX_EXPERTS:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: column {grp['column']} is not a column of the availability table")
+        table = self._avail(obs_avail, B, name, like)
+        for g, grp in enumerate(groups):
+            arg.recon[g], arg.obs[g], arg.out[g] = _ptr(grp["recon"]), _ptr(grp.get("obs")), _ptr(grp["out"])
+            arg.row_len[g], arg.logits[g], arg.column[g] = grp["recon"].numel() // B, int(bool(grp["logits"])), int(grp["column"])
+        check(self.lib.mmdyn_rollout_feed(ctypes.addressof(arg), len(groups), table, B, _stream()), "mmdyn_rollout_feed")
 
     # ---- importance-weighted K-sample bound (evaluation only) ----
     @staticmethod

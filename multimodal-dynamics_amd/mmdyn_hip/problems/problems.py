@@ -755,3 +755,72 @@ class DynModeling(SeqModeling):
                  'shock': shock},
                 {'target_output': to, 'target_object_pose': [torch.roll(data[2], -1, dims=0).to(dev)],
                  'loss_mask': target[3].to(dev)})
+
+    def rollout(self, data_input, data_target, steps=None, observe=(), sample=False):
+        """The one-step predictor applied to its own output along each sequence of one loader batch (cnn-mvae; n sequences of l
+        frames as flat [n*l, ...] tensors): :meth:`mmdyn_hip.engine.MVAEInference.rollout` from frame 0 of every sequence (with its
+        ``data[3]`` availability) for ``steps`` <= l steps (default l), scored against the recorded sequence.  The target of step
+        t is frame t + 1 (images with that frame's ``data[3]`` as target availability, pose ``data[2]``) and, for t + 1 = l, the
+        dataset's final target (``target[i][l-1::l]``, ``target[2][l-1::l]`` for the pose -- not the wrap-around roll of
+        :meth:`parse_input`), counted as present; the pose target always counts.  ``observe``: a tuple out of ("visual",
+        "tactile", "pose") -- those modalities are fed back from the recorded frames t + 1 < l where the dataset has them (touch
+        keeps arriving after vision is lost).  ``data[4]`` per frame is the per-step condition of a ``--conditional`` model.
+        Eval-mode arithmetic: the model is put in ``eval()`` for the call and goes back to the mode it was in; the engine is
+        built on first use and re-packs the weights on every call.  Returns clones of the engine's dict."""
+        if 'mvae' not in str(self.parameters.get('model_name')):
+            raise ValueError(f"rollout() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
+        if not isinstance(data_input, (list, tuple)) or len(data_input) < 4 or self.parameters.get('input_type') != 'visuotactile':
+            raise ValueError("rollout() takes a visuotactile batch in the loader's format (a list of tensors)")
+        names = ('visual', 'tactile', 'pose')
+        observe = (observe,) if isinstance(observe, str) else tuple(observe)
+        if any(o not in names for o in observe):
+            raise ValueError(f"observe holds names out of {names}, got {observe!r}")
+        l = int(self._seq_length)
+        T = l if steps is None else steps
+        if isinstance(T, bool) or not isinstance(T, int) or T < 1 or T > l:
+            raise ValueError(f"steps must be an integer in [1, {l}] (the sequences hold {l} frames), got {steps!r}")
+        data, target, dev = list(data_input), list(data_target), self._device
+        if data[0].shape[0] % l:
+            raise ValueError(f"a batch of {data[0].shape[0]} frames does not hold whole sequences of {l}")
+        n = data[0].shape[0] // l
+        use_pose = bool(self._model._use_pose)
+
+        def steps_of(frames, last):
+            """[T, n, ...]: frame t + 1 of every sequence for t + 1 < l, ``last`` [n, ...] for t + 1 = l."""
+            f = frames.reshape((n, l) + tuple(frames.shape[1:]))[:, 1:T + 1].transpose(0, 1)
+            return (f if T < l else torch.cat((f, last.unsqueeze(0).to(f.dtype)), 0)).to(dev)
+
+        targets = [steps_of(data[0], target[0][l - 1::l]), steps_of(data[1], target[1][l - 1::l]),
+                   steps_of(data[2], target[2][l - 1::l]) if use_pose else None]
+        has = data[3].to(torch.float32)
+        tavail = torch.cat((steps_of(has[:, :2], torch.ones(n, 2)), torch.ones(T, n, 1, device=dev)), 2)
+        observed = oavail = None
+        if observe:
+            # past the recorded frames (t + 1 = l) nothing is observed: a zero frame the table switches off
+            observed = [steps_of(data[m], torch.zeros_like(data[m][l - 1::l])) if names[m] in observe and (m < 2 or use_pose)
+                        else None for m in range(3)]
+            inside = steps_of(torch.ones(n * l, 1), torch.zeros(n, 1))
+            col = lambda m: (steps_of(has[:, m:m + 1], torch.zeros(n, 1)) if m < 2 else inside) if observed[m] is not None \
+                else torch.zeros(T, n, 1, device=dev)
+            oavail = torch.cat([col(m) for m in range(3)], 2)
+        cond = None
+        if self._conditional:
+            if len(data) < 5:
+                raise ValueError("a conditional model needs the shock force of every frame (data[4])")
+            cond = data[4].reshape((n, l) + tuple(data[4].shape[1:]))[:, :T].transpose(0, 1).to(dev)
+        from ..engine import MVAEInference
+        was_training = self._model.training
+        self._model.eval()
+        try:
+            eng = getattr(self, '_roller', None)
+            if eng is None or eng.model is not self._model:
+                eng = self._roller = MVAEInference(self._model)
+            else:
+                eng.refresh()
+            res = eng.rollout([data[0][::l].to(dev), data[1][::l].to(dev)], pose=data[2][::l].to(dev) if use_pose else None,
+                              steps=T, available=data[3][::l].to(dev), condition=cond, sample=sample, observed=observed,
+                              observed_available=oavail, targets=targets, target_available=tavail, kl_weight=self._kl_weight,
+                              pose_multiplier=self._pose_multiplier)
+            return {k: None if v is None else v.clone() for k, v in res.items()}
+        finally:
+            self._model.train(was_training)
