@@ -76,7 +76,13 @@ extern "C" {
 
 #define MMDYN_TCONV_S1P0 4      /* transposed k4 s1 p0 (Ho = Hi+3): rows ordered (output pixel, sample) inside a group so
                                   every tile covers one output pixel and only its 1..16 valid taps are multiplied --
-                                  exactly the useful MACs, no zero padding, no column matrix */
+                                  exactly the useful MACs, no zero padding, no column matrix.  Served for the 5x5 -> 8x8
+                                  layer only (vae.py:268): the blocks walk the four-pixel quads of an 8x8 output, so any
+                                  other extent -- Hi != Wi included -- is MMDYN_ERR_SHAPE.  C itself is plain NHWC */
+/* Hi != Wi: the other modes take non-square extents (tests/test_exact_gpu.py holds them to exact results).  The kernels
+ * specialised to the model's square layers -- the patch-resident k4 s2 p1 kernel (N = 32), its plane form and the 3-channel
+ * first / last-layer kernels -- decline such a shape and the launch runs on the generic kernels; mmdyn_igemm_planes_served answers
+ * 0 for a non-square shape only they would serve. */
 
 const char* mmdyn_version(void);
 /* ABI revision of this header.  It changes whenever an exported signature or a workspace requirement changes (round 4 added

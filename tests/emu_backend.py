@@ -93,7 +93,7 @@ class EmuBackend:
     def igemm_nt(self, A, Bp, bias, C, C_act, stats, ws, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, ldc, stride, offset,
                  act, splitk):
         self.calls.append("igemm_nt")
-        assert Cin % 32 == 0 and N % 32 == 0 and ldc == N
+        assert Cin % 32 == 0 and N % 32 == 0 and ldc >= N
         Bt = G * Bg
         Bp = Bp.reshape(-1, N, Cin)
         # operands rounded to bf16 (RNE), fp32 accumulate -- except on the HBM-bound 3-channel layers, whose kernels
@@ -146,9 +146,10 @@ class EmuBackend:
             return
         if bias is not None:
             out = out + bias
-        C.reshape(-1, N).copy_(out)
+        # rows of stride ldc: the columns N..ldc of a row are left untouched
+        C.reshape(-1)[: out.shape[0] * ldc].reshape(-1, ldc)[:, :N].copy_(out)
         if C_act is not None:
-            C_act.reshape(-1, N).copy_(_act(out, act))
+            C_act.reshape(-1)[: out.shape[0] * ldc].reshape(-1, ldc)[:, :N].copy_(_act(out, act))
 
     def igemm_nt_grouped(self, A, Bp, bias, C, C_act, u, G, rows, K, N, act):
         """mmdyn_igemm_nt_grouped: G dense GEMMs of one shape, group g on its own weights / bias."""
