@@ -276,7 +276,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-// v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the ~10-instruction IEEE division sequence
+// Block total of a double (blocks of 256 threads) times `scale`, added into *dst by ONE fp64 atomic: the 64-lane shuffle sums, then
+// the four wave totals in wave order -- red[0] + red[1] + red[2] + red[3], the scale applied to that sum.  Every thread of the block
+// must call it; a second call in the same kernel needs a __syncthreads() first (the scratch is reused).
+__device__ __forceinline__ void block_atomic_add(double v, double* dst, double scale = 1.0) {
+  v = wave_sum_d(v);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(dst, scale * (red[0] + red[1] + red[2] + red[3]));
+}
+
+// Product of experts: the reference adds eps to a variance and again to its reciprocal's denominator (vae.py:311-318)
+constexpr float POE_EPS = 1e-8f;
+
+// Per-row availability: uint8 [B][MMDYN_MAX_EXPERTS] tables read as ONE 32-bit word per row (byte m = expert m, little endian)
+constexpr uint32_t ALL_PRESENT = 0x01010101u;
+__device__ __forceinline__ bool has(uint32_t word, int m) { return ((word >> (8 * m)) & 0xffu) != 0u; }
+
+// Two sigmoids with DIFFERENT bits.  sigmoid_exact: library expf and an IEEE division -- what the completion select and the
+// rollout feed publish as image values.  sigmoidf_ (Swish): v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the ~10-instruction
+// IEEE division sequence.
+__device__ __forceinline__ float sigmoid_exact(float v) { return 1.f / (1.f + expf(-v)); }
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float swishf_(float x) { return x * sigmoidf_(x); }
 // d/dx [x*sigmoid(x)] = s * (1 + x*(1-s))

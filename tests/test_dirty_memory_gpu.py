@@ -763,7 +763,7 @@ def test_last_decoder_layer_fused_forms(G, Bg, H, dtype, monkeypatch):
 
 
 def test_row_loss_kernels():
-    """The per-sample forms (elbo_rows.hip, elbo_weighted.hip): row tables are accumulators (v + first == second to rtol 1e-12),
+    """The per-sample forms (elbo_loss.hip, plain and GRAD instances): row tables are accumulators (v + first == second to rtol 1e-12),
     the gradient outputs bit-identical, a discarded pass's gradient rows written as zeros; sums of the rows against the emulation's
     batch sums at the bound test_bce_logits_groups_* holds the sums to (rtol 1e-5)."""
     Bg, G, chw, hw = 5, 3, 3 * 4096, 4096
