@@ -87,8 +87,9 @@ extern "C" {
 const char* mmdyn_version(void);
 /* ABI revision of this header.  It changes whenever an exported signature or a workspace requirement changes (round 4 added
  * the `ws` argument of mmdyn_igemm_nt_dgrad_act / _dgrad_bn and the slab workspace of large launches: revision 4; round 5 the
- * plane-packed weight kinds of the pack plan: revision 5; round 6 the `zdst` field of mmdyn_pass_experts, the arrival-flag words in
- * front of the slab workspace (mmdyn_igemm_slab_floats*) and new entry points: revision 6; the per-sample
+ * plane-packed weight kinds of the pack plan: revision 5; round 6 the `zdst` field of mmdyn_pass_experts, the separate, nullable
+ * `arrival_flags` argument of mmdyn_igemm_nt_mx / _dgrad_bn / _dgrad_act (MMDYN_IGEMM_FLAG_WORDS zeroed words of its own; the layout
+ * and size of `ws`, mmdyn_igemm_slab_floats*, did not change) and new entry points: revision 6; the per-sample
  * ELBO entry points (mmdyn_*_rows*) and the importance-weighted bound (mmdyn_iw_*) were added without touching an existing signature or
  * workspace and keep revision 6).  A binding checks mmdyn_abi_version() == MMDYN_ABI_VERSION right after
  * loading the library (mmdyn_hip/_lib.py does) so that a caller built against an older header fails at load time instead of

@@ -261,6 +261,18 @@ struct LdsOptIn {
   }
 };
 
+// Compute units of the current device (persistent kernels size their grids by it); 256, the MI355X's, where no device answers
+static inline int device_cus() {
+  static int cus[LdsOptIn::MAX_DEVICES] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= LdsOptIn::MAX_DEVICES) return 256;
+  if (!cus[dev]) {
+    hipDeviceProp_t p;
+    cus[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
+  }
+  return cus[dev];
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -426,40 +426,24 @@ static int launch_t(const float* A, const float* Bp, const float* bias, float* C
 
 }  // namespace
 
-int mmdyn_igemm_d16_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats,
-                        float* ws, IgemmGeom g, int stride, int offset, hipStream_t st) {
-  if (g.bn_y && !g.bn_mean) return 1;          // activation-only backward epilogue: not built here
-
-  (void)stride;
-  (void)offset;
+// Served: opt-in only (d16_serves).  One BatchNorm partial-sum tile per wave tile of 16*mt rows.
+bool mmdyn_igemm_d16_plan(const IgemmGeom& g, IgemmPlan* p) {
+  if (g.bn_y && !g.bn_mean) return false;          // activation-only backward epilogue: not built here
   D16Tile t;
-  if (!d16_serves(g) || !d16_pick(g, &t)) return 1;
-  if (t.mt == 4 && t.nt == 4) return launch_t<4, 4>(A, Bp, bias, C, C_act, stats, ws, g, st);
-  if (t.mt == 8 && t.nt == 2) return launch_t<8, 2>(A, Bp, bias, C, C_act, stats, ws, g, st);
-  if (t.mt == 4 && t.nt == 2) return launch_t<4, 2>(A, Bp, bias, C, C_act, stats, ws, g, st);
+  if (!d16_serves(g) || !d16_pick(g, &t)) return false;
+  *p = IgemmPlan{};
+  p->family = IGEMM_D16;
+  p->bm = 16 * t.mt;
+  p->bn = 16 * t.nt;
+  p->stat_tiles = igemm_m_tiles(g, p->bm);
+  return true;
+}
+
+int mmdyn_igemm_d16_launch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
+                           const IgemmGeom& g, const IgemmPlan& p, hipStream_t st) {
+  if (p.bm == 64 && p.bn == 64) return launch_t<4, 4>(A, Bp, bias, C, C_act, stats, ws, g, st);
+  if (p.bm == 128 && p.bn == 32) return launch_t<8, 2>(A, Bp, bias, C, C_act, stats, ws, g, st);
+  if (p.bm == 64 && p.bn == 32) return launch_t<4, 2>(A, Bp, bias, C, C_act, stats, ws, g, st);
   return launch_t<2, 2>(A, Bp, bias, C, C_act, stats, ws, g, st);
 }
 
-// number of BatchNorm partial-sum tiles per group this kernel family writes for the shape (0: shape not served)
-int mmdyn_igemm_d16_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  IgemmGeom g{};
-  g.mode = mode;
-  g.G = G;
-  g.Bg = Bg;
-  g.Hi = Hi;
-  g.Wi = Wi;
-  g.Cin = Cin;
-  g.Ho = Ho;
-  g.Wo = Wo;
-  g.N = N;
-  g.ldc = N;
-  g.splitk = 1;
-  g.nclasses = (mode == MMDYN_TCONV_S2P1) ? 4 : 1;
-  g.ntaps = (mode == MMDYN_CONV || mode == MMDYN_TCONV_S1P0) ? 16 : (mode == MMDYN_TCONV_S2P1 ? 4 : 1);   // as igemm_entry
-  g.Hr = (mode == MMDYN_TCONV_S2P1) ? Hi : Ho;
-  g.Wr = (mode == MMDYN_TCONV_S2P1) ? Wi : Wo;
-  D16Tile t;
-  if (!d16_serves(g) || !d16_pick(g, &t)) return 0;
-  if (mode == MMDYN_TCONV_S1P0) return Ho * Wo * ceil_div(Bg, 16 * t.mt);
-  return g.nclasses * ceil_div(Bg * g.Hr * g.Wr, 16 * t.mt);
-}

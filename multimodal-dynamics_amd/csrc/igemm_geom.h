@@ -47,47 +47,107 @@ struct IgemmGeom {
   unsigned* flags;
 };
 
-// igemm_d16.hip: fp32 implicit GEMM on v_mfma_f32_16x16x4_f32 with operand fragments loaded straight from global
-// memory (no LDS, no block barrier).  Returns MMDYN_OK / an error code, or 1 when the shape is not served (the caller
-// then takes the LDS-tiled kernel).  d16_stat_tiles: number of BatchNorm partial-sum tiles per group it writes, 0 when
-// the shape is not served.
-// LAB build only (igemm_d16.hip is not part of the product library: measured slower inside the two-lane step, LAB_NOTES A.a).
+// Shape -> row grid, output-parity classes and taps: the one place that knows the modes' geometry.  Fills the shape fields of *g
+// for every mode and returns MMDYN_OK or the mode's shape error.  A launch returns that error; the host queries ignore it (they
+// have always answered for any shape, and the launch is what refuses a bad one).
+static inline int igemm_shape_geom(IgemmGeom* g, int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, int ldc,
+                                   int stride, int offset, int splitk) {
+  g->mode = mode;
+  g->G = G;
+  g->Bg = Bg;
+  g->Hi = Hi;
+  g->Wi = Wi;
+  g->Cin = Cin;
+  g->Ho = Ho;
+  g->Wo = Wo;
+  g->N = N;
+  g->ldc = ldc;
+  g->splitk = splitk;
+  g->Hr = Ho;
+  g->Wr = Wo;
+  g->rs = 1;
+  g->ro = 0;
+  g->os = 1;
+  g->ntaps = 1;
+  g->nclasses = 1;
+  if (mode == MMDYN_DENSE) return (Hi != Ho || Wi != Wo) ? MMDYN_ERR_SHAPE : MMDYN_OK;
+  if (mode == MMDYN_CONV) {
+    g->rs = stride;
+    g->ro = offset;
+    g->ntaps = 16;
+    return MMDYN_OK;
+  }
+  if (mode == MMDYN_IM2COL3) return (Hi != 2 * Ho || Wi != 2 * Wo || Cin != 64 || splitk != 1) ? MMDYN_ERR_SHAPE : MMDYN_OK;
+  if (mode == MMDYN_TCONV_S1P0) {
+    g->ntaps = 16;
+    return (Ho != Hi + 3 || Wo != Wi + 3 || Ho != 8 || Wo != 8 || splitk != 1) ? MMDYN_ERR_SHAPE : MMDYN_OK;
+  }
+  if (mode == MMDYN_TCONV_S2P1) {
+    g->Hr = Hi;
+    g->Wr = Wi;
+    g->os = 2;
+    g->ntaps = 4;
+    g->nclasses = 4;
+    return (Ho != 2 * Hi || Wo != 2 * Wi) ? MMDYN_ERR_SHAPE : MMDYN_OK;
+  }
+  return MMDYN_ERR_SHAPE;
+}
+
+// BatchNorm partial-sum tiles per group of a launch that cuts its rows into M-tiles of bm: one per M-tile and parity class
+// (TCONV_S1P0: per output pixel and sample tile -- a tile never straddles an output pixel)
+static inline int igemm_m_tiles(const IgemmGeom& g, int bm) {
+  if (g.mode == MMDYN_TCONV_S1P0) return g.Hr * g.Wr * ceil_div(g.Bg, bm);
+  return g.nclasses * ceil_div(g.Bg * g.Hr * g.Wr, bm);
+}
+
+// ---- routing: the kernel family that serves a launch, and its plan (igemm_route in igemm_nt.hip is the one author) ----
+enum IgemmFamily {
+  IGEMM_NONE = 0,   // not served (only a plane launch can end here: every other one ends at the register-staged tiles)
+  IGEMM_TILES,      // register-staged block tiles (igemm_nt.hip)
+  IGEMM_TILES_X3,   // ... in the three-term split arithmetic
+  IGEMM_WS,         // one-tile LDS-DMA ring (igemm_ws.hip)
+  IGEMM_WSP,        // persistent stream-K ring (igemm_wsp.hip)
+  IGEMM_WSP3,       // ... on operands that arrive split (the plane ring)
+  IGEMM_PATCH,      // patch-resident k4 s2 p1 transposed convolution (tconv_patch.hip), fp32 or plane operands
+  IGEMM_D16         // direct-fragment kernels (igemm_d16.hip, LAB build only)
+};
+// What a family's launcher branches on, decided once by its plan hook, and the two numbers the caller must know before the
+// launch.  Fields a family does not use stay 0.
+struct IgemmPlan {
+  int family;
+  int bm, bn;        // block tile (D16: the wave tile)
+  int wm, wn;        // MFMA-wave tile, where one block tile is built with more than one (WSP, WSP3)
+  int slots;         // LDS ring slots (WS, WSP, WSP3)
+  int bpc;           // stream-K: resident blocks per CU the grid is sized for
+  int per;           // stream-K: K-step units per block -- the cut of the schedule
+  int x3;            // fp32 launch in the three-term split arithmetic
+  int planes;        // PATCH: operands arrive split
+  int stat_tiles;    // BatchNorm partial-sum tiles per group the launch writes into `stats`
+  int slab_floats;   // floats of slab workspace the launch wants in `ws` (stream-K split tiles; 0: none)
+};
+
+// One hook pair per family.  plan: geometry (shape, splitk, storage flags, grouped weights, epilogue pointers) in; false = not
+// served, else *p is filled.  launch: runs that plan and does not pick again; returns MMDYN_OK / an error code.
+bool mmdyn_igemm_ws_plan(const IgemmGeom& g, bool bf16_ops, IgemmPlan* p);
+int mmdyn_igemm_ws_launch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
+                          const IgemmGeom& g, const IgemmPlan& p, bool bf16_ops, hipStream_t st);
+bool mmdyn_igemm_wsp_plan(const IgemmGeom& g, bool bf16_ops, bool x3, IgemmPlan* p);
+int mmdyn_igemm_wsp_launch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
+                           const IgemmGeom& g, const IgemmPlan& p, bool bf16_ops, hipStream_t st);
+bool mmdyn_igemm_wsp3_plan(const IgemmGeom& g, IgemmPlan* p);
+int mmdyn_igemm_wsp3_launch(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
+                            const IgemmGeom& g, const IgemmPlan& p, hipStream_t st);
+bool mmdyn_tconv_patch_plan(const IgemmGeom& g, bool planes, IgemmPlan* p);
+int mmdyn_tconv_patch_launch(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
+                             const IgemmGeom& g, const IgemmPlan& p, hipStream_t st);
+// LAB build only (igemm_d16.hip is not part of the product library: measured slower inside the two-lane step, LAB_NOTES A.a)
 #ifdef MMDYN_LAB
-int mmdyn_igemm_d16_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats,
-                        float* ws, IgemmGeom g, int stride, int offset, hipStream_t st);
-int mmdyn_igemm_d16_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N);
+bool mmdyn_igemm_d16_plan(const IgemmGeom& g, IgemmPlan* p);
+int mmdyn_igemm_d16_launch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
+                           const IgemmGeom& g, const IgemmPlan& p, hipStream_t st);
 #else
-static inline int mmdyn_igemm_d16_try(const float*, const float*, const float*, float*, float*, float*, float*, const IgemmGeom&,
-                                      int, int, hipStream_t) { return 1; }
-static inline int mmdyn_igemm_d16_stat_tiles(int, int, int, int, int, int, int, int, int) { return 0; }
+static inline bool mmdyn_igemm_d16_plan(const IgemmGeom&, IgemmPlan*) { return false; }
 #endif
-
-// tconv_patch.hip: patch-resident k4 s2 p1 transposed convolution (fp32, 16x16x64 -> 32x32x32).  Same protocol as the d16 hooks.
-int mmdyn_tconv_patch_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                          const IgemmGeom& g, hipStream_t st);
-int mmdyn_tconv_patch_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N);
-// ... on operands that arrive split (fp32x3 plane rows): the shapes served, and the launch (1: not served)
-bool mmdyn_tconv_patch_p3_serves(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N);
-int mmdyn_tconv_patch_p3_try(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                             const IgemmGeom& g, hipStream_t st);
-
-// igemm_ws.hip: wave-specialised fp32 implicit GEMM (loader waves + LDS-DMA ring).  Same protocol as the hooks above.
-int mmdyn_igemm_ws_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                       const IgemmGeom& g, bool bf16_ops, hipStream_t st);
-int mmdyn_igemm_ws_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N);
-
-// igemm_wsp.hip: the persistent, stream-K-scheduled form of the ring kernel for the large launches.  Same protocol as the
-// hooks above; `slabs` is the workspace for the pieces of split tiles (mmdyn_igemm_wsp_slab_bytes; may be null when that is 0).
-int mmdyn_igemm_wsp_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
-                        const IgemmGeom& g, bool bf16_ops, hipStream_t st);
-int mmdyn_igemm_wsp_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, bool b16);
-// ... with BOTH operands arriving as the three-plane bf16 split of fp32 tensors (rows of [plane][Cin]); same protocol
-int mmdyn_igemm_wsp3_try(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
-                         const IgemmGeom& g, hipStream_t st);
-bool mmdyn_igemm_wsp3_serves(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N);
-int mmdyn_igemm_wsp3_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N);
-int64_t mmdyn_igemm_wsp3_slab_bytes(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N);
-int64_t mmdyn_igemm_wsp_slab_bytes(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, bool b16);
 
 // tile choice shared by the launcher and mmdyn_igemm_stat_tiles.  Measured on MI355X over every shape of the
 // bs=256 step (tests/microbench/sweep_tiles.py): the 64x64 tile (more resident blocks per CU to hide the

@@ -878,105 +878,104 @@ static bool x3_pick(bool allowed, int mode, int G, int rows_per_group, int N, in
   }
   return true;
 }
-static int x3_stat_tiles(bool allowed, int mode, int G, int Bg, int Hi, int Wi, int Ho, int Wo, int N) {
-  int bm, bn;
-  if (mode == MMDYN_TCONV_S1P0) return x3_pick(allowed, mode, G, Bg * Ho * Wo, N, 1, &bm, &bn) ? Ho * Wo * ceil_div(Bg, bm) : 0;
-  const int Hr = mode == MMDYN_TCONV_S2P1 ? Hi : Ho, Wr = mode == MMDYN_TCONV_S2P1 ? Wi : Wo, ncls = mode == MMDYN_TCONV_S2P1 ? 4 : 1;
-  return x3_pick(allowed, mode, G, Bg * Hr * Wr, N, 1, &bm, &bn) ? ncls * ceil_div(Bg * Hr * Wr, bm) : 0;
-}
-
-static int lds_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  if (mode == MMDYN_TCONV_S1P0) {
+// ---- the route: which kernel family serves a launch, decided ONCE -- for the launcher and for the host queries ----
+// The chain, first family that serves the launch wins:
+//   operands that arrive split:  the patch-resident plane kernel, the plane ring, else not served;
+//   fp32 only:                   the persistent ring in the split arithmetic, (LAB) the one-tile ring in the split arithmetic,
+//                                the register-staged X3 tiles, the patch-resident kernel, (LAB) the direct-fragment kernels;
+//   fp32 and all-16-bit:         the persistent ring, the one-tile ring;
+//   every launch:                the register-staged tiles.
+// Each family's own rule (its plan hook, next to the measurements behind it) says whether it serves; this function only orders
+// them.  Nothing is cached: the LAB knobs are read at every call (tests flip them between launches).
+static IgemmPlan igemm_route(const IgemmGeom& g, bool bf16, bool x3_allowed, bool planes) {
+  IgemmPlan r{};
+  const int mode = g.mode;
+  if (planes) {       // operands already split: served by a plane kernel or not at all
+    if (mode == MMDYN_TCONV_S2P1 && !g.b_group_stride && mmdyn_tconv_patch_plan(g, true, &r)) return r;
+    if (ws_enabled() && mmdyn_igemm_wsp3_plan(g, &r)) return r;
+    return IgemmPlan{};
+  }
+  // the ring kernels' picks do not depend on the arithmetic, so one call each decides both of their places in the chain
+  const bool ring = ws_enabled() && mode != MMDYN_IM2COL3;
+  const bool wsp_x3 = !bf16 && x3_wsp(x3_allowed);
+  IgemmPlan wsp{}, ws{};
+  const bool wsp_ok = ring && mmdyn_igemm_wsp_plan(g, bf16, wsp_x3, &wsp);
+  if (wsp_ok && (bf16 || wsp_x3)) return wsp;
+  const bool ws_ok = ring && mode != MMDYN_TCONV_S1P0 && mmdyn_igemm_ws_plan(g, bf16, &ws);
+  if (!bf16) {
+    IgemmPlan patch{};
+    const bool patch_ok = mode == MMDYN_TCONV_S2P1 && mmdyn_tconv_patch_plan(g, false, &patch);
+    if (ws_ok && !patch_ok && x3_ws(x3_allowed)) {      // (LAB experiment: see x3_ws)
+      ws.x3 = 1;
+      return ws;
+    }
     int bm, bn;
-    pick_tile(N, Bg, G * 16, 1, 1, 0, &bm, &bn);
-    return Ho * Wo * ceil_div(Bg, bm);
+    if (x3_pick(x3_allowed, mode, g.G, g.Bg * g.Hr * g.Wr, g.N, g.splitk, &bm, &bn)) {
+      r.family = IGEMM_TILES_X3;
+      r.bm = bm;
+      r.bn = bn;
+      r.x3 = 1;
+      r.stat_tiles = igemm_m_tiles(g, bm);
+      return r;
+    }
+    if (patch_ok) return patch;
+    if (mode != MMDYN_IM2COL3 && !g.b_group_stride && mmdyn_igemm_d16_plan(g, &r)) return r;
+    if (wsp_ok) return wsp;
   }
-  int Hr = Ho, Wr = Wo, ncls = 1, ntaps = (mode == MMDYN_CONV) ? 16 : 1;
-  if (mode == MMDYN_TCONV_S2P1) {
-    Hr = Hi;
-    Wr = Wi;
-    ncls = 4;
-    ntaps = 4;
-  }
-  const int ksteps = ntaps * (Cin / BK);
-  int bm, bn;
-  pick_tile(N, Bg * Hr * Wr, G, ncls, 1, ksteps, &bm, &bn);
-  return ncls * ceil_div(Bg * Hr * Wr, bm);
+  if (ws_ok) return ws;
+  r.family = IGEMM_TILES;
+  if (mode == MMDYN_TCONV_S1P0)
+    pick_tile(g.N, g.Bg, g.G * 16, 1, 1, 0, &r.bm, &r.bn);
+  else
+    pick_tile(g.N, g.Bg * g.Hr * g.Wr, g.G, g.nclasses, g.splitk, g.ntaps * (g.Cin / BK), &r.bm, &r.bn);
+  r.stat_tiles = igemm_m_tiles(g, r.bm);
+  return r;
 }
 
-// fp32 launches go to the wave-independent kernels of igemm_d16.hip where those serve the shape; the bf16 matrix-core
-// modes always take the LDS-tiled kernels of this file.  The number of partial-sum tiles follows the kernel.
-static int f32_stat_tiles(bool x3, int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  int t = x3_wsp(x3) ? mmdyn_igemm_wsp_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, false) : 0;   // (same order as igemm_entry)
-  if (t > 0) return t;
-  t = (x3_ws(x3) && mode != MMDYN_TCONV_S1P0) ? mmdyn_igemm_ws_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) : 0;
-  if (t > 0 && mmdyn_tconv_patch_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) == 0) return t;
-  t = x3_stat_tiles(x3, mode, G, Bg, Hi, Wi, Ho, Wo, N);
-  if (t > 0) return t;
-  const int tp = mmdyn_tconv_patch_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  if (tp > 0) return tp;
-  t = mmdyn_igemm_d16_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  if (t > 0) return t;
-  t = ws_enabled() ? mmdyn_igemm_wsp_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, false) : 0;
-  if (t > 0) return t;
-  t = ws_enabled() ? mmdyn_igemm_ws_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) : 0;
-  return t > 0 ? t : lds_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
+// The host queries ask about the launch a layer is about to make, and know its shape and storage flags only.  What makes a
+// route a query, written down here once: splitk == 1, one weight matrix shared by the groups (b_group_stride == 0), no
+// backward epilogue, ldc == N.  The launcher-only conditions behind these (no query-side counterpart: d16 and the plane patch
+// kernel are skipped for grouped weights, ws_pick divides the K-steps by splitk, d16 has no activation-only epilogue) therefore
+// never apply to a query.  The shape is not validated: a query answers for any shape, and the launch refuses a bad one.
+static IgemmPlan query_route(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, int flags) {
+  IgemmGeom g{};
+  (void)igemm_shape_geom(&g, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, /*ldc=*/N, /*stride=*/1, /*offset=*/0, /*splitk=*/1);
+  const bool bf16 = (flags & 1) != 0 || (flags & 32) != 0;     // flags as mmdyn_igemm_nt_mx
+  if (bf16) {
+    g.a_b16 = (flags & 2) != 0;
+    g.b_b16 = (flags & 16) != 0;
+    g.f16 = (flags & 32) != 0;
+  }
+  return igemm_route(g, bf16, (flags & 128) != 0, (flags & 384) == 384);
 }
+
+/* BatchNorm partial-sum tiles per group the launch of this shape writes into `stats`: fp32, the bf16 matrix cores on fp32
+ * storage, and (flags as mmdyn_igemm_nt_mx) the mixed-storage / fp32x3 / plane launches.  0: a plane launch that is not served. */
 extern "C" int mmdyn_igemm_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  return f32_stat_tiles(false, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-}
-/* Floats of workspace the fp32 launch of this shape wants in `ws` (with splitk == 1): the slabs of the persistent kernel's
- * split tiles (igemm_wsp.hip).  0: none. */
-static int f32_slab_floats(bool x3, int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  if (!ws_enabled()) return 0;
-  if (x3_wsp(x3) && mmdyn_igemm_wsp_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, false) > 0)
-    return (int)(mmdyn_igemm_wsp_slab_bytes(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, false) / 4);
-  if (x3_ws(x3) && mode != MMDYN_TCONV_S1P0 && mmdyn_tconv_patch_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) == 0 &&
-      mmdyn_igemm_ws_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) > 0)
-    return 0;
-  if (x3_stat_tiles(x3, mode, G, Bg, Hi, Wi, Ho, Wo, N) > 0) return 0;
-  if (mmdyn_tconv_patch_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) > 0) return 0;
-  if (mmdyn_igemm_d16_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) > 0) return 0;
-  return (int)(mmdyn_igemm_wsp_slab_bytes(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, false) / 4);
-}
-extern "C" int mmdyn_igemm_slab_floats(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  return f32_slab_floats(false, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-}
-/* 1: the fp32x3 launch of this shape can take its operands ALREADY SPLIT (flag bits 7 + 8 of mmdyn_igemm_nt_mx); its
- * partial-sum tile count and slab workspace are those of the flags == 128 queries.  0: keep fp32 operands. */
-extern "C" int mmdyn_igemm_planes_served(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  if (G <= 0 || Bg <= 0 || Cin <= 0 || N <= 0 || Cin % BK || N % 32) return 0;
-  if (mmdyn_tconv_patch_p3_serves(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N)) return 1;      // the patch-resident 32-channel up-sampling layers
-  if (!ws_enabled()) return 0;
-  return mmdyn_igemm_wsp3_serves(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) ? 1 : 0;
+  return query_route(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 0).stat_tiles;
 }
 extern "C" int mmdyn_igemm_stat_tiles_bf16(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  return lds_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
+  return query_route(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 1).stat_tiles;
 }
-/* ... of the mixed-storage entry points, flags as mmdyn_igemm_nt_mx: launches whose operands are BOTH 16-bit in HBM (bits 1 and
- * 4) may run the persistent ring kernel (igemm_wsp.hip), which writes one partial tile per wave row */
 extern "C" int mmdyn_igemm_stat_tiles_mx(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, int flags) {
-  if ((flags & 384) == 384) {     // plane launch
-    if (mmdyn_tconv_patch_p3_serves(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N)) return mmdyn_tconv_patch_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-    return ws_enabled() ? mmdyn_igemm_wsp3_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) : 0;
-  }
-  if (!(flags & 1) && !(flags & 32)) return f32_stat_tiles((flags & 128) != 0, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  if ((flags & 2) && (flags & 16) && ws_enabled()) {
-    const int t = mmdyn_igemm_wsp_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, true);
-    if (t > 0) return t;
-  }
-  return lds_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
+  return query_route(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, flags).stat_tiles;
+}
+/* Floats of workspace the launch of this shape wants in `ws` (with splitk == 1): the slabs of the stream-K kernels' split
+ * tiles (igemm_wsp.hip).  0: none. */
+extern "C" int mmdyn_igemm_slab_floats(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
+  return query_route(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 0).slab_floats;
 }
 extern "C" int mmdyn_igemm_slab_floats_mx(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, int flags) {
-  if ((flags & 384) == 384) {
-    if (mmdyn_tconv_patch_p3_serves(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N)) return 0;
-    return ws_enabled() ? (int)(mmdyn_igemm_wsp3_slab_bytes(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) / 4) : 0;
-  }
-  if (!(flags & 1) && !(flags & 32)) return f32_slab_floats((flags & 128) != 0, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  if (!((flags & 2) && (flags & 16)) || !ws_enabled()) return 0;
-  return (int)(mmdyn_igemm_wsp_slab_bytes(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, true) / 4);
+  return query_route(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, flags).slab_floats;
+}
+/* 1: the fp32x3 launch of this shape can take its operands ALREADY SPLIT (flag bits 7 + 8 of mmdyn_igemm_nt_mx); its
+ * partial-sum tile count and slab workspace are those of the flags == 384 queries.  0: keep fp32 operands. */
+extern "C" int mmdyn_igemm_planes_served(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
+  if (G <= 0 || Bg <= 0 || Cin <= 0 || N <= 0 || Cin % BK || N % 32) return 0;
+  return query_route(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 384).family != IGEMM_NONE ? 1 : 0;
 }
 
+// validate, build the geometry, route, launch
 static int igemm_entry(const float* A, const float* Bp, const float* bias, float* C, float* C_act,
                        float* stats, float* ws, int mode, int G, int Bg, int Hi, int Wi, int Cin,
                        int Ho, int Wo, int N, int ldc, int stride, int offset, int act, int splitk,
@@ -989,16 +988,6 @@ static int igemm_entry(const float* A, const float* Bp, const float* bias, float
   if (splitk < 1) splitk = 1;
   if (splitk > 1 && (mode != MMDYN_DENSE || !ws || stats)) return MMDYN_ERR_SHAPE;
   IgemmGeom g{};
-  g.mode = mode;
-  g.G = G;
-  g.Bg = Bg;
-  g.Hi = Hi;
-  g.Wi = Wi;
-  g.Cin = Cin;
-  g.Ho = Ho;
-  g.Wo = Wo;
-  g.N = N;
-  g.ldc = ldc;
   g.act = act;
   g.has_bias = bias != nullptr;
   g.want_stats = stats != nullptr;
@@ -1039,48 +1028,7 @@ static int igemm_entry(const float* A, const float* Bp, const float* bias, float
   g.b_group_stride = b_group_stride;
   g.bias_group_stride = bias_group_stride;
   g.flags = arrival_flags;
-  g.splitk = splitk;
-  g.nclasses = 1;
-  g.os = 1;
-  if (mode == MMDYN_DENSE) {
-    if (Hi != Ho || Wi != Wo) return MMDYN_ERR_SHAPE;
-    g.Hr = Ho;
-    g.Wr = Wo;
-    g.rs = 1;
-    g.ro = 0;
-    g.ntaps = 1;
-  } else if (mode == MMDYN_CONV) {
-    g.Hr = Ho;
-    g.Wr = Wo;
-    g.rs = stride;
-    g.ro = offset;
-    g.ntaps = 16;
-  } else if (mode == MMDYN_IM2COL3) {
-    if (Hi != 2 * Ho || Wi != 2 * Wo || Cin != 64 || splitk != 1) return MMDYN_ERR_SHAPE;
-    g.Hr = Ho;
-    g.Wr = Wo;
-    g.rs = 1;
-    g.ro = 0;
-    g.ntaps = 1;
-  } else if (mode == MMDYN_TCONV_S1P0) {
-    if (Ho != Hi + 3 || Wo != Wi + 3 || Ho != 8 || Wo != 8 || splitk != 1) return MMDYN_ERR_SHAPE;
-    g.Hr = Ho;
-    g.Wr = Wo;
-    g.rs = 1;
-    g.ro = 0;
-    g.ntaps = 16;
-  } else if (mode == MMDYN_TCONV_S2P1) {
-    if (Ho != 2 * Hi || Wo != 2 * Wi) return MMDYN_ERR_SHAPE;
-    g.Hr = Hi;
-    g.Wr = Wi;
-    g.rs = 1;
-    g.ro = 0;
-    g.os = 2;
-    g.ntaps = 4;
-    g.nclasses = 4;
-  } else {
-    return MMDYN_ERR_SHAPE;
-  }
+  if (const int rc = igemm_shape_geom(&g, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, ldc, stride, offset, splitk)) return rc;
   const int64_t rows = (int64_t)G * Bg * g.Hr * g.Wr;
   if ((int64_t)G * Bg * Hi * Wi * (mode == MMDYN_IM2COL3 ? 3 : Cin) >= (1LL << 31) ||
       (int64_t)G * Bg * Ho * Wo * ldc >= (1LL << 31))
@@ -1094,67 +1042,28 @@ static int igemm_entry(const float* A, const float* Bp, const float* bias, float
                                       st);
     if (rc != 1) return rc;
   }
-  if (planes) {       // operands already split: served by a plane kernel or not at all (mmdyn_igemm_planes_served)
-    if (mode == MMDYN_TCONV_S2P1 && !b_group_stride) {
-      const int rp = mmdyn_tconv_patch_p3_try(A, Bp, bias, C, C_act, stats, ws, g, st);
-      if (rp != 1) return rp;
-    }
-    const int rc = ws_enabled() ? mmdyn_igemm_wsp3_try(A, Bp, bias, C, C_act, stats, ws, g, st) : 1;
-    return rc == 1 ? MMDYN_ERR_SHAPE : rc;
+  const IgemmPlan r = igemm_route(g, bf16, x3_allowed, planes);
+  g.x3 = r.x3;
+  switch (r.family) {
+    case IGEMM_PATCH: return mmdyn_tconv_patch_launch(A, Bp, bias, C, C_act, stats, ws, g, r, st);
+    case IGEMM_WSP3: return mmdyn_igemm_wsp3_launch(A, Bp, bias, C, C_act, stats, ws, g, r, st);
+    case IGEMM_WSP: return mmdyn_igemm_wsp_launch(A, Bp, bias, C, C_act, stats, ws, g, r, bf16, st);
+    case IGEMM_WS: return mmdyn_igemm_ws_launch(A, Bp, bias, C, C_act, stats, ws, g, r, bf16, st);
+#ifdef MMDYN_LAB
+    case IGEMM_D16: return mmdyn_igemm_d16_launch(A, Bp, bias, C, C_act, stats, ws, g, r, st);
+#endif
+    case IGEMM_TILES:
+    case IGEMM_TILES_X3: break;
+    default: return MMDYN_ERR_SHAPE;      // a plane launch no plane kernel serves (mmdyn_igemm_planes_served says so beforehand)
   }
-  if (!bf16 && mode != MMDYN_IM2COL3 && x3_wsp(x3_allowed)) {     // the persistent ring kernel in the split arithmetic
-    IgemmGeom gx = g;
-    gx.x3 = 1;
-    const int rc = mmdyn_igemm_wsp_try(A, Bp, bias, C, C_act, stats, ws, gx, false, st);
-    if (rc != 1) return rc;
-  }
-  if (!bf16 && mode != MMDYN_IM2COL3 && mode != MMDYN_TCONV_S1P0 && x3_ws(x3_allowed) &&
-      mmdyn_tconv_patch_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N) == 0) {      // (LAB experiment: see x3_ws)
-    IgemmGeom gx = g;
-    gx.x3 = 1;
-    const int rc = mmdyn_igemm_ws_try(A, Bp, bias, C, C_act, stats, ws, gx, false, st);
-    if (rc != 1) return rc;
-  }
-  if (!bf16) {        // fp32 through the bf16 matrix cores (three-term operand split)
-    int bm, bn;
-    if (x3_pick(x3_allowed, mode, G, mode == MMDYN_TCONV_S1P0 ? Bg * Ho * Wo : Bg * g.Hr * g.Wr, N, splitk, &bm, &bn)) {
-      g.x3 = 1;
-      if (bn == 128 && bm == 128) return mmdyn_igemm_tile0(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-      if (bn == 128 && bm == 64) return mmdyn_igemm_tile1(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-      if (bn == 64 && bm == 128) return mmdyn_igemm_tile2(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-      if (bn == 32 && bm == 256) return mmdyn_igemm_tile4(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-      if (bn == 32) return mmdyn_igemm_tile5(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-      return mmdyn_igemm_tile3(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-    }
-  }
-  if (!bf16 && mode == MMDYN_TCONV_S2P1) {     // the 64 -> 32 channel up-sampling layer has a patch-resident kernel (tconv_patch.hip)
-    const int rc = mmdyn_tconv_patch_try(A, Bp, bias, C, C_act, stats, ws, g, st);
-    if (rc != 1) return rc;
-  }
-  if (!bf16 && mode != MMDYN_IM2COL3 && !b_group_stride) {
-    const int rc = mmdyn_igemm_d16_try(A, Bp, bias, C, C_act, stats, ws, g, stride, offset, st);
-    if (rc != 1) return rc;
-  }
-  if (ws_enabled() && mode != MMDYN_IM2COL3 && (!bf16 || (g.a_b16 && g.b_b16))) {   // persistent ring kernel (igemm_wsp.hip)
-    const int rc = mmdyn_igemm_wsp_try(A, Bp, bias, C, C_act, stats, ws, g, bf16, st);
-    if (rc != 1) return rc;
-  }
-  if (ws_enabled() && mode != MMDYN_IM2COL3 && mode != MMDYN_TCONV_S1P0) {   // wave-specialised LDS-DMA ring kernels (igemm_ws.hip)
-    const int rc = mmdyn_igemm_ws_try(A, Bp, bias, C, C_act, stats, ws, g, bf16, st);
-    if (rc != 1) return rc;
-  }
-  int bm, bn;
-  if (mode == MMDYN_TCONV_S1P0)
-    pick_tile(N, Bg, G * 16, 1, 1, 0, &bm, &bn);
-  else
-    pick_tile(N, Bg * g.Hr * g.Wr, G, g.nclasses, splitk, g.ntaps * (Cin / BK), &bm, &bn);
-  if (bn == 128 && bm == 128) return mmdyn_igemm_tile0(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-  if (bn == 128 && bm == 64) return mmdyn_igemm_tile1(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-  if (bn == 64 && bm == 128) return mmdyn_igemm_tile2(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-  if (bn == 64 && bm == 64) return mmdyn_igemm_tile3(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
-  if (bn == 32 && bm == 256) return mmdyn_igemm_tile4(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
+  if (r.bn == 128 && r.bm == 128) return mmdyn_igemm_tile0(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
+  if (r.bn == 128 && r.bm == 64) return mmdyn_igemm_tile1(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
+  if (r.bn == 64 && r.bm == 128) return mmdyn_igemm_tile2(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
+  if (r.bn == 64 && r.bm == 64) return mmdyn_igemm_tile3(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
+  if (r.bn == 32 && r.bm == 256) return mmdyn_igemm_tile4(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
   return mmdyn_igemm_tile5(A, Bp, bias, C, C_act, stats, ws, g, st, bf16);
 }
+
 
 extern "C" int mmdyn_igemm_nt(const float* A, const float* Bp, const float* bias, float* C, float* C_act,
                               float* stats, float* ws, int mode, int G, int Bg, int Hi, int Wi, int Cin,

@@ -436,9 +436,9 @@ static WsPick ws_pick(int mode, int G, int Bg, int Hi, int Wi, int Hr, int Wr, i
   const int esz = b16 ? 2 : 4;
   if ((int64_t)G * Bg * Hi * Wi * Cin * esz >= MAX_BUFFER_BYTES || (int64_t)16 * N * Cin * esz >= MAX_BUFFER_BYTES) return p;
   if (b16) {
-    // bf16 operands: the block tile follows the register-staged kernels' rule (igemm_geom.h pick_tile), so the number of
-    // BatchNorm partial-sum tiles a launch writes does not depend on which of the two kernels serves it
-    // (mmdyn_igemm_stat_tiles_bf16 knows the shape, not the storage types)
+    // 16-bit operands: the block tile follows the register-staged kernels' rule (igemm_geom.h pick_tile).  (The number of
+    // BatchNorm partial-sum tiles is this plan's whichever tile is picked here: launch and mmdyn_igemm_stat_tiles_mx share
+    // the route, which knows the storage flags.)
     int bm, bn;
     pick_tile(N, Bg * Hr * Wr, G, ncls, splitk, (mode == MMDYN_CONV ? 16 : (mode == MMDYN_TCONV_S2P1 ? 4 : 1)) * (Cin / BK), &bm,
               &bn);
@@ -505,7 +505,7 @@ static int ws_launch(const float* A, const float* Bp, const float* bias, float* 
 
 template <int MODE, int B16>
 static int ws_launch_mode(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                          const IgemmGeom& g, WsPick p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
+                          const IgemmGeom& g, const IgemmPlan& p, unsigned a_bytes, unsigned b_bytes, hipStream_t st) {
   if constexpr (!B16)
     if (p.bm == 128 && p.bn == 32)
       return ws_launch<MODE, 128, 32, 32, 32, 3, false>(A, Bp, bias, C, C_act, stats, ws, g, a_bytes, b_bytes, st);
@@ -516,21 +516,14 @@ static int ws_launch_mode(const float* A, const float* Bp, const float* bias, fl
   if constexpr (!B16)         // LAB: 64 rows x 128 channels (the gathered operand filled once per 128 output channels)
     if (p.bn == 128) return ws_launch<MODE, 64, 128, 32, 64, 3, B16>(A, Bp, bias, C, C_act, stats, ws, g, a_bytes, b_bytes, st);
 #endif
-  if constexpr (MODE == MMDYN_DENSE) {
-    // Launches of at most two 64x64 blocks per CU (the heads / pose / FC-level GEMMs: K loops of 8-16 steps at one or two
-    // blocks per CU) are chains of DMA round trips, not matrix work: a four-slot ring keeps three K-steps in flight instead of
-    // two (65 KB of LDS: still two blocks per CU).  LAB build: MMDYN_WS_DENSE_S=3 switches it off (A/B).
-    const long blocks = (long)g.G * ceil_div(g.Bg * g.Hr * g.Wr, 64) * (g.N / 64) * g.splitk;
-    const char* e = lab_env("MMDYN_WS_DENSE_S");
-    if (blocks <= 2L * 256 && !(e && e[0] == '3'))
-      return ws_launch<MODE, 64, 64, 32, 32, 4, B16>(A, Bp, bias, C, C_act, stats, ws, g, a_bytes, b_bytes, st);
-  }
+  if constexpr (MODE == MMDYN_DENSE)
+    if (p.slots == 4) return ws_launch<MODE, 64, 64, 32, 32, 4, B16>(A, Bp, bias, C, C_act, stats, ws, g, a_bytes, b_bytes, st);
   return ws_launch<MODE, 64, 64, 32, 32, 3, B16>(A, Bp, bias, C, C_act, stats, ws, g, a_bytes, b_bytes, st);
 }
 
 template <int B16>
 static int ws_dispatch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                       const IgemmGeom& g, WsPick p, hipStream_t st) {
+                       const IgemmGeom& g, const IgemmPlan& p, hipStream_t st) {
   const int esz = B16 ? 2 : 4;
   const unsigned a_bytes = (unsigned)((int64_t)g.G * g.Bg * g.Hi * g.Wi * g.Cin * esz);
   const unsigned b_bytes = (unsigned)(((int64_t)(g.mode == MMDYN_DENSE ? 1 : 16) * g.N * g.Cin +
@@ -544,29 +537,37 @@ static int ws_dispatch(const float* A, const float* Bp, const float* bias, float
 
 }  // namespace
 
-int mmdyn_igemm_ws_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  int Hr = Ho, Wr = Wo, ncls = 1;
-  if (mode == MMDYN_TCONV_S2P1) {
-    Hr = Hi;
-    Wr = Wi;
-    ncls = 4;
+// bf16_ops: the launch runs on the 16-bit matrix cores; served here only when BOTH operands are 16-bit in HBM (bf16, or IEEE
+// half when g.f16 is set too).  One BatchNorm partial-sum tile per M-tile and parity class.
+bool mmdyn_igemm_ws_plan(const IgemmGeom& g, bool bf16_ops, IgemmPlan* p) {
+  if (bf16_ops && (!g.a_b16 || !g.b_b16)) return false;
+  if ((int64_t)g.G * g.b_group_stride * 4 >= MAX_BUFFER_BYTES) return false;      // (grouped weights: one buffer descriptor)
+  const WsPick t = ws_pick(g.mode, g.G, g.Bg, g.Hi, g.Wi, g.Hr, g.Wr, g.Cin, g.N, g.nclasses, g.splitk, bf16_ops);
+  if (!t.bm) return false;
+  *p = IgemmPlan{};
+  p->family = IGEMM_WS;
+  p->bm = t.bm;
+  p->bn = t.bn;
+  p->slots = 3;
+  if (g.mode == MMDYN_DENSE && t.bm == 64 && t.bn == 64) {
+    // Launches of at most two 64x64 blocks per CU (the heads / pose / FC-level GEMMs: K loops of 8-16 steps at one or two
+    // blocks per CU) are chains of DMA round trips, not matrix work: a four-slot ring keeps three K-steps in flight instead of
+    // two (65 KB of LDS: still two blocks per CU).  LAB build: MMDYN_WS_DENSE_S=3 switches it off (A/B).
+    const long blocks = (long)g.G * ceil_div(g.Bg * g.Hr * g.Wr, 64) * (g.N / 64) * g.splitk;
+    const char* e = lab_env("MMDYN_WS_DENSE_S");
+    if (blocks <= 2L * 256 && !(e && e[0] == '3')) p->slots = 4;
   }
-  const WsPick p = ws_pick(mode, G, Bg, Hi, Wi, Hr, Wr, Cin, N, ncls, 1);
-  return p.bm ? ncls * ceil_div(Bg * Hr * Wr, p.bm) : 0;
+  p->stat_tiles = igemm_m_tiles(g, t.bm);
+  return true;
 }
 
-// bf16_ops: the launch runs on the 16-bit matrix cores; served here only when BOTH operands are 16-bit in HBM (bf16, or IEEE
-// half when g.f16 is set too)
-int mmdyn_igemm_ws_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                       const IgemmGeom& g_in, bool bf16_ops, hipStream_t st) {
+int mmdyn_igemm_ws_launch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
+                          const IgemmGeom& g_in, const IgemmPlan& p, bool bf16_ops, hipStream_t st) {
   IgemmGeom g = g_in;
   g.tap_order = g.mode == MMDYN_CONV && g.rs == 2;
   if (const char* e = lab_env("MMDYN_WS_TAPORDER")) g.tap_order = g.tap_order && e[0] != '0';      // LAB: raster order (A/B)
-  if (bf16_ops && (!g.a_b16 || !g.b_b16)) return 1;
-  if ((int64_t)g.G * g.b_group_stride * 4 >= MAX_BUFFER_BYTES) return 1;      // (grouped weights: one buffer descriptor)
-  const WsPick p = ws_pick(g.mode, g.G, g.Bg, g.Hi, g.Wi, g.Hr, g.Wr, g.Cin, g.N, g.nclasses, g.splitk, bf16_ops);
-  if (!p.bm) return 1;
   if (bf16_ops && g.f16) return ws_dispatch<2>(A, Bp, bias, C, C_act, stats, ws, g, p, st);
   if (bf16_ops) return ws_dispatch<1>(A, Bp, bias, C, C_act, stats, ws, g, p, st);
   return ws_dispatch<0>(A, Bp, bias, C, C_act, stats, ws, g, p, st);
 }
+

@@ -21,7 +21,7 @@
 //     and a second, tiny launch (igemm_wsp_fixup_kernel) sums the pieces of each split tile in piece order and runs the
 //     SAME epilogue -- deterministic, no atomics, no in-kernel inter-block hand-off (the kernel boundary is the fence);
 //   * BatchNorm partial sums are written per (tile, wave row): no cross-wave reduction, hence no block barrier in the
-//     epilogue (mmdyn_igemm_wsp_stat_tiles tells the host how many partial tiles a launch writes).
+//     epilogue (the plan's stat_tiles, wsp_counts, tells the host how many partial tiles a launch writes).
 // The ring itself (LDS-DMA pieces of 8 rows x 128 B, XOR swizzle on the DMA source address and on the fragment read,
 // counted vmcnt, ONE raw s_barrier per K-step, out-of-range offsets for padding rows) is igemm_ws.hip's.
 #include "common.h"
@@ -950,17 +950,6 @@ struct WspPick {
   int bpc;         // resident blocks per CU the grid is sized for
 };
 
-static int device_cus() {
-  static int cus[LdsOptIn::MAX_DEVICES] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= LdsOptIn::MAX_DEVICES) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 // Measured per shape against the one-tile-per-block ring kernels and the register-staged kernels, each launch alone on the
 // chip (tests/microbench/ab_wsp.py, profiles/r4/ab_wsp_per_shape.txt).  Served: fp32 (and all-16-bit) CONV / TCONV_S2P1 launches
 // with N % 128 == 0 and at least two 16-K-step tiles' worth of work per CU, and the k4 s1 p0 transposed convolution with N = 128.
@@ -1035,7 +1024,9 @@ static WspPick wsp_pick(int mode, int G, int Bg, int Hi, int Wi, int Hr, int Wr,
   return p;
 }
 
-static WspSched make_sched(const IgemmGeom& g, const WspPick& p, bool b16) {
+// The tile walk of a launch and its cut into blocks.  per == 0: the plan hooks -- the cut (K-step units per block) is chosen here;
+// per > 0: the launch hooks -- the cut of the plan.
+static WspSched make_sched(const IgemmGeom& g, const WspPick& p, bool b16, int per = 0) {
   WspSched sc{};
   sc.cin_steps = g.Cin / (b16 ? 64 : BK);
   if (g.mode == MMDYN_TCONV_S1P0) {
@@ -1053,11 +1044,14 @@ static WspSched make_sched(const IgemmGeom& g, const WspPick& p, bool b16) {
     sc.ksteps = (g.mode == MMDYN_CONV ? 16 : (g.mode == MMDYN_TCONV_S2P1 ? 4 : 1)) * sc.cin_steps;
     sc.units = sc.tiles * sc.ksteps;
   }
-  const long nblk = (long)device_cus() * p.bpc;
-  sc.per = (int)((sc.units + nblk - 1) / nblk);
-  if (const char* e = lab_env("MMDYN_WSP_UNITS_PER_BLOCK")) {      // LAB build: force the cut (kernel tests: split tiles)
-    const int v = atoi(e);
-    if (v > 0 && (sc.units + v - 1) / v <= 65535L * 16) sc.per = v;
+  sc.per = per;
+  if (!per) {
+    const long nblk = (long)device_cus() * p.bpc;
+    sc.per = (int)((sc.units + nblk - 1) / nblk);
+    if (const char* e = lab_env("MMDYN_WSP_UNITS_PER_BLOCK")) {      // LAB build: force the cut (kernel tests: split tiles)
+      const int v = atoi(e);
+      if (v > 0 && (sc.units + v - 1) / v <= 65535L * 16) sc.per = v;
+    }
   }
   sc.inv_hw = 1.0f / (float)(g.Hr * g.Wr);
   sc.inv_w = 1.0f / (float)g.Wr;
@@ -1124,23 +1118,14 @@ static int wsp_launch(const float* A, const float* Bp, const float* bias, float*
 
 template <int MODE, int B16>
 static int wsp_launch_mode(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
-                           const IgemmGeom& g, const WspPick& p, const WspSched& sc, unsigned a_bytes, unsigned b_bytes,
+                           const IgemmGeom& g, const IgemmPlan& p, const WspSched& sc, unsigned a_bytes, unsigned b_bytes,
                            hipStream_t st) {
 #ifdef MMDYN_LAB
-  if constexpr (B16 == 0) {        // LAB experiment: a four-slot ring (three K-steps in flight, 140 KB of LDS)
-    const char* e = lab_env("MMDYN_WSP_S");
-    if (e && e[0] == '4' && p.bn == 128)
-      return wsp_launch<MODE, 128, 128, 64, 32, 4, B16>(A, Bp, bias, C, C_act, stats, slabs, g, sc, a_bytes, b_bytes, st);
-  }
+  if constexpr (B16 == 0)
+    if (p.slots == 4) return wsp_launch<MODE, 128, 128, 64, 32, 4, B16>(A, Bp, bias, C, C_act, stats, slabs, g, sc, a_bytes, b_bytes, st);
 #endif
-  if constexpr (B16 == 0) {
-    // the split arithmetic runs FOUR MFMA waves of 64x64 instead of eight of 64x32: a wave then splits 64 fragment values for 96
-    // MFMAs instead of 48 for 48 (3.7 instead of 5.5 VALU operations per MFMA; one MFMA wave per SIMD): x1.06-1.09 on the launches it
-    // serves, step 5.81 -> 5.74 ms on one box (profiles/r4/step_ab_x3_persistent_wave_tile.txt).  LAB: MMDYN_X3_WSP_W64=0 = eight waves.
-    const char* e = lab_env("MMDYN_X3_WSP_W64");
-    if (g.x3 && p.bn == 128 && !(e && e[0] == '0'))
-      return wsp_launch<MODE, 128, 128, 64, 64, 3, B16>(A, Bp, bias, C, C_act, stats, slabs, g, sc, a_bytes, b_bytes, st);
-  }
+  if constexpr (B16 == 0)
+    if (p.wn == 64) return wsp_launch<MODE, 128, 128, 64, 64, 3, B16>(A, Bp, bias, C, C_act, stats, slabs, g, sc, a_bytes, b_bytes, st);
   if (p.bn == 128) return wsp_launch<MODE, 128, 128, 64, 32, 3, B16>(A, Bp, bias, C, C_act, stats, slabs, g, sc, a_bytes, b_bytes, st);
   if constexpr (MODE != MMDYN_TCONV_S1P0)
     return wsp_launch<MODE, 128, 64, 64, 32, 3, B16>(A, Bp, bias, C, C_act, stats, slabs, g, sc, a_bytes, b_bytes, st);
@@ -1149,7 +1134,7 @@ static int wsp_launch_mode(const float* A, const float* Bp, const float* bias, f
 
 template <int B16>
 static int wsp_dispatch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
-                        const IgemmGeom& g, const WspPick& p, const WspSched& sc, hipStream_t st) {
+                        const IgemmGeom& g, const IgemmPlan& p, const WspSched& sc, hipStream_t st) {
   const int esz = B16 ? 2 : 4;
   const unsigned a_bytes = (unsigned)((int64_t)g.G * g.Bg * g.Hi * g.Wi * g.Cin * esz);
   const unsigned b_bytes = (unsigned)((int64_t)(g.mode == MMDYN_DENSE ? 1 : 16) * g.N * g.Cin * esz);
@@ -1261,60 +1246,53 @@ static WspSched make_sched3(const IgemmGeom& g, const Wsp3Cfg& c) {
   return sc;
 }
 
-// geometry of a launch as the queries below know it (shape only)
-static IgemmGeom query_geom(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  IgemmGeom g{};
-  g.mode = mode;
-  g.G = G;
-  g.Bg = Bg;
-  g.Hi = Hi;
-  g.Wi = Wi;
-  g.Cin = Cin;
-  g.N = N;
-  g.Hr = Ho;
-  g.Wr = Wo;
-  g.nclasses = 1;
-  if (mode == MMDYN_TCONV_S2P1) {
-    g.Hr = Hi;
-    g.Wr = Wi;
-    g.nclasses = 4;
-  }
-  return g;
+
+// What the caller must know of a stream-K launch, beside its pick.  Partial-sum tiles: one per M-tile, parity class and wave row
+// (TCONV_S1P0: per output pixel, sample tile and wave row) -- every (block tile, wave tile) pair of this file has BM / WM = 2 wave
+// rows.  Slabs: two tile-sized pieces per block where tiles straddle the blocks' ranges, else none.
+static void wsp_counts(const IgemmGeom& g, const WspSched& sc, IgemmPlan* p) {
+  p->per = sc.per;
+  p->stat_tiles = igemm_m_tiles(g, p->bm) * 2;
+  const long nblk = (sc.units + sc.per - 1) / sc.per;
+  p->slab_floats = has_split_tiles(g, sc) ? (int)((int64_t)nblk * 2 * p->bm * p->bn) : 0;
 }
 
 }  // namespace
 
-// BatchNorm partial-sum tiles per group the persistent kernel writes for the shape (0: not served): one per M-tile, parity
-// class and wave row (TCONV_S1P0: per output pixel, sample tile and wave row)
-int mmdyn_igemm_wsp_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, bool b16) {
-  const IgemmGeom g = query_geom(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  const WspPick p = wsp_pick(mode, G, Bg, Hi, Wi, g.Hr, g.Wr, Cin, N, g.nclasses, 1, b16, 0);
-  if (!p.bm) return 0;
-  if (mode == MMDYN_TCONV_S1P0) return 64 * ceil_div(Bg, p.bm) * 2;
-  return g.nclasses * ceil_div(Bg * g.Hr * g.Wr, p.bm) * 2;        // both tiles are cut into waves of 64 x 32: two wave rows
+// bf16_ops: the launch runs on the 16-bit matrix cores; served only when BOTH operands are 16-bit in HBM.  x3: an fp32 launch in
+// the split arithmetic (the pick is the same; the 128x128 tile is then cut into other wave tiles).
+bool mmdyn_igemm_wsp_plan(const IgemmGeom& g, bool bf16_ops, bool x3, IgemmPlan* p) {
+  if (bf16_ops && (!g.a_b16 || !g.b_b16)) return false;
+  const WspPick t = wsp_pick(g.mode, g.G, g.Bg, g.Hi, g.Wi, g.Hr, g.Wr, g.Cin, g.N, g.nclasses, g.splitk, bf16_ops, g.b_group_stride);
+  if (!t.bm) return false;
+  *p = IgemmPlan{};
+  p->family = IGEMM_WSP;
+  p->bm = t.bm;
+  p->bn = t.bn;
+  p->bpc = t.bpc;
+  p->x3 = x3;
+  p->wm = 64;
+  p->wn = 32;
+  p->slots = 3;
+  if (!bf16_ops && t.bn == 128) {
+    // the split arithmetic runs FOUR MFMA waves of 64x64 instead of eight of 64x32: a wave then splits 64 fragment values for 96
+    // MFMAs instead of 48 for 48 (3.7 instead of 5.5 VALU operations per MFMA; one MFMA wave per SIMD): x1.06-1.09 on the launches it
+    // serves, step 5.81 -> 5.74 ms on one box (profiles/r4/step_ab_x3_persistent_wave_tile.txt).  LAB: MMDYN_X3_WSP_W64=0 = eight waves.
+    const char* w = lab_env("MMDYN_X3_WSP_W64");
+    const char* s = lab_env("MMDYN_WSP_S");        // LAB experiment: a four-slot ring (three K-steps in flight, 140 KB of LDS)
+    if (s && s[0] == '4') p->slots = 4;
+    else if (x3 && !(w && w[0] == '0')) p->wn = 64;
+  }
+  wsp_counts(g, make_sched(g, t, bf16_ops), p);
+  return true;
 }
 
-// bytes of slab workspace the launch needs for its split tiles (0: none, or not served)
-int64_t mmdyn_igemm_wsp_slab_bytes(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N, bool b16) {
-  const IgemmGeom g = query_geom(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  const WspPick p = wsp_pick(mode, G, Bg, Hi, Wi, g.Hr, g.Wr, Cin, N, g.nclasses, 1, b16, 0);
-  if (!p.bm) return 0;
-  const WspSched sc = make_sched(g, p, b16);
-  if (!has_split_tiles(g, sc)) return 0;
-  const long nblk = (sc.units + sc.per - 1) / sc.per;
-  return (int64_t)nblk * 2 * p.bm * p.bn * 4;
-}
-
-// bf16_ops: the launch runs on the 16-bit matrix cores; served only when BOTH operands are 16-bit in HBM
-int mmdyn_igemm_wsp_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
-                        const IgemmGeom& g_in, bool bf16_ops, hipStream_t st) {
+int mmdyn_igemm_wsp_launch(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
+                           const IgemmGeom& g_in, const IgemmPlan& p, bool bf16_ops, hipStream_t st) {
   IgemmGeom g = g_in;
   g.tap_order = g.mode == MMDYN_CONV && g.rs == 2;
   if (const char* e = lab_env("MMDYN_WS_TAPORDER")) g.tap_order = g.tap_order && e[0] != '0';
-  if (bf16_ops && (!g.a_b16 || !g.b_b16)) return 1;
-  const WspPick p = wsp_pick(g.mode, g.G, g.Bg, g.Hi, g.Wi, g.Hr, g.Wr, g.Cin, g.N, g.nclasses, g.splitk, bf16_ops, g.b_group_stride);
-  if (!p.bm) return 1;
-  const WspSched sc = make_sched(g, p, bf16_ops);
+  const WspSched sc = make_sched(g, WspPick{p.bm, p.bn, p.bpc}, bf16_ops, p.per);
 #ifdef MMDYN_LAB
   if (bf16_ops && g.f16) return wsp_dispatch<2>(A, Bp, bias, C, C_act, stats, slabs, g, p, sc, st);
   if (bf16_ops) return wsp_dispatch<1>(A, Bp, bias, C, C_act, stats, slabs, g, p, sc, st);
@@ -1322,36 +1300,30 @@ int mmdyn_igemm_wsp_try(const float* A, const float* Bp, const float* bias, floa
   return wsp_dispatch<0>(A, Bp, bias, C, C_act, stats, slabs, g, p, sc, st);
 }
 
-// The launch with both operands ARRIVING as three-plane bf16 rows (igemm_wsp3_kernel).  Returns 1 when the shape is not served.
-bool mmdyn_igemm_wsp3_serves(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  const IgemmGeom g = query_geom(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  return wsp3_pick(mode, G, Bg, Hi, Wi, g.Hr, g.Wr, Cin, N, g.nclasses, 1, 0).bm != 0;
-}
-// BatchNorm partial-sum tiles per group of a plane launch (0: not served): one per M-tile, parity class and wave row
-int mmdyn_igemm_wsp3_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  const IgemmGeom g = query_geom(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  const Wsp3Cfg c = wsp3_pick(mode, G, Bg, Hi, Wi, g.Hr, g.Wr, Cin, N, g.nclasses, 1, 0);
-  if (!c.bm) return 0;
-  if (mode == MMDYN_TCONV_S1P0) return 64 * ceil_div(Bg, c.bm) * 2;
-  return g.nclasses * ceil_div(Bg * g.Hr * g.Wr, c.bm) * 2;
-}
-int64_t mmdyn_igemm_wsp3_slab_bytes(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  const IgemmGeom g = query_geom(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N);
-  const Wsp3Cfg c = wsp3_pick(mode, G, Bg, Hi, Wi, g.Hr, g.Wr, Cin, N, g.nclasses, 1, 0);
-  if (!c.bm) return 0;
-  const WspSched sc = make_sched3(g, c);
-  if (!has_split_tiles(g, sc)) return 0;
-  const long nblk = (sc.units + sc.per - 1) / sc.per;
-  return (int64_t)nblk * 2 * c.bm * c.bn * 4;
+// The launch with both operands ARRIVING as three-plane bf16 rows (igemm_wsp3_kernel).
+bool mmdyn_igemm_wsp3_plan(const IgemmGeom& g, IgemmPlan* p) {
+  const Wsp3Cfg c = wsp3_pick(g.mode, g.G, g.Bg, g.Hi, g.Wi, g.Hr, g.Wr, g.Cin, g.N, g.nclasses, g.splitk, g.b_group_stride);
+  if (!c.bm) return false;
+  *p = IgemmPlan{};
+  p->family = IGEMM_WSP3;
+  p->bm = c.bm;
+  p->bn = c.bn;
+  p->slots = c.s;
+  p->bpc = c.bpc;
+  p->wm = c.bm / 2;
+  p->wn = c.bn == 128 ? 32 : 16;
+  // LAB, MMDYN_P3_W64=1: the 128x128 tile on FOUR MFMA waves of 64x64 (one per SIMD; 0.25 fragment reads per MFMA instead of 0.375)
+  if (const char* e = lab_env("MMDYN_P3_W64"))
+    if (e[0] == '1' && c.bn == 128 && c.bm == 128 && g.mode != MMDYN_DENSE) p->wn = 64;
+  wsp_counts(g, make_sched3(g, c), p);
+  return true;
 }
 
-int mmdyn_igemm_wsp3_try(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
-                         const IgemmGeom& g_in, hipStream_t st) {
+int mmdyn_igemm_wsp3_launch(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* slabs,
+                            const IgemmGeom& g_in, const IgemmPlan& p, hipStream_t st) {
   IgemmGeom g = g_in;
-  const Wsp3Cfg c = wsp3_pick(g.mode, g.G, g.Bg, g.Hi, g.Wi, g.Hr, g.Wr, g.Cin, g.N, g.nclasses, g.splitk, g.b_group_stride);
-  if (!c.bm) return 1;
   g.tap_order = g.mode == MMDYN_CONV && g.rs == 2;
-  const WspSched sc = make_sched3(g, c);
+  const WspSched sc = make_sched(g, WspPick{p.bm, p.bn, p.bpc}, false, p.per);
   const unsigned a_bytes = (unsigned)((int64_t)g.G * g.Bg * g.Hi * g.Wi * g.Cin * 6);
   const unsigned b_bytes = (unsigned)((int64_t)(g.mode == MMDYN_DENSE ? 1 : 16) * g.N * g.Cin * 6);
   const bf16_t* Ap = reinterpret_cast<const bf16_t*>(A);
@@ -1359,25 +1331,23 @@ int mmdyn_igemm_wsp3_try(const void* A, const void* Bp, const float* bias, float
 #define P3_GO(MODE_, BM_, BN_, WM_, WN_, S_) \
   return wsp3_launch<MODE_, BM_, BN_, WM_, WN_, S_>(Ap, Bq, bias, C, C_act, stats, slabs, g, sc, a_bytes, b_bytes, st)
 #ifdef MMDYN_LAB
-  // LAB, MMDYN_P3_W64=1: the 128x128 tile on FOUR MFMA waves of 64x64 (one per SIMD; 0.25 fragment reads per MFMA instead of 0.375)
-  if (const char* e = lab_env("MMDYN_P3_W64"))
-    if (e[0] == '1' && c.bn == 128 && c.bm == 128) {
-      if (g.mode == MMDYN_TCONV_S1P0) P3_GO(MMDYN_TCONV_S1P0, 128, 128, 64, 64, 3);
-      if (g.mode == MMDYN_CONV) P3_GO(MMDYN_CONV, 128, 128, 64, 64, 3);
-      if (g.mode == MMDYN_TCONV_S2P1) P3_GO(MMDYN_TCONV_S2P1, 128, 128, 64, 64, 3);
-    }
+  if (p.wn == 64) {
+    if (g.mode == MMDYN_TCONV_S1P0) P3_GO(MMDYN_TCONV_S1P0, 128, 128, 64, 64, 3);
+    if (g.mode == MMDYN_CONV) P3_GO(MMDYN_CONV, 128, 128, 64, 64, 3);
+    if (g.mode == MMDYN_TCONV_S2P1) P3_GO(MMDYN_TCONV_S2P1, 128, 128, 64, 64, 3);
+  }
 #endif
   if (g.mode == MMDYN_TCONV_S1P0) P3_GO(MMDYN_TCONV_S1P0, 128, 128, 64, 32, 3);
   if (g.mode == MMDYN_DENSE) P3_GO(MMDYN_DENSE, 128, 128, 64, 32, 3);
   if (g.mode == MMDYN_CONV) {
-    if (c.bn == 128) P3_GO(MMDYN_CONV, 128, 128, 64, 32, 3);
-    if (c.bm == 256) P3_GO(MMDYN_CONV, 256, 64, 128, 16, 2);
-    if (c.s == 2) P3_GO(MMDYN_CONV, 128, 64, 64, 16, 2);
+    if (p.bn == 128) P3_GO(MMDYN_CONV, 128, 128, 64, 32, 3);
+    if (p.bm == 256) P3_GO(MMDYN_CONV, 256, 64, 128, 16, 2);
+    if (p.slots == 2) P3_GO(MMDYN_CONV, 128, 64, 64, 16, 2);
     P3_GO(MMDYN_CONV, 128, 64, 64, 16, 3);
   }
-  if (c.bn == 128) P3_GO(MMDYN_TCONV_S2P1, 128, 128, 64, 32, 3);
-  if (c.bm == 256) P3_GO(MMDYN_TCONV_S2P1, 256, 64, 128, 16, 2);
-  if (c.s == 2) P3_GO(MMDYN_TCONV_S2P1, 128, 64, 64, 16, 2);
+  if (p.bn == 128) P3_GO(MMDYN_TCONV_S2P1, 128, 128, 64, 32, 3);
+  if (p.bm == 256) P3_GO(MMDYN_TCONV_S2P1, 256, 64, 128, 16, 2);
+  if (p.slots == 2) P3_GO(MMDYN_TCONV_S2P1, 128, 64, 64, 16, 2);
   P3_GO(MMDYN_TCONV_S2P1, 128, 64, 64, 16, 3);
 #undef P3_GO
 }

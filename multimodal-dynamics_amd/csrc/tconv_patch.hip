@@ -310,24 +310,13 @@ int patch_tiles(int mode, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
   return 0;
 }
 
-int patch_cus() {
-  static int cus[LdsOptIn::MAX_DEVICES] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= LdsOptIn::MAX_DEVICES) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 template <int H, int W, int CIN, int N, int TH, bool P3>
 int patch_launch(const void* A, const void* Bp, float* C, float* stats, const IgemmGeom& g, const PatchEpi& ep, hipStream_t st) {
   using K = PatchCfg<H, W, CIN, N, TH, P3>;
   static LdsOptIn lds_opt_in;                               // (~105 KB of the CU's 160 KB; plane rows: 148-158 KB)
   static LdsOptIn lds_opt_in_bwd;
   const int Bt = g.G * g.Bg;
-  const int grid = Bt * K::TILES < patch_cus() ? Bt * K::TILES : patch_cus();      // one resident block per CU, persistent
+  const int grid = Bt * K::TILES < device_cus() ? Bt * K::TILES : device_cus();      // one resident block per CU, persistent
   if (ep.bn_y) {
     if (int e = lds_opt_in_bwd.ensure((const void*)tconv_patch_kernel<H, W, CIN, N, TH, P3, true>, (int)K::SMEM)) return e;
     hipLaunchKernelGGL((tconv_patch_kernel<H, W, CIN, N, TH, P3, true>), dim3(grid), dim3(512), K::SMEM, st, A, Bp, C, stats, Bt, g.Bg,
@@ -341,9 +330,8 @@ int patch_launch(const void* A, const void* Bp, float* C, float* stats, const Ig
 }
 
 template <bool P3>
-int patch_try(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws, const IgemmGeom& g,
-              hipStream_t st) {
-  if (!patch_tiles(g.mode, g.Hi, g.Wi, g.Cin, g.Ho, g.Wo, g.N)) return 1;
+int patch_go(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws, const IgemmGeom& g,
+             hipStream_t st) {
   if (ws || g.splitk != 1) return MMDYN_ERR_SHAPE;          // (split-K is a DENSE-mode feature: the entry point has refused it)
   if (g.bn_y && g.ldc != g.N) return MMDYN_ERR_SHAPE;
   const PatchEpi ep{bias, C_act, g.act, g.bn_y, g.bn_mean, g.bn_rstd, g.bn_gamma, g.bn_beta, g.bwd_act};
@@ -362,24 +350,20 @@ bool patch_p3_enabled() {      // (LAB, MMDYN_TCONV_PATCH_P3=0: the 32-channel u
 
 }  // namespace
 
-// Number of BatchNorm partial-sum tiles per group this kernel writes (one per row tile of an image), 0 when the shape is not
-// served.
-int mmdyn_tconv_patch_stat_tiles(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  return Bg * patch_tiles(mode, Hi, Wi, Cin, Ho, Wo, N);
+// Served: the shapes of patch_tiles, on fp32 operands or (planes) on operands that arrive split (fp32x3, rows of [plane][Cin]
+// bf16).  One BatchNorm partial-sum tile per row tile of an image; no workspace.
+bool mmdyn_tconv_patch_plan(const IgemmGeom& g, bool planes, IgemmPlan* p) {
+  if (planes && !(patch_p3_enabled() && g.G > 0 && g.Bg > 0)) return false;
+  const int tiles = patch_tiles(g.mode, g.Hi, g.Wi, g.Cin, g.Ho, g.Wo, g.N);
+  if (!tiles) return false;
+  *p = IgemmPlan{};
+  p->family = IGEMM_PATCH;
+  p->planes = planes;
+  p->stat_tiles = g.Bg * tiles;
+  return true;
 }
 
-// Returns MMDYN_OK / an error code, or 1 when the launch is not served (fp32 only: the caller has checked that).
-int mmdyn_tconv_patch_try(const float* A, const float* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                          const IgemmGeom& g, hipStream_t st) {
-  return patch_try<false>(A, Bp, bias, C, C_act, stats, ws, g, st);
-}
-
-// The same shapes on operands that arrive split (fp32x3, rows of [plane][Cin] bf16): same tile count, no workspace.
-bool mmdyn_tconv_patch_p3_serves(int mode, int G, int Bg, int Hi, int Wi, int Cin, int Ho, int Wo, int N) {
-  return patch_p3_enabled() && G > 0 && Bg > 0 && patch_tiles(mode, Hi, Wi, Cin, Ho, Wo, N) > 0;
-}
-int mmdyn_tconv_patch_p3_try(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
-                             const IgemmGeom& g, hipStream_t st) {
-  if (!patch_p3_enabled()) return 1;
-  return patch_try<true>(A, Bp, bias, C, C_act, stats, ws, g, st);
+int mmdyn_tconv_patch_launch(const void* A, const void* Bp, const float* bias, float* C, float* C_act, float* stats, float* ws,
+                             const IgemmGeom& g, const IgemmPlan& p, hipStream_t st) {
+  return p.planes ? patch_go<true>(A, Bp, bias, C, C_act, stats, ws, g, st) : patch_go<false>(A, Bp, bias, C, C_act, stats, ws, g, st);
 }

@@ -1236,6 +1236,37 @@ static bool p3_enabled() {
   return !(e && e[0] == '0');
 }
 
+// both operands arrive split on a convolution-level launch: the plane-ring kernel (wgrad_p3.hip) is asked first
+static bool p3_asked(bool x3, int pre, int mode) { return x3 && pre == 3 && mode == MMDYN_CONV && p3_enabled(); }
+
+// ---- the route of this file's kernels: family and channel tile, ONE rule for wgrad_entry and the slab-count queries ----
+// (the plane ring, the LAB ring and the direct 3-channel kernel are asked before it and answer for themselves)
+enum WgradFamily {
+  WGRAD_TN,    // one tap per block (wgrad_tn_kernel), WK waves share a tile's row range
+  WGRAD_TN4,   // narrow convolution tiles: the four kw taps of a kernel row per block (wgrad_tn4_kernel, every storage type)
+  WGRAD_B16    // both operands 16-bit in HBM: the transposing-LDS-read kernel (wgrad_b16_kernel)
+};
+struct WgradRoute {
+  int family, bd, bg, wk;
+};
+// both16: D and Gt are both 16-bit in HBM (never with MMDYN_IM2COL3, whose gathered operand is the fp32 image)
+static WgradRoute wgrad_route(int mode, int Cd, int Cg, bool both16) {
+  const bool d64 = (Cd % 64 == 0), g64 = (Cg % 64 == 0);
+  const int wide = both16 ? WGRAD_B16 : WGRAD_TN;
+  if (Cd % 128 == 0 && Cg % 128 == 0) return {wide, 128, 128, 1};
+  // 128 x 64 channel layers: one 128x64 tile instead of two 64x64 ones -- the gathered operand is filled once for all 128
+  // output channels (21 instead of 16 flop per filled byte): x1.10-1.16 with twice the partial slabs (mmdyn_wgrad_chunks),
+  // profiles/r3/ab_wgrad_tile_128x64.txt
+  if (Cd % 128 == 0 && g64 && !both16 && tile_128x64()) return {WGRAD_TN, 128, 64, 1};
+  if (d64 && g64) return {wide, 64, 64, 1};
+  // narrow channel tiles of a convolution: four kw taps per block share the dense operand (measured +11 %; 64x64 tiles are
+  // faster on the one-tap kernel, so they stay there; 16-bit operands too: measured faster than the narrow b16 tiles)
+  if (mode == MMDYN_CONV) return {WGRAD_TN4, d64 ? 64 : 32, g64 ? 64 : 32, 1};
+  if (d64) return {wide, 64, 32, 2};
+  if (g64) return {wide, 32, 64, 2};
+  return {WGRAD_TN, 32, 32, 4};
+}
+
 static int wgrad_entry(const float* D, const float* Gt, float* partial, int mode, int Bt, int Hr,
                        int Wr, int Cd, int Hi, int Wi, int Cg, int stride, int offset, int chunks,
                        void* stream, bool bf16, int storage_flags = 0, int groups = 1) {
@@ -1279,8 +1310,7 @@ static int wgrad_entry(const float* D, const float* Gt, float* partial, int mode
     const int rc = mmdyn_conv3_wgrad_try(D, Gt, partial, Bt, Hr, Wr, Cd, Hi, Wi, Cg, chunks, g.d_b16 << g.f16, st);
     if (rc != 1) return rc;
   }
-  const bool d64 = (Cd % 64 == 0), g64 = (Cg % 64 == 0);
-  if (g.x3 && g.pre == 3 && mode == MMDYN_CONV && p3_enabled()) {      // both operands arrive split: the plane-ring kernel (wgrad_p3.hip)
+  if (p3_asked(g.x3, g.pre, mode)) {      // the plane-ring kernel (wgrad_p3.hip)
     const int rc = mmdyn_wgrad_p3_try(D, Gt, partial, g, Bt, st);
     if (rc != 1) return rc;
   }
@@ -1295,29 +1325,23 @@ static int wgrad_entry(const float* D, const float* Gt, float* partial, int mode
     }
   }
   if (groups > 1 && g.d_b16 && g.g_b16) return MMDYN_ERR_SHAPE;     // (grouped: the register-staged kernel below only)
-  if (bf16 && g.d_b16 && g.g_b16 && mode != MMDYN_IM2COL3) {
-    // both operands bf16 in HBM: the transposing-LDS-read kernel (two waves share a 64x32 / 32x64 tile's rows)
-    if (Cd % 128 == 0 && Cg % 128 == 0) return launch_b16<128, 128, 64, 64, 1>(D, Gt, partial, g, st);
-    if (d64 && g64) return launch_b16<64, 64, 32, 32, 1>(D, Gt, partial, g, st);
-    if (mode == MMDYN_DENSE) {           // (narrow convolution tiles stay on the four-tap kernel below: measured faster)
-      if (d64) return launch_b16<64, 32, 32, 32, 2>(D, Gt, partial, g, st);
-      if (g64) return launch_b16<32, 64, 32, 32, 2>(D, Gt, partial, g, st);
-    }
+  const WgradRoute r = wgrad_route(mode, Cd, Cg, bf16 && g.d_b16 && g.g_b16 && mode != MMDYN_IM2COL3);
+  if (r.family == WGRAD_B16) {
+    if (r.bd == 128) return launch_b16<128, 128, 64, 64, 1>(D, Gt, partial, g, st);
+    if (r.bd == 64 && r.bg == 64) return launch_b16<64, 64, 32, 32, 1>(D, Gt, partial, g, st);
+    if (r.bd == 64) return launch_b16<64, 32, 32, 32, 2>(D, Gt, partial, g, st);
+    return launch_b16<32, 64, 32, 32, 2>(D, Gt, partial, g, st);
   }
-  if (Cd % 128 == 0 && Cg % 128 == 0) return launch<128, 128, 64, 64, 1>(D, Gt, partial, g, st, bf16);
-  // 128 x 64 channel layers: one 128x64 tile instead of two 64x64 ones -- the gathered operand is filled once for all 128
-  // output channels (21 instead of 16 flop per filled byte): x1.10-1.16 with twice the partial slabs (mmdyn_wgrad_chunks),
-  // profiles/r3/ab_wgrad_tile_128x64.txt
-  if (Cd % 128 == 0 && g64 && tile_128x64()) return launch<128, 64, 64, 32, 1>(D, Gt, partial, g, st, bf16);
-  if (mode == MMDYN_CONV && !(d64 && g64)) {   // narrow channel tiles: four kw taps per block share the dense
-    if (d64) return launch4<64, 32>(D, Gt, partial, g, st, bf16);   // operand (measured +11 %; 64x64 tiles are faster
-                                                              // on the one-tap kernel, so they stay there)
-    if (g64) return launch4<32, 64>(D, Gt, partial, g, st, bf16);
+  if (r.family == WGRAD_TN4) {
+    if (r.bd == 64) return launch4<64, 32>(D, Gt, partial, g, st, bf16);
+    if (r.bg == 64) return launch4<32, 64>(D, Gt, partial, g, st, bf16);
     return launch4<32, 32>(D, Gt, partial, g, st, bf16);
   }
-  if (d64 && g64) return launch<64, 64, 32, 32, 1>(D, Gt, partial, g, st, bf16);
-  if (d64) return launch<64, 32, 32, 32, 2>(D, Gt, partial, g, st, bf16);
-  if (g64) return launch<32, 64, 32, 32, 2>(D, Gt, partial, g, st, bf16);
+  if (r.bd == 128 && r.bg == 128) return launch<128, 128, 64, 64, 1>(D, Gt, partial, g, st, bf16);
+  if (r.bd == 128) return launch<128, 64, 64, 32, 1>(D, Gt, partial, g, st, bf16);
+  if (r.bd == 64 && r.bg == 64) return launch<64, 64, 32, 32, 1>(D, Gt, partial, g, st, bf16);
+  if (r.bd == 64) return launch<64, 32, 32, 32, 2>(D, Gt, partial, g, st, bf16);
+  if (r.bg == 64) return launch<32, 64, 32, 32, 2>(D, Gt, partial, g, st, bf16);
   return launch<32, 32, 32, 32, 4>(D, Gt, partial, g, st, bf16);
 }
 
@@ -1372,24 +1396,15 @@ extern "C" int mmdyn_wgrad_tn_f16(const float* D, const float* Gt, float* partia
   return wgrad_entry(D, Gt, partial, mode, Bt, Hr, Wr, Cd, Hi, Wi, Cg, stride, offset, chunks, stream, true, 32);
 }
 
-// recommended number of partial slabs: ~768 blocks in flight, at least 128 rows per block
-// b16_storage: both operands are 16-bit in HBM (the wgrad_b16 kernels: their own tiles)
+// recommended number of partial slabs: ~768 blocks in flight, at least 128 rows per block.  The tile comes from the route.
+// b16_storage: both operands are 16-bit in HBM
 // x3: the launch may take the three-term split (flag bit 7): its tiles hold three bf16 planes in LDS, so fewer blocks fit a CU
 static int wgrad_chunks_impl(int mode, int rows, int Cd, int Cg, bool b16_storage, bool x3 = false) {
   if (Cd % 32 || Cg % 32 || rows <= 0) return MMDYN_ERR_SHAPE;
-  int bd, bg, wk;
-  if (Cd % 128 == 0 && Cg % 128 == 0) { bd = 128; bg = 128; wk = 1; }
-  else if (Cd % 128 == 0 && Cg % 64 == 0 && !b16_storage && tile_128x64()) { bd = 128; bg = 64; wk = 1; }
-  else if (Cd % 64 == 0 && Cg % 64 == 0) { bd = 64; bg = 64; wk = 1; }
-  else if (Cd % 64 == 0) { bd = 64; bg = 32; wk = 2; }
-  else if (Cg % 64 == 0) { bd = 32; bg = 64; wk = 2; }
-  else { bd = 32; bg = 32; wk = 4; }
-  const int taps = (mode == MMDYN_CONV) ? 16 : 1;
-  long tiles = (long)(Cd / bd) * (Cg / bg) * taps;
-  if (mode == MMDYN_CONV && !(Cd % 64 == 0 && Cg % 64 == 0)) {     // four-tap kernel: one block per kernel row
-    tiles = (long)(Cd / bd) * (Cg / bg) * 4;
-    wk = 1;
-  }
+  const WgradRoute r = wgrad_route(mode, Cd, Cg, b16_storage);
+  // blocks per row range: one per channel tile and tap (four-tap kernel: per kernel row)
+  long tiles = (long)(Cd / r.bd) * (Cg / r.bg) * (r.family == WGRAD_TN4 ? 4 : mode == MMDYN_CONV ? 16 : 1);
+  int wk = r.wk;
   long target = 768;      // blocks in flight (whole-step sweep after the fetch fixes: 768 beats 512 / 1024 in all three precisions)
   if (x3 && mode != MMDYN_IM2COL3) {
     // the split kernels: 61 KB of LDS per 128x128 tile = two blocks per CU, so 768 blocks would run as one and a half rounds;
@@ -1414,11 +1429,12 @@ static int wgrad_chunks_impl(int mode, int rows, int Cd, int Cg, bool b16_storag
 extern "C" int mmdyn_wgrad_chunks(int mode, int rows, int Cd, int Cg) { return wgrad_chunks_impl(mode, rows, Cd, Cg, false); }
 /* flags as mmdyn_wgrad_tn_mx: the count for the kernel those storage flags select */
 extern "C" int mmdyn_wgrad_chunks_mx(int mode, int rows, int Cd, int Cg, int flags) {
-  if ((flags & 896) == 896 && !(flags & 1) && mode == MMDYN_CONV && p3_enabled()) {     // both operands arrive split: the plane-ring kernel's cut
+  const bool x3 = (flags & 128) != 0 && !(flags & 1);
+  if (p3_asked(x3, (flags >> 8) & 3, mode)) {     // the plane-ring kernel's cut
     const int c = mmdyn_wgrad_p3_chunks(rows, Cd, Cg);
     if (c > 0) return c;
   }
-  return wgrad_chunks_impl(mode, rows, Cd, Cg, (flags & 6) == 6, (flags & 128) != 0 && !(flags & 1));
+  return wgrad_chunks_impl(mode, rows, Cd, Cg, (flags & 6) == 6, x3);
 }
 
 extern "C" int mmdyn_wgrad_reduce(const float* partial, float* canon, int chunks, int taps, int Cd, int Cg,

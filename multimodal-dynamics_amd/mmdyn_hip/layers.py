@@ -163,6 +163,14 @@ def split_operands(x, Wp, mode, G, Bg, Hi, Cin, Ho, N):
     return x, wp
 
 
+def _stat_tiles(x, Wp, mode, G, Bg, Hi, Cin, Ho, N):
+    """BatchNorm partial-sum tiles of the launch that takes these operands: as Planes (the plane launch's count), or with both
+    16-bit in HBM, or anything else."""
+    if isinstance(x, ops.Planes):
+        return ops.B.igemm_stat_tiles(mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N, planes=True)
+    return ops.B.igemm_stat_tiles(mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N, all16=ops._is16(x) and ops._is16(Wp))
+
+
 def as_planes(x, C):
     """The fp32 activation x ([rows][C], or any contiguous tensor whose rows are C channels) as an ops.Planes: one mmdyn_split_planes
     launch (for tensors whose producer cannot write planes itself)."""
@@ -179,10 +187,7 @@ def conv_like(x, Wp, mode, G, Bg, Hi, Cin, Ho, N, stride=1, offset=0, stats=Fals
     y = _new(x, Bt * Ho * Ho, N, dtype=ACT_DTYPE if out_dtype is None else out_dtype)
     st, T = None, 0
     if stats:
-        if isinstance(x, ops.Planes):                # (operands that arrive split: the plane launch's tile count)
-            T = ops.B.igemm_stat_tiles(mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N, planes=True)
-        else:
-            T = ops.B.igemm_stat_tiles(mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N, all16=ops._is16(x) and ops._is16(Wp))
+        T = _stat_tiles(x, Wp, mode, G, Bg, Hi, Cin, Ho, N)
         st = _new(x, G, T, 2, N)
     ops.B.igemm_nt(x, Wp, None, y, None, st, None, mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N, N, stride, offset,
                    ACT_NONE, 1)
@@ -396,10 +401,7 @@ def dgrad_bn_swish_backward(x, Wp, mode, G, Bg, Hi, Cin, Ho, N, stride, offset, 
         _eval_mode_check()
     if y.dtype == torch.float32 and mode != IM2COL3:
         x, Wp = split_operands(x, Wp, mode, G, Bg, Hi, Cin, Ho, N)
-    if isinstance(x, ops.Planes):
-        T = ops.B.igemm_stat_tiles(mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N, planes=True)
-    else:
-        T = ops.B.igemm_stat_tiles(mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N, all16=ops._is16(x) and ops._is16(Wp))
+    T = _stat_tiles(x, Wp, mode, G, Bg, Hi, Cin, Ho, N)
     du = torch.empty_like(y)
     partial = _new(y, G, T, 2, N)
     ops.B.igemm_nt_dgrad_bn(x, Wp, du, partial, y, mean, rstd, bn.gamma, bn.beta, mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N,

@@ -223,19 +223,23 @@ class HipBackend:
         """Flags of a launch whose two operands are both 16-bit in HBM, in the current storage mode."""
         return 1 | 2 | 16 | (32 if self.precision == "fp16s" else 0)
 
+    def _query_flags(self, all16=False, planes=False):
+        """Flag word (as mmdyn_igemm_nt_mx) under which the host queries see a launch of the current precision mode: plane
+        operands, fp32 (with bit 7 where the split is allowed), both operands 16-bit in HBM, or the 16-bit matrix cores on
+        anything else."""
+        if planes:
+            return 384
+        if self.precision == "fp32":
+            return self._x3()
+        if all16 and self.precision in ("bf16s", "fp16s"):
+            return self._all16_flags()
+        return 1
+
     def igemm_stat_tiles(self, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, all16=False, planes=False):
         """T of the per-tile BatchNorm partial sums the implicit GEMM of the current precision mode writes.  ``all16``: both
         operands of the launch are 16-bit in HBM (the convolution-level launches of the "bf16s" / "fp16s" modes); ``planes``: the
         fp32x3 launch takes its operands already split (ops.Planes)."""
-        if planes:
-            return self.lib.mmdyn_igemm_stat_tiles_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 384)
-        if self.precision == "fp32":
-            if self._x3():
-                return self.lib.mmdyn_igemm_stat_tiles_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 128)
-            return self.lib.mmdyn_igemm_stat_tiles(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N)
-        if all16 and self.precision in ("bf16s", "fp16s"):
-            return self.lib.mmdyn_igemm_stat_tiles_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, self._all16_flags())
-        return self.lib.mmdyn_igemm_stat_tiles_bf16(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N)
+        return self.lib.mmdyn_igemm_stat_tiles_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, self._query_flags(all16, planes))
 
     def colstats_tiles(self, rows_per_group):
         return self.lib.mmdyn_colstats_tiles(rows_per_group)
@@ -252,16 +256,7 @@ class HipBackend:
     # ---- GEMMs ----
     def _slabs(self, like, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, all16=False, planes=False):
         """Workspace for the pieces of the persistent ring kernel's split tiles (fp32 launches not split over K), or None."""
-        if planes:
-            n = self.lib.mmdyn_igemm_slab_floats_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 384)
-        elif self.precision == "fp32" and self._x3():
-            n = self.lib.mmdyn_igemm_slab_floats_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, 128)
-        elif self.precision == "fp32":
-            n = self.lib.mmdyn_igemm_slab_floats(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N)
-        elif all16 and self.precision in ("bf16s", "fp16s"):
-            n = self.lib.mmdyn_igemm_slab_floats_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, self._all16_flags())
-        else:
-            return None
+        n = self.lib.mmdyn_igemm_slab_floats_mx(mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N, self._query_flags(all16, planes))
         return torch.empty(n, device=like.device, dtype=torch.float32) if n > 0 else None
 
     def _mx(self, *fmts):
