@@ -649,6 +649,49 @@ typedef struct {
 } mmdyn_feed_groups;
 int mmdyn_rollout_feed(const mmdyn_feed_groups* groups, int G, const uint8_t* obs_avail, int B, void* stream);
 
+/* ---- candidate conditions: N conditions scored per row, the best one picked on the device (the reference has no such operation:
+ * with vae.py:126-165 a caller would run MVAE.forward once per candidate and take the argmin of the losses of problems.py:473-546
+ * on the host) --------------------------------------------------------------------------------------------------------------
+ * mmdyn_plan_select: the cost table and each row's winner from the row tables of the N * B (candidate, row) passes:
+ *   c[n][b]    = ((bce_rows[0][n][b] + bce_rows[1][n][b]) + pose_multiplier * mse_rows[n][b]) + kl_weight * kl_rows[n][b]
+ *                in fp64, in exactly this order, every product and every sum rounded to nearest on its own (no fused multiply-add);
+ *   cost[n][b] = (float)c[n][b];  best[b] = the n of the smallest c[n][b];  best_cost[b] = (float)c[best[b]][b].
+ * Selection rules, on the fp64 value: the smallest cost wins; equal costs: the lowest n; a NaN cost never wins; +Inf / -Inf are
+ * ordinary values (+Inf loses to every finite cost, -Inf wins).  All N costs of a row NaN: best[b] = -1, best_cost[b] = NaN, the
+ * row of best_cond is NaN (best_idx[b] = -1).
+ * bce_rows: [2][N][B] double (slot 0 = visual, 1 = tactile), may be null; mse_rows: [N][B] double or null; kl_rows: [N][B] double,
+ * required.  A table that is null enters as +0.0.  tavail (may be null): a TARGET-availability table as in
+ * mmdyn_iw_assemble_rows -- bce slot s belongs to modality s, mse_rows to modality 2; a (row, term) whose target is absent enters
+ * as +0.0 for every n and its N table entries are overwritten with 0 (so bce_rows / mse_rows are OUTPUTS for those entries and
+ * read-only elsewhere).  Candidates, candidate-major, exactly one kind (MMDYN_ERR_NULL otherwise), with the output of that kind:
+ *   cand [N * B][cd] float  -> best_cond [B][cd] float = cand[best[b] * B + b];
+ *   cand_idx [N * B] int64  -> best_idx [B] int64 = cand_idx[best[b] * B + b]  (cd is not used).
+ * cost: [N][B] float; best: [B] int; best_cost: [B] float; all OUTPUTS.  kl_weight_dev as in mmdyn_elbo_assemble.  One thread per
+ * row b walking n; no atomics: the same bits in every run.  N < 1, B < 1, cd < 1 or a misaligned table: MMDYN_ERR_SHAPE;
+ * N * B * cd >= 2^31: MMDYN_ERR_RANGE. */
+int mmdyn_plan_select(double* bce_rows, double* mse_rows, const double* kl_rows, const uint8_t* tavail, const float* cand,
+                      const int64_t* cand_idx, int cd, float* cost, int* best, float* best_cost, float* best_cond,
+                      int64_t* best_idx, int N, int B, float pose_multiplier, float kl_weight, const float* kl_weight_dev,
+                      void* stream);
+/* mmdyn_gather_best: the winner's rows out of the candidate-major outputs, for up to MMDYN_FEED_GROUPS tensors in one launch:
+ *   out[g][b][i] = f(src[g][best[b] * B + b][i]),  f(r) = logits[g] ? 1 / (1 + expf(-r)) : r,
+ * src[g]: fp32 [N * B][row_len[g]], out[g]: fp32 [B][row_len[g]].  The element scheme of mmdyn_rollout_feed (16-byte accesses where
+ * src[g] and out[g] are 16-byte aligned, element by element otherwise, any row_len; a block works on one group), so a row has the
+ * bits of mmdyn_complete_select(NULL, src[g] + (best[b] * B + b) * row_len[g], ...) on that row.  best[b] == -1 (mmdyn_plan_select:
+ * every cost NaN): the row is filled with NaN and nothing is read; an index outside [-1, N) is treated the same way -- it never
+ * causes an access out of bounds.  Rows that are not taken are not loaded and may hold NaN / Inf.  No LDS, no atomics.
+ * Checked on the host: groups, best, or src / out of a group < G, null: MMDYN_ERR_NULL; G outside [1, MMDYN_FEED_GROUPS], N < 1,
+ * B < 1, a row_len < 1, or an out[g] that overlaps best, the src of ANY group < G or the out of another group < G:
+ * MMDYN_ERR_SHAPE; N * B * row_len[g] >= 2^31: MMDYN_ERR_RANGE.
+ * The struct is read during the call only.  Both added without touching an existing signature or workspace: the revision stays 6. */
+typedef struct {
+  const float* src[MMDYN_FEED_GROUPS];    /* [N * B][row_len[g]], candidate-major: the decoder outputs of every (candidate, row) */
+  float* out[MMDYN_FEED_GROUPS];          /* [B][row_len[g]]: the winner's row of each b */
+  int row_len[MMDYN_FEED_GROUPS];
+  int logits[MMDYN_FEED_GROUPS];          /* != 0: src holds logits, out their sigmoid */
+} mmdyn_gather_groups;
+int mmdyn_gather_best(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call
  * (graph-replay safe); p/g/m/v: flat fp32 buffers of n elements; g is multiplied by grad_scale first */
@@ -793,6 +836,14 @@ int mmdyn_nhwc_to_nchw(const float* in, float* out, int B, int C, int HW, void* 
  * replaces the memset + two mmdyn_repack2d_ld launches per consumer. */
 int mmdyn_concat_condition(const float* x, const float* cond, const int64_t* cond_idx, float* out, int* bad_index, int rows,
                            int K, int ldx, int cd, int width, void* stream);
+/* The tiled join: x holds x_rows rows and out row r reads x[r % x_rows]; cond / cond_idx, out and bad_index keep one entry per out
+ * row, exactly as above.  The operand [h[r mod B] | candidate of row r | 0] of N candidate conditions per row of a batch, written
+ * without the features being repeated in memory.  rows % x_rows != 0 (or x_rows < 1): MMDYN_ERR_SHAPE; the range check covers
+ * x_rows * ldx.  The same kernels as mmdyn_concat_condition, which is this call with x_rows == rows: every property above holds
+ * (both access paths, every element of out written, the one-hot written by the kernel, a bad index served as zeros and reported).
+ * Added without touching an existing signature or workspace: the revision stays 6. */
+int mmdyn_concat_condition_tiled(const float* x, const float* cond, const int64_t* cond_idx, float* out, int* bad_index, int rows,
+                                 int x_rows, int K, int ldx, int cd, int width, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,9 @@
 //   - EVERY element of out is written (the padding too: the padded weight columns are zero, but 0 * NaN is not).
 // A streaming copy: one thread per 16 bytes of out, grid-stride, no LDS; 16-byte loads of x where K, ldx and the pointers allow,
 // an element-per-thread kernel otherwise.
+// Tiled form (mmdyn_concat_condition_tiled): x holds x_rows rows and out row r reads x[r % x_rows] -- the features of a batch joined
+// to N candidate conditions per row without the features being repeated in memory.  The same two kernels: x_rows == rows is the
+// plain join (the row index is then used as it is; the choice is uniform over the launch).
 #include "common.h"
 
 namespace {
@@ -19,18 +22,21 @@ __device__ __forceinline__ float cond_elem(const float* __restrict__ cond, int64
   return idx == (int64_t)j ? 1.f : 0.f;
 }
 
+// the row of x that out row r reads
+__device__ __forceinline__ int x_row(int r, int rows, int x_rows) { return x_rows == rows ? r : r % x_rows; }
+
 // K % 4 == 0, ldx % 4 == 0, x and out 16-byte aligned: a quad of out never straddles the x | condition border
 __global__ __launch_bounds__(256) void concat_condition_vec_kernel(const float* __restrict__ x, const float* __restrict__ cond,
                                                                    const int64_t* __restrict__ cond_idx, float* __restrict__ out,
-                                                                   int* __restrict__ bad_index, int rows, int K, int ldx, int cd,
-                                                                   int width) {
+                                                                   int* __restrict__ bad_index, int rows, int x_rows, int K, int ldx,
+                                                                   int cd, int width) {
   const int wq = width >> 2;
   const int64_t quads = (int64_t)rows * wq;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
     const int r = (int)(q / wq), c0 = 4 * (int)(q - (int64_t)r * wq);
     f32x4 v;
     if (c0 < K) {
-      v = *reinterpret_cast<const f32x4*>(x + (size_t)r * ldx + c0);
+      v = *reinterpret_cast<const f32x4*>(x + (size_t)x_row(r, rows, x_rows) * ldx + c0);
     } else if (c0 < K + cd) {
       int64_t idx = -1;
       if (cond_idx) {
@@ -52,14 +58,14 @@ __global__ __launch_bounds__(256) void concat_condition_vec_kernel(const float* 
 // any K / ldx / alignment: one element per thread
 __global__ __launch_bounds__(256) void concat_condition_elem_kernel(const float* __restrict__ x, const float* __restrict__ cond,
                                                                     const int64_t* __restrict__ cond_idx, float* __restrict__ out,
-                                                                    int* __restrict__ bad_index, int rows, int K, int ldx, int cd,
-                                                                    int width) {
+                                                                    int* __restrict__ bad_index, int rows, int x_rows, int K, int ldx,
+                                                                    int cd, int width) {
   const int64_t n = (int64_t)rows * width;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int r = (int)(i / width), c = (int)(i - (int64_t)r * width);
     float v = 0.f;
     if (c < K) {
-      v = x[(size_t)r * ldx + c];
+      v = x[(size_t)x_row(r, rows, x_rows) * ldx + c];
     } else if (c < K + cd) {
       int64_t idx = -1;
       if (cond_idx) {
@@ -79,17 +85,23 @@ __global__ __launch_bounds__(256) void concat_condition_elem_kernel(const float*
 
 #define ST ((hipStream_t)stream)
 
-extern "C" int mmdyn_concat_condition(const float* x, const float* cond, const int64_t* cond_idx, float* out, int* bad_index,
-                                      int rows, int K, int ldx, int cd, int width, void* stream) {
+extern "C" int mmdyn_concat_condition_tiled(const float* x, const float* cond, const int64_t* cond_idx, float* out, int* bad_index,
+                                            int rows, int x_rows, int K, int ldx, int cd, int width, void* stream) {
   if (!x || !out || (cond == nullptr) == (cond_idx == nullptr)) return MMDYN_ERR_NULL;          // exactly one condition source
   if (rows <= 0 || K <= 0 || ldx < K || cd <= 0 || width <= 0 || width % 32 || (int64_t)K + cd > width) return MMDYN_ERR_SHAPE;
-  if ((int64_t)rows * width >= (1LL << 31) || (int64_t)rows * ldx >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  if (x_rows <= 0 || rows % x_rows) return MMDYN_ERR_SHAPE;
+  if ((int64_t)rows * width >= (1LL << 31) || (int64_t)x_rows * ldx >= (1LL << 31)) return MMDYN_ERR_RANGE;
   const bool vec = K % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0;
   if (vec)
     hipLaunchKernelGGL(concat_condition_vec_kernel, dim3(ew_grid((int64_t)rows * width / 4)), dim3(256), 0, ST, x, cond, cond_idx,
-                       out, bad_index, rows, K, ldx, cd, width);
+                       out, bad_index, rows, x_rows, K, ldx, cd, width);
   else
     hipLaunchKernelGGL(concat_condition_elem_kernel, dim3(ew_grid((int64_t)rows * width)), dim3(256), 0, ST, x, cond, cond_idx, out,
-                       bad_index, rows, K, ldx, cd, width);
+                       bad_index, rows, x_rows, K, ldx, cd, width);
   MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_concat_condition(const float* x, const float* cond, const int64_t* cond_idx, float* out, int* bad_index,
+                                      int rows, int K, int ldx, int cd, int width, void* stream) {
+  return mmdyn_concat_condition_tiled(x, cond, cond_idx, out, bad_index, rows, rows, K, ldx, cd, width, stream);
 }

@@ -12,6 +12,11 @@
 //     A block belongs to ONE group (first_block[] is an exclusive scan of the groups' block counts, which follow their quad
 //     counts: the pose group is 7 * B floats next to 12288 * B), so the group's pointers and flags are block-uniform and the
 //     row's presence is wave-uniform wherever 256 consecutive floats lie in one row.
+//   - plan_select / gather_best: N candidate conditions per request (MVAEInference.plan).  plan_select forms the fp64 cost of
+//     every (candidate, row) from the row tables, writes the [N][B] cost table and each row's winner (index, cost, condition);
+//     gather_best copies the winner's decoder rows out of the [N * B] candidate-major outputs, for up to MMDYN_FEED_GROUPS tensors
+//     in one launch (images through sigmoid_exact, so a taken row has the bits of mmdyn_complete_select(x = null) on that row).
+//     Both read best[] from device memory: the choice never visits the host and the request sits in one captured graph.
 // Memory-bound, no LDS, no atomics, no scratch.
 #include "common.h"
 
@@ -97,6 +102,137 @@ bool overlap(const float* p, const float* q, int64_t n) {
   return q != nullptr && a < b + bytes && b < a + bytes;
 }
 
+// ---- candidate conditions: the cost table, the winner of each row, and the winner's rows ----
+
+// The cost in its one written order, ((bce_v + bce_t) + pm * mse) + klw * kl, every product and every sum rounded on its own.
+// Contraction is switched off for this function by the pragma: the device default fuses a * b + c into one v_fma_f64 / v_fmac_f64
+// (one rounding instead of two), and the HIP headers' __dadd_rn / __dmul_rn are a plain + and * that fuse all the same.  The
+// instructions keep the setting when the function is inlined: the kernel holds v_mul_f64 and v_add_f64 for this expression.
+__device__ __forceinline__ double plan_cost(double bce_v, double bce_t, double mse, double kl, double pm, double klw) {
+#pragma clang fp contract(off)
+  const double rec = bce_v + bce_t;
+  const double pose = pm * mse;
+  const double klt = klw * kl;
+  return (rec + pose) + klt;
+}
+
+// One thread per row b walks the candidates n = 0 .. N-1, so the table reads coalesce across b.  A table that is not given, and an
+// absent (row, term), enter plan_cost as +0.0 (x + 0.0 == x for every x the tables hold).  Selection on the fp64 value: smallest
+// wins, the first of equals wins, NaN never wins (every comparison with it is false), +-Inf are ordinary values.
+__global__ __launch_bounds__(256) void plan_select_kernel(double* __restrict__ bce, double* __restrict__ mse,
+                                                          const double* __restrict__ kl, const uint32_t* __restrict__ tavail,
+                                                          const float* __restrict__ cand, const int64_t* __restrict__ cand_idx, int cd,
+                                                          float* __restrict__ cost, int* __restrict__ best,
+                                                          float* __restrict__ best_cost, float* __restrict__ best_cond,
+                                                          int64_t* __restrict__ best_idx, int N, int B, float pose_multiplier,
+                                                          float kl_weight_arg, const float* __restrict__ kl_weight_dev) {
+  const float kl_weight = kl_weight_dev ? kl_weight_arg * kl_weight_dev[0] : kl_weight_arg;
+  const double pm = (double)pose_multiplier, klw = (double)kl_weight;
+  const size_t NB = (size_t)N * B;
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    const uint32_t word = tavail ? tavail[b] : ALL_PRESENT;
+    const bool has0 = has(word, 0), has1 = has(word, 1), has2 = has(word, 2);
+    double low = NAN;
+    int win = -1;
+    for (int n = 0; n < N; ++n) {
+      const size_t o = (size_t)n * B + b;
+      const double v = bce && has0 ? bce[o] : 0.0, t = bce && has1 ? bce[NB + o] : 0.0, p = mse && has2 ? mse[o] : 0.0;
+      if (bce && !has0) bce[o] = 0.0;
+      if (bce && !has1) bce[NB + o] = 0.0;
+      if (mse && !has2) mse[o] = 0.0;
+      const double c = plan_cost(v, t, p, kl[o], pm, klw);
+      cost[o] = (float)c;
+      if (c == c && (win < 0 || c < low)) {
+        low = c;
+        win = n;
+      }
+    }
+    best[b] = win;
+    best_cost[b] = (float)low;
+    if (best_idx) best_idx[b] = win < 0 ? (int64_t)-1 : cand_idx[(size_t)win * B + b];
+    if (best_cond)
+      for (int j = 0; j < cd; ++j) best_cond[(size_t)b * cd + j] = win < 0 ? NAN : cand[((size_t)win * B + b) * cd + j];
+  }
+}
+
+// out [B][row_len] = f(src[best[b] * B + b]) over the flat out array, in the element scheme of select_rows with no observed side:
+// quads [0, n4) by 16-byte stores, the elements from 4 * n4 on one by one.  The source of out element e of row b is element
+// e + best[b] * n of src (n = B * row_len); a quad inside one row loads 16 bytes where that offset keeps the alignment and four
+// floats otherwise (the same values either way).  A row whose index lies outside [0, N) is filled with NaN and reads nothing.
+__device__ __forceinline__ void gather_rows(const float* src, const int* best, float* out, int64_t n, int64_t n4, int row_len, int N,
+                                            int logits, int64_t tid, int64_t nthreads) {
+  auto taken = [&](int b) {
+    const int w = best[b];
+    return (w < 0 || w >= N) ? (int64_t)-1 : (int64_t)w * n;
+  };
+  auto value = [&](int64_t off, int64_t e) {
+    if (off < 0) return NAN;
+    const float r = src[off + e];
+    return logits ? sigmoid_exact(r) : r;
+  };
+  for (int64_t q = tid; q < n4; q += nthreads) {
+    const int64_t e0 = 4 * q;
+    const int b0 = (int)(e0 / row_len), b3 = (int)((e0 + 3) / row_len);
+    f32x4 v;
+    const int64_t off0 = taken(b0);
+    if (b0 == b3 && off0 >= 0 && ((off0 & 3) == 0)) {
+      v = *reinterpret_cast<const f32x4*>(src + off0 + e0);
+      if (logits) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = sigmoid_exact(v[k]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int b = (int)((e0 + k) / row_len);
+        v[k] = value(b == b0 ? off0 : taken(b), e0 + k);
+      }
+    }
+    *reinterpret_cast<f32x4*>(out + e0) = v;
+  }
+  for (int64_t i = 4 * n4 + tid; i < n; i += nthreads) out[i] = value(taken((int)(i / row_len)), i);
+}
+
+struct GatherArgs {
+  const float* src[MMDYN_FEED_GROUPS];
+  float* out[MMDYN_FEED_GROUPS];
+  int64_t n[MMDYN_FEED_GROUPS], n4[MMDYN_FEED_GROUPS];
+  int row_len[MMDYN_FEED_GROUPS], logits[MMDYN_FEED_GROUPS];
+  int first_block[MMDYN_FEED_GROUPS + 1];
+};
+
+__global__ __launch_bounds__(256) void gather_best_kernel(const GatherArgs a, const int* __restrict__ best, int G, int N) {
+  int g = 0;
+#pragma unroll
+  for (int k = 1; k < MMDYN_FEED_GROUPS; ++k)
+    if (k < G && (int)blockIdx.x >= a.first_block[k]) g = k;
+  gather_rows(a.src[g], best, a.out[g], a.n[g], a.n4[g], a.row_len[g], N, a.logits[g],
+              (int64_t)((int)blockIdx.x - a.first_block[g]) * blockDim.x + threadIdx.x,
+              (int64_t)(a.first_block[g + 1] - a.first_block[g]) * blockDim.x);
+}
+
+bool ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
+}
+
+// The grid of a launch whose blocks belong to one group each: every group at least one block; past the element-wise cap the groups
+// shrink in proportion to their work (work[g]: blocks of one item per thread).  first_block[g] for g <= MMDYN_FEED_GROUPS.
+int split_blocks(const int64_t* work, int G, int* first_block) {
+  int64_t total = 0;
+  for (int g = 0; g < G; ++g) total += work[g];
+  const int cap = ew_grid_cap();
+  int blocks = 0;
+  for (int g = 0; g < G; ++g) {
+    int64_t nb = total > cap ? work[g] * cap / total : work[g];
+    if (nb < 1) nb = 1;
+    first_block[g] = blocks;
+    blocks += (int)nb;
+  }
+  for (int g = G; g <= MMDYN_FEED_GROUPS; ++g) first_block[g] = blocks;
+  return blocks;
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -119,7 +255,7 @@ extern "C" int mmdyn_rollout_feed(const mmdyn_feed_groups* groups, int G, const 
   if (!groups) return MMDYN_ERR_NULL;
   if (G < 1 || G > MMDYN_FEED_GROUPS || B < 1 || ((uintptr_t)obs_avail & 3)) return MMDYN_ERR_SHAPE;
   FeedArgs a{};
-  int64_t work[MMDYN_FEED_GROUPS], total = 0;
+  int64_t work[MMDYN_FEED_GROUPS];
   for (int g = 0; g < G; ++g) {
     if (!groups->recon[g] || !groups->out[g]) return MMDYN_ERR_NULL;
     if (groups->row_len[g] < 1 || groups->column[g] < 0 || groups->column[g] >= MMDYN_MAX_EXPERTS) return MMDYN_ERR_SHAPE;
@@ -137,18 +273,58 @@ extern "C" int mmdyn_rollout_feed(const mmdyn_feed_groups* groups, int G, const 
     a.logits[g] = groups->logits[g];
     a.column[g] = groups->column[g];
     work[g] = ceil_div64(a.n4[g] ? a.n4[g] : n, 256);           // blocks of one item per thread
-    total += work[g];
   }
-  // every group at least one block; past the element-wise cap the groups shrink in proportion to their work
-  const int cap = ew_grid_cap();
-  int blocks = 0;
-  for (int g = 0; g < G; ++g) {
-    int64_t nb = total > cap ? work[g] * cap / total : work[g];
-    if (nb < 1) nb = 1;
-    a.first_block[g] = blocks;
-    blocks += (int)nb;
-  }
-  for (int g = G; g <= MMDYN_FEED_GROUPS; ++g) a.first_block[g] = blocks;
+  const int blocks = split_blocks(work, G, a.first_block);
   hipLaunchKernelGGL(rollout_feed_kernel, dim3(blocks), dim3(256), 0, ST, a, reinterpret_cast<const uint32_t*>(obs_avail), G);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_plan_select(double* bce_rows, double* mse_rows, const double* kl_rows, const uint8_t* tavail, const float* cand,
+                                 const int64_t* cand_idx, int cd, float* cost, int* best, float* best_cost, float* best_cond,
+                                 int64_t* best_idx, int N, int B, float pose_multiplier, float kl_weight, const float* kl_weight_dev,
+                                 void* stream) {
+  if (!kl_rows || !cost || !best || !best_cost) return MMDYN_ERR_NULL;
+  // exactly one kind of candidates, and the winner's condition in that kind
+  if ((cand == nullptr) == (cand_idx == nullptr) || (cand != nullptr) != (best_cond != nullptr) ||
+      (cand_idx != nullptr) != (best_idx != nullptr))
+    return MMDYN_ERR_NULL;
+  if (N < 1 || B < 1 || cd < 1 || ((uintptr_t)tavail & 3)) return MMDYN_ERR_SHAPE;
+  if ((int64_t)N * B * (cand ? cd : 1) >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  hipLaunchKernelGGL(plan_select_kernel, dim3(ew_grid(B)), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows,
+                     reinterpret_cast<const uint32_t*>(tavail), cand, cand_idx, cd, cost, best, best_cost, best_cond, best_idx, N, B,
+                     pose_multiplier, kl_weight, kl_weight_dev);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_gather_best(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, void* stream) {
+  if (!groups || !best) return MMDYN_ERR_NULL;
+  if (G < 1 || G > MMDYN_FEED_GROUPS || N < 1 || B < 1) return MMDYN_ERR_SHAPE;
+  GatherArgs a{};
+  int64_t work[MMDYN_FEED_GROUPS];
+  for (int g = 0; g < G; ++g) {
+    if (!groups->src[g] || !groups->out[g]) return MMDYN_ERR_NULL;
+    if (groups->row_len[g] < 1) return MMDYN_ERR_SHAPE;
+    const int64_t n = (int64_t)B * groups->row_len[g];
+    if (n * N >= (1LL << 31)) return MMDYN_ERR_RANGE;
+    const bool vec = (((uintptr_t)groups->src[g] | (uintptr_t)groups->out[g]) & 15) == 0;
+    a.src[g] = groups->src[g];
+    a.out[g] = groups->out[g];
+    a.n[g] = n;
+    a.n4[g] = vec ? n / 4 : 0;
+    a.row_len[g] = groups->row_len[g];
+    a.logits[g] = groups->logits[g];
+    work[g] = ceil_div64(a.n4[g] ? a.n4[g] : n, 256);
+  }
+  // the winner's rows of a group are written while other blocks read the indices and the candidates' rows of EVERY group and
+  // write the other groups' rows: an out[g] may touch none of them
+  for (int g = 0; g < G; ++g) {
+    if (ranges_overlap(a.out[g], a.n[g] * 4, best, (int64_t)B * 4)) return MMDYN_ERR_SHAPE;
+    for (int h = 0; h < G; ++h)
+      if (ranges_overlap(a.out[g], a.n[g] * 4, a.src[h], a.n[h] * N * 4) ||
+          (h != g && ranges_overlap(a.out[g], a.n[g] * 4, a.out[h], a.n[h] * 4)))
+        return MMDYN_ERR_SHAPE;
+  }
+  const int blocks = split_blocks(work, G, a.first_block);
+  hipLaunchKernelGGL(gather_best_kernel, dim3(blocks), dim3(256), 0, ST, a, best, G, N);
   MMDYN_LAUNCH_CHECK();
 }

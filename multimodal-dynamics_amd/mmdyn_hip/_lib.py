@@ -29,6 +29,11 @@ class FeedGroups(ctypes.Structure):
     _fields_ = [("recon", _P * 4), ("obs", _P * 4), ("out", _P * 4), ("row_len", _I * 4), ("logits", _I * 4), ("column", _I * 4)]
 
 
+class GatherGroups(ctypes.Structure):
+    """mmdyn_gather_groups (include/mmdyn_hip.h)."""
+    _fields_ = [("src", _P * 4), ("out", _P * 4), ("row_len", _I * 4), ("logits", _I * 4)]
+
+
 MAX_PASSES = 8
 MAX_EXPERTS = 4
 FEED_GROUPS = 4           # MMDYN_FEED_GROUPS
@@ -144,6 +149,9 @@ _SIGNATURES = {
     "mmdyn_iw_latent": "pp" + "i" + "ppp" + "iii" + "p",
     "mmdyn_iw_assemble_rows": "ppppppp" + "iii" + "ff" + "pp",
     "mmdyn_rollout_feed": "p" + "i" + "p" + "i" + "p",
+    "mmdyn_concat_condition_tiled": "ppppp" + "iiiiii" + "p",
+    "mmdyn_plan_select": "pppppp" + "i" + "ppppp" + "ii" + "ff" + "pp",
+    "mmdyn_gather_best": "p" + "i" + "p" + "ii" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

@@ -1341,7 +1341,9 @@ class MVAEInference:
     ``inference`` takes ``c``.  The condition is joined to the 512 features in front of each image encoder's heads and to the
     latent in front of each image decoder by one mmdyn_concat_condition launch per consumer (four for a joint request); the
     packed head / up-sampling weights carry the condition columns, zero-padded to the GEMM's K-step.  A categorical model takes
-    class indices; its one-hot rows are written by the join kernel.  :meth:`bad_condition` reports an index out of range."""
+    class indices; its one-hot rows are written by the join kernel.  :meth:`bad_condition` reports an index out of range.
+    :meth:`plan` asks the inverse question: N candidate conditions per row are scored against a goal state and the best one is
+    picked on the device, in one graph whose launch count does not grow with N (up to 8 candidates)."""
 
     def __init__(self, model, precision="fp32x3", use_graph=True, seed=0):
         from .models.vae import NoiseSource
@@ -1450,10 +1452,10 @@ class MVAEInference:
         synchronisation, which :meth:`forward` / :meth:`score` / :meth:`inference` do not make on their own."""
         return bool(self._bad is not None and int(self._bad.item()))
 
-    def _encode(self, key, x, cond=None):
+    def _encode(self, key, x, cond=None, x_rows=None):
         h, _ = layers.run(layers.encoder_trunk_forward_steps(self.P[key], self.buf[key], x, packed=self.pk[key],
                                                              training=False))
-        return layers.heads_forward(self.P[key], h, self.pk[key[0] + "h"], cond=cond)[0]
+        return layers.heads_forward(self.P[key], h, self.pk[key[0] + "h"], cond=cond, x_rows=x_rows)[0]
 
     def _forward(self, visual, tactile, pose, cond=None, avail=None, sample=True):
         with self._index_scope():
@@ -1466,17 +1468,19 @@ class MVAEInference:
         mu, lv, z = self._poe(heads, avail, self._draw_latent(B) if sample else self._zero_latent(B), B, ref.device)
         return self._decode(z, cond) + (mu, lv)
 
-    def _heads(self, visual, tactile, pose, cond):
-        """The fused (means | log_var) head outputs [B][2L] of the modalities given, None for the others."""
+    def _heads(self, visual, tactile, pose, cond, x_rows=None):
+        """The fused (means | log_var) head outputs [B][2L] of the modalities given, None for the others.  ``x_rows`` = B with
+        ``cond`` holding N * B candidate rows: the trunks run on the B rows, the image heads on the N * B rows [h[r % B] | cond[r]]
+        (the pose heads take no condition and stay [B][2L])."""
         LN = self.lanes
         heads = [None, None, None]
         LN.fork()
         if visual is not None:
             with LN.lane(0):
-                heads[0] = self._encode("ve", visual, cond)
+                heads[0] = self._encode("ve", visual, cond, x_rows)
         if tactile is not None:
             with LN.lane(1):
-                heads[1] = self._encode("te", tactile, cond)
+                heads[1] = self._encode("te", tactile, cond, x_rows)
         if pose is not None and self.use_pose:
             hp, _ = layers.pose_encoder_trunk_forward(self.P["pe"], pose)
             heads[2] = layers.heads_forward(self.P["pe"], hp, self.pk["ph"])[0]
@@ -1689,6 +1693,37 @@ class MVAEInference:
                 "bce_tactile": tab[1] if tt is not None else None, "mse_pose": tab[2] if tp is not None else None, "kl": kl[0],
                 "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
 
+    def _targets(self, what, given, B):
+        """``targets`` of :meth:`score` / ``goal`` of :meth:`plan`: [visual | None, tactile | None, pose | None] -> three contiguous
+        tensors / None (the pose dropped for a model without one); ValueError for an entry that does not match the batch."""
+        tg = [None if t is None else t.contiguous() for t in (list(given) + [None] * 3)[:3]]
+        if not self.use_pose:
+            tg[2] = None
+        for t, shape in zip(tg, ((B, 3), (B, 3), (B, 7))):
+            if t is not None and tuple(t.shape[:2]) != shape:
+                raise ValueError(f"{what} {tuple(t.shape)} does not match the batch of {B}")
+        return tg
+
+    @staticmethod
+    def _loss_mask(loss_mask, pose_term, B, who, what):
+        """The request's loss mask as fp32 [B][1 or 3][H][W] (None stays None); ValueError next to a pose term or for a wrong shape."""
+        if loss_mask is None:
+            return None
+        if pose_term:
+            raise ValueError(f"loss_mask is image-shaped and cannot multiply the (B, 7) pose term ({who} without a pose {what})")
+        if loss_mask.dim() == 3:
+            loss_mask = loss_mask.unsqueeze(1)
+        if loss_mask.dim() != 4 or loss_mask.shape[0] != B or loss_mask.shape[1] not in (1, 3):
+            raise ValueError(f"loss_mask {tuple(loss_mask.shape)} is not [B={B}][1 or 3][H][W]")
+        return loss_mask.to(torch.float32).contiguous()
+
+    def _set_weights(self, kl_weight, pose_multiplier):
+        """The KL weight into device memory (one captured graph serves every weight) and the pose multiplier of the request."""
+        if getattr(self, "_klw", None) is None:
+            self._klw = torch.zeros(1, device=self.dev)
+        self._klw.fill_(float(kl_weight))
+        self._pose_multiplier = float(pose_multiplier)
+
     @torch.no_grad()
     def score(self, x, pose=None, targets=None, loss_mask=None, kl_weight=1.0, pose_multiplier=1000.0, condition=None,
               available=None, target_available=None, samples=None):
@@ -1737,24 +1772,9 @@ class MVAEInference:
                                  f"elements, past 2^31; the largest samples for B = {B} is {((1 << 31) - 1) // (B * per_row)}")
         cond = self._condition(condition, B)
         self_target = targets is None
-        tg = [None] * 3 if self_target else [c(t) for t in (list(targets) + [None] * 3)[:3]]
-        if not self.use_pose:
-            tg[2] = None
-        for t, shape in zip(tg, ((B, 3), (B, 3), (B, 7))):
-            if t is not None and tuple(t.shape[:2]) != shape:
-                raise ValueError(f"target {tuple(t.shape)} does not match the batch of {B}")
-        if loss_mask is not None:
-            if (ins[2] is not None) if self_target else (tg[2] is not None):
-                raise ValueError("loss_mask is image-shaped and cannot multiply the (B, 7) pose term (score without a pose target)")
-            if loss_mask.dim() == 3:
-                loss_mask = loss_mask.unsqueeze(1)
-            if loss_mask.dim() != 4 or loss_mask.shape[0] != B or loss_mask.shape[1] not in (1, 3):
-                raise ValueError(f"loss_mask {tuple(loss_mask.shape)} is not [B={B}][1 or 3][H][W]")
-            loss_mask = loss_mask.to(torch.float32).contiguous()
-        if getattr(self, "_klw", None) is None:
-            self._klw = torch.zeros(1, device=self.dev)         # read from device memory: one captured graph serves every weight
-        self._klw.fill_(float(kl_weight))
-        self._pose_multiplier = float(pose_multiplier)
+        tg = [None] * 3 if self_target else self._targets("target", targets, B)
+        loss_mask = self._loss_mask(loss_mask, (ins[2] is not None) if self_target else (tg[2] is not None), B, "score", "target")
+        self._set_weights(kl_weight, pose_multiplier)
         args = ins + tg + [loss_mask]
         key = ("score", self_target, self._pose_multiplier) + tuple(None if t is None else tuple(t.shape) for t in args)
         key, args = key + (self._cond_key(cond),), args + [cond]
@@ -1804,6 +1824,142 @@ class MVAEInference:
         key = ("complete", sample) + tuple(None if t is None else tuple(t.shape) for t in ins) + \
             (self._cond_key(cond), None if avail is None else ("avail",) + tuple(avail.shape))
         return self._run(key, lambda *a: self._complete(sample, *a), None, ins + [cond, avail])
+
+    def _candidates(self, candidates, B):
+        """The request's candidate conditions laid out candidate-major for the kernels: (fp32 [N * B][condition_dim], or int64
+        [N * B] for a categorical model; N; whether they were given per row).  A few torch ops on a tiny tensor, before the captured
+        region; the values are not looked at."""
+        cd = self.condition_dim
+        if self.categorical:
+            if candidates is None:
+                candidates = torch.arange(cd)
+            from .models.vae import _INDEX_DTYPES
+            if not torch.is_tensor(candidates) or candidates.dtype not in _INDEX_DTYPES:
+                raise ValueError("categorical candidates are class indices of an integer dtype, [N] or [B, N]; got "
+                                 f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
+            per_row = candidates.dim() == 2
+            if candidates.dim() not in (1, 2) or (per_row and candidates.shape[0] != B):
+                raise ValueError(f"categorical candidates are [N] (shared) or [B={B}, N] (per row), got {tuple(candidates.shape)}")
+            N = candidates.shape[-1]
+            c = candidates.detach().to(device=self.dev, dtype=torch.int64)
+            rows = (c.t() if per_row else c.unsqueeze(1).expand(N, B)).reshape(N * B)
+        else:
+            if not torch.is_tensor(candidates) or not candidates.dtype.is_floating_point:
+                raise ValueError(f"real-valued candidates are a floating-point tensor [N, {cd}] or [B, N, {cd}], got "
+                                 f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
+            per_row = candidates.dim() == 3
+            if candidates.dim() not in (2, 3) or candidates.shape[-1] != cd or (per_row and candidates.shape[0] != B):
+                raise ValueError(f"real-valued candidates are [N, {cd}] (shared) or [B={B}, N, {cd}] (per row), got "
+                                 f"{tuple(candidates.shape)}")
+            N = candidates.shape[-2]
+            c = candidates.detach().to(device=self.dev, dtype=torch.float32)
+            rows = (c.transpose(0, 1) if per_row else c.unsqueeze(1).expand(N, B, cd)).reshape(N * B, cd)
+        if N < 1:
+            raise ValueError("plan needs at least one candidate condition (N >= 1)")
+        return rows.contiguous(), N, per_row
+
+    def _plan_candidates(self, N, sample, visual, tactile, pose, gv, gt, gp, mask, cand, avail, tavail):
+        """The encoder trunks (and the pose heads) ONCE on the B rows; the image heads, the PoE launch and the decoders on the N * B
+        (candidate, row) rows, candidate-major; the row kernels with G = N passes against the one goal (slots 0..N-1 of [N][B]
+        tables, ops.ROW_GROUPS_MAX passes per launch); one plan_select and one gather_best launch.  Tables: fp64 [3][N][B] =
+        (visual, tactile, pose), zeroed by one fill that a captured graph replays."""
+        plan_select, gather_best = ops.backend_op("plan_select"), ops.backend_op("gather_best")
+        ops.backend_op("concat_condition_tiled")        # (a backend without the join: an error before anything is launched)
+        with self._index_scope():
+            ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
+            B, L, dev = ref.shape[0], self.L, ref.device
+            heads = self._heads(visual, tactile, pose, cand, x_rows=B)
+            if heads[2] is not None:
+                heads[2] = heads[2].repeat(N, 1)
+            eps = (self._draw_latent(B) if sample else self._zero_latent(B)).repeat(N, 1)       # one draw per row, shared by its candidates
+            mu, lv, z = self._poe(heads, None if avail is None else avail.repeat(N, 1), eps, N * B, dev)
+            v, t, pr = self._decode(z, cand)
+        tab = torch.zeros(3, N, B, dtype=torch.float64, device=dev)
+        kl = torch.empty(N, B, dtype=torch.float64, device=dev)
+        chw, hw = v[0].numel(), v[0, 0].numel()
+        mc = 1 if mask is None else mask.shape[1]
+        for g0 in range(0, N, ops.ROW_GROUPS_MAX):
+            slots = list(range(g0, min(N, g0 + ops.ROW_GROUPS_MAX)))
+            rows_of = slice(g0 * B, (slots[-1] + 1) * B)
+            for slot, (lg, tg) in enumerate(((v, gv), (t, gt))):
+                if tg is not None:
+                    ops.B.bce_logits_rows_groups(lg[rows_of], tg, tab[slot], slots, B, chw, mask=mask, hw=hw, mask_channels=mc)
+            if gp is not None:
+                ops.B.mse_rows_groups(pr[rows_of], gp, tab[2], slots, B, gp.shape[1])
+        ops.B.kl_rows(mu, lv, kl.view(1, N * B), 1, N * B, L)
+        cost, best, best_cost = torch.empty(N, B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev)
+        best_cond = torch.empty((B,) + tuple(cand.shape[1:]), dtype=cand.dtype, device=dev)
+        plan_select(tab[:2] if gv is not None or gt is not None else None, tab[2] if gp is not None else None, kl, tavail, cand,
+                    cost, best, best_cost, best_cond, N, B, self._pose_multiplier, 1.0, self._klw)
+        groups = [{"src": v, "out": torch.empty((B,) + tuple(v.shape[1:]), device=dev), "logits": True},
+                  {"src": t, "out": torch.empty((B,) + tuple(t.shape[1:]), device=dev), "logits": True}]
+        if self.use_pose:
+            groups.append({"src": pr, "out": torch.empty(B, pr.shape[1], device=dev), "logits": False})
+        gather_best(groups, best, N, B)
+        return {"cost": cost, "best": best, "best_cost": best_cost, "best_condition": best_cond,
+                "prediction": [g["out"] for g in groups] + ([] if self.use_pose else [None]),
+                "bce_visual": tab[0] if gv is not None else None, "bce_tactile": tab[1] if gt is not None else None,
+                "mse_pose": tab[2] if gp is not None else None, "kl": kl, "means": mu.view(N, B, L), "log_var": lv.view(N, B, L),
+                "recon_x": [v, t] + ([pr] if self.use_pose else [])}
+
+    @torch.no_grad()
+    def plan(self, x, pose=None, goal=None, candidates=None, loss_mask=None, kl_weight=0.0, pose_multiplier=1000.0, available=None,
+             goal_available=None, sample=False):
+        """The inverse question of a conditional model: given the state ``x`` (+ ``pose``, ``available``: as in :meth:`forward`)
+        and a ``goal`` state, which of N candidate conditions gets there?  Every candidate is scored against the goal and the best
+        one is picked on the device, in ONE captured graph: the encoder trunks run once on the B rows, the image heads, the PoE
+        launch and the decoders on the N * B (candidate, row) rows, and the launch count does not depend on N up to
+        MMDYN_BCE_GROUPS_MAX = 8 candidates (beyond: one more launch per term and 8 candidates).
+
+        ``goal`` = [visual | None, tactile | None, pose | None] with at least one entry, shapes as the targets of :meth:`score`;
+        ``goal_available`` / ``loss_mask``: as ``target_available`` / ``loss_mask`` there.  ``candidates``: fp [N, condition_dim]
+        (shared by every row) or [B, N, condition_dim] (per row); for a categorical model class indices of any integer dtype, [N] or
+        [B, N], None = every class 0 .. condition_dim-1.  They are a static input of the graph: the key carries N and the kind, not
+        the values.  An index outside [0, condition_dim) is served as an all-zero block and reported by :meth:`bad_condition`.
+        ``sample=False``: z = the posterior mean of each (candidate, row), deterministic; ``sample=True``: ONE [B, L] draw from the
+        engine's Philox stream, shared by the N candidates of a row (common random numbers: candidates differ only through the
+        condition).
+
+        cost[n][b] = bce_visual + bce_tactile + pose_multiplier * mse_pose + kl_weight * kl of candidate n's prediction for row b
+        against the goal, in fp64 in that order; a term without a goal, and an absent (row, term) under ``goal_available``, is left
+        out (its table entries are 0).  The smallest cost wins, ties go to the lowest n, a NaN cost never wins, +-Inf are ordinary
+        values; all N costs NaN: best = -1, best_cost = NaN, the row's best_condition and prediction NaN (-1 for a categorical
+        model's best_condition).  The KL weight is read from device memory: one graph serves every weight.
+
+        Returns a dict of the graph's static outputs (copy what must survive the next call of the same shapes): ``cost`` fp32
+        [N, B]; ``best`` int32 [B]; ``best_cost`` fp32 [B]; ``best_condition`` fp32 [B, condition_dim] (categorical: int64 [B]);
+        ``prediction`` = [visual, tactile, pose | None], the winner's next state [B, ...] -- images in image space (sigmoid), the
+        pose plain, what :meth:`rollout` / :meth:`complete` would feed on; ``bce_visual`` / ``bce_tactile`` / ``mse_pose`` (fp64
+        [N, B], None without a goal), ``kl`` (fp64 [N, B]); ``means`` / ``log_var`` [N, B, L]; ``recon_x``: the logits of the N * B
+        rows, candidate-major.  Nothing synchronises.  ValueError: an unconditional model, no goal, N < 1, wrong shapes or dtypes,
+        or N * B rows of the largest decoder activation reaching 2^31 elements."""
+        if not self.conditional:
+            raise ValueError("candidate conditions were passed to an unconditional model")
+        visual, tactile = x
+        c = lambda t: None if t is None else t.contiguous()
+        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
+        if all(t is None for t in ins) and available is None:
+            raise ValueError("plan needs at least one modality")
+        B = self._batch_of(ins, available)
+        cand, N, per_row = self._candidates(candidates, B)
+        per = 32 * (self.model.visual_decoder.image_size // 2) ** 2
+        if N * B * per >= 1 << 31:
+            raise ValueError(f"candidates = {N} conditions of B = {B} rows make a decoder activation of {N * B} x {per} "
+                             f"elements, past 2^31; the largest N for B = {B} is {((1 << 31) - 1) // (B * per)}")
+        if not isinstance(goal, (list, tuple)) or len(goal) > 3:
+            raise ValueError("goal must be a list [visual | None, tactile | None, pose | None]")
+        tg = self._targets("goal", goal, B)
+        if all(t is None for t in tg):
+            raise ValueError("plan needs a goal: at least one of [visual, tactile, pose]")
+        loss_mask = self._loss_mask(loss_mask, tg[2] is not None, B, "plan", "goal")
+        self._set_weights(kl_weight, pose_multiplier)
+        sample = bool(sample)
+        avail, tavail = self._availability(available, B), self._availability(goal_available, B)
+        args = ins + tg + [loss_mask, cand, avail, tavail]
+        key = ("plan",) + tuple(None if t is None else tuple(t.shape) for t in ins + tg + [loss_mask]) + \
+            ("index" if self.categorical else "real", ("candidates", N, per_row), sample, self._pose_multiplier) + \
+            tuple(None if t is None else ("avail",) + tuple(t.shape) for t in (avail, tavail))
+        return self._run(key, lambda *a: self._plan_candidates(N, sample, *a), None, args)
 
     def _rollout(self, T, sample, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
         """T forwards in a row, each followed by ONE feed launch that writes the next state into its trajectory slot, where the
@@ -1935,10 +2091,7 @@ class MVAEInference:
         oav = self._step_availability("observed_available", observed_available, T, B)
         tg = self._step_tensors("targets", targets, T, B)
         tav = self._step_availability("target_available", target_available, T, B)
-        if getattr(self, "_klw", None) is None:
-            self._klw = torch.zeros(1, device=self.dev)         # read from device memory: one captured graph serves every weight
-        self._klw.fill_(float(kl_weight))
-        self._pose_multiplier = float(pose_multiplier)
+        self._set_weights(kl_weight, pose_multiplier)
         avail = self._availability(available, B)
         args = ins + [cond, avail] + obs + [oav] + tg + [tav]
         key = ("rollout", T, sample, self._pose_multiplier, per_step_cond, None if cond is None else self._cond_key(cond)) + \

@@ -524,16 +524,25 @@ def repeat_condition(cond, n):
     return cond.repeat(n) if is_index_condition(cond) else cond.repeat(n, 1)
 
 
-def concat_condition(x, cond, width, cd=None):
+def concat_condition(x, cond, width, cd=None, x_rows=None):
     """[x | cond | 0] as one [rows, width] matrix (width = K padded to the MFMA K-step): the reference's
     torch.cat((x, c.float()), dim=-1) of the conditional models (vae.py:231-237, 286-291).  ``cond``: fp32 [rows, cd], or int64
     class indices [rows] of a categorical model (``cd`` = condition_dim: the one-hot of vae.py:337-344 is written by the kernel).
     One launch (mmdyn_concat_condition) where the backend offers it, a zero fill and two block copies otherwise.  No gradient
-    flows to the condition: the callers' backward drops the condition columns of the operand's gradient."""
+    flows to the condition: the callers' backward drops the condition columns of the operand's gradient.
+    ``x_rows`` (None: everything above): x holds x_rows rows and ``cond`` a multiple of them; out row r = [x[r % x_rows] | condition
+    of row r | 0], one launch of the backend's concat_condition_tiled (mmdyn_concat_condition_tiled; forward only)."""
     rows, K = x.shape
     index = is_index_condition(cond)
     if not index:
         cd = cond.shape[1]
+    if x_rows is not None:
+        if rows != x_rows:
+            raise ValueError(f"concat_condition: x holds {rows} rows, x_rows = {x_rows}")
+        out = _new(x, cond.shape[0], width)
+        ops.backend_op("concat_condition_tiled")(x, cond if index else cond.to(torch.float32).contiguous(), out, K, cd, x_rows,
+                                                 _BAD_INDEX if index else None)
+        return out
     if hasattr(ops.B, "concat_condition"):
         out = _new(x, rows, width)
         ops.B.concat_condition(x, cond if index else cond.to(torch.float32).contiguous(), out, K, cd, _BAD_INDEX if index else None)
@@ -1129,15 +1138,16 @@ def decoder_backward_steps(P, c, dlogits, grads, need_dz=True, defer=None, need=
 # ------------------------------------------------------------------------------------------------
 # fused heads (linear_means | linear_log_var) and the pose MLPs
 # ------------------------------------------------------------------------------------------------
-def heads_forward(P, hd, packed=None, cond=None):
+def heads_forward(P, hd, packed=None, cond=None, x_rows=None):
     """hd: [rows, 512] (+ cond [rows, cd] for the conditional models) -> out [rows, 2L]: columns [0,L) = means,
-    [L,2L) = log-variances."""
+    [L,2L) = log-variances.  ``x_rows`` (with ``cond``): hd holds x_rows rows and cond N * x_rows; the heads run on the N * x_rows
+    rows [hd[r % x_rows] | cond[r]] (the tiled join, forward only)."""
     L, K = P["linear_means.weight"].shape
     Kp = _pad32(K)
     pk = packed if packed is not None else pack_now(heads_pack_specs(P))
     K0 = hd.shape[1]                                   # width of the features proper (512 for the image encoders)
     if cond is not None or Kp != K0:
-        hd = concat_condition(hd, cond, Kp, K - K0)
+        hd = concat_condition(hd, cond, Kp, K - K0, x_rows)
     out, _ = dense(hd, pk["Wh"], pk["bh"], hd.shape[0], Kp, 2 * L)
     return out, {"hd": hd, "pk": pk, "L": L, "K": K, "Kp": Kp, "K0": K0}
 

@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import PassExperts, FeedGroups, MAX_PASSES, MAX_EXPERTS, FEED_GROUPS, check
+from ._lib import PassExperts, FeedGroups, GatherGroups, MAX_PASSES, MAX_EXPERTS, FEED_GROUPS, check
 
 ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
 DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0 = 0, 1, 2, 3, 4
@@ -484,17 +484,34 @@ class HipBackend:
         stride (any row stride >= K); ``cond``: fp32 [rows][cd] (real-valued) or int64 [rows] (categorical: the kernel writes the
         one-hot row); ``bad_index``: int32 [1], bit 0 is set when an index lies outside [0, cd) (that row's block is all zero)."""
         rows, width = out.shape
-        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != rows or x.shape[1] < K or \
-                (x.stride(1) != 1 and x.shape[1] > 1) or (rows > 1 and x.stride(0) < K):
-            raise ValueError("mmdyn_concat_condition: x must be fp32 GPU rows [rows][>= K] of unit element stride")
-        ldx = x.stride(0) if rows > 1 else max(x.stride(0), K)
-        index = cond.dtype == torch.int64
-        if tuple(cond.shape) != ((rows,) if index else (rows, cd)):
-            raise ValueError(f"mmdyn_concat_condition: condition {tuple(cond.shape)} ({cond.dtype}) does not match rows={rows}, "
-                             f"cd={cd}")
+        ldx, index = self._concat_operands("mmdyn_concat_condition", x, cond, rows, rows, K, cd)
         check(self.lib.mmdyn_concat_condition(x.data_ptr(), None if index else _ptr(cond), _ptr(cond, torch.int64) if index else None,
                                               _ptr(out), _ptr(bad_index, torch.int32), rows, K, ldx, cd, width, _stream()),
               "mmdyn_concat_condition")
+
+    @staticmethod
+    def _concat_operands(name, x, cond, rows, x_rows, K, cd):
+        """The checks of the two joins: (row stride of x, whether the condition is class indices)."""
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != x_rows or x.shape[1] < K or \
+                (x.stride(1) != 1 and x.shape[1] > 1) or (x_rows > 1 and x.stride(0) < K):
+            raise ValueError(f"{name}: x must be fp32 GPU rows [{'x_rows' if x_rows != rows else 'rows'}][>= K] of unit element stride")
+        index = cond.dtype == torch.int64
+        if tuple(cond.shape) != ((rows,) if index else (rows, cd)):
+            raise ValueError(f"{name}: condition {tuple(cond.shape)} ({cond.dtype}) does not match rows={rows}, cd={cd}")
+        return (x.stride(0) if x_rows > 1 else max(x.stride(0), K)), index
+
+    def concat_condition_tiled(self, x, cond, out, K, cd, x_rows, bad_index=None):
+        """concat_condition with ``x`` holding ``x_rows`` rows: out row r = [x[r % x_rows][:K] | condition of row r | 0]
+        (mmdyn_concat_condition_tiled).  ``cond`` keeps one entry per out row; rows must be a multiple of x_rows."""
+        rows, width = out.shape
+        x_rows = int(x_rows)
+        if x_rows < 1 or rows % x_rows:
+            raise ValueError(f"mmdyn_concat_condition_tiled: rows={rows} is not a multiple of x_rows={x_rows}")
+        ldx, index = self._concat_operands("mmdyn_concat_condition_tiled", x, cond, rows, x_rows, K, cd)
+        check(self.lib.mmdyn_concat_condition_tiled(x.data_ptr(), None if index else _ptr(cond),
+                                                    _ptr(cond, torch.int64) if index else None, _ptr(out),
+                                                    _ptr(bad_index, torch.int32), rows, x_rows, K, ldx, cd, width, _stream()),
+              "mmdyn_concat_condition_tiled")
 
     def pack_plan(self, plan_dev, n):
         """plan_dev: uint8 device tensor holding n mmdyn_pack_entry structs (see layers.PackPlan)."""
@@ -1015,6 +1032,70 @@ class HipBackend:
             arg.recon[g], arg.obs[g], arg.out[g] = _ptr(grp["recon"]), _ptr(grp.get("obs")), _ptr(grp["out"])
             arg.row_len[g], arg.logits[g], arg.column[g] = grp["recon"].numel() // B, int(bool(grp["logits"])), int(grp["column"])
         check(self.lib.mmdyn_rollout_feed(ctypes.addressof(arg), len(groups), table, B, _stream()), "mmdyn_rollout_feed")
+
+    # ---- candidate conditions: the cost table, the winner of each row, the winner's rows ----
+    def plan_select(self, bce_rows, mse_rows, kl_rows, tavail, candidates, cost, best, best_cost, best_condition, N, B,
+                    pose_multiplier, kl_weight=1.0, kl_weight_dev=None):
+        """cost [N][B] fp32 = ((bce_rows[0] + bce_rows[1]) + pose_multiplier * mse_rows) + kl_weight * kl_rows, formed in fp64 in that
+        order; best [B] int32 = the candidate of the smallest fp64 cost (ties: the lowest index; NaN never wins; all NaN: -1);
+        best_cost [B] fp32; best_condition = the winner's condition.  bce_rows: fp64 [2][N][B] or None; mse_rows: fp64 [N][B] or
+        None; kl_rows: fp64 [N][B]; tavail: the target-availability table (uint8 [B][4]) or None -- the N table entries of an
+        absent (row, term) are overwritten with 0 and left out.  candidates, candidate-major: fp32 [N * B][cd] with best_condition
+        fp32 [B][cd], or int64 [N * B] with best_condition int64 [B]."""
+        name, N, B = "plan_select", int(N), int(B)
+        if N < 1 or B < 1:
+            raise ValueError(f"mmdyn_plan_select: N = {N} and B = {B} must be positive")
+        if not torch.is_tensor(candidates) or candidates.dtype not in (torch.float32, torch.int64):
+            raise ValueError(f"mmdyn_plan_select: candidates must be fp32 [N * B][cd] or int64 [N * B], got "
+                             f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
+        index = candidates.dtype == torch.int64
+        if index:
+            cd, shapes = 1, ((N * B,), (B,))
+        else:
+            if candidates.dim() != 2 or candidates.shape[1] < 1:
+                raise ValueError(f"mmdyn_plan_select: real-valued candidates must be [N * B = {N * B}][cd], got {tuple(candidates.shape)}")
+            cd = candidates.shape[1]
+            shapes = ((N * B, cd), (B, cd))
+        if any(t is None for t in (kl_rows, cost, best, best_cost, best_condition)):
+            raise ValueError("mmdyn_plan_select: kl_rows, cost, best, best_cost and best_condition are required")
+        f32, f64, ctype = torch.float32, torch.float64, candidates.dtype
+        tp = self._avail(tavail, B, name, cost)
+        bp, mp, kp, cp, op, sp, wp, qp = self._iw_tables(
+            name, (bce_rows, (2, N, B), "bce_rows", f64), (mse_rows, (N, B), "mse_rows", f64), (kl_rows, (N, B), "kl_rows", f64),
+            (candidates, shapes[0], "candidates", ctype), (cost, (N, B), "cost", f32), (best, (B,), "best", torch.int32),
+            (best_cost, (B,), "best_cost", f32), (best_condition, shapes[1], "best_condition", ctype))
+        check(self.lib.mmdyn_plan_select(bp, mp, kp, tp, None if index else cp, cp if index else None, cd, op, sp, wp,
+                                         None if index else qp, qp if index else None, N, B, float(pose_multiplier),
+                                         float(kl_weight), _ptr(kl_weight_dev), _stream()), "mmdyn_plan_select")
+
+    def gather_best(self, groups, best, N, B):
+        """One launch for up to FEED_GROUPS tensors: ``groups`` is a list of dicts {src, out, logits}; out[b] = f(src[best[b] * B +
+        b]) with f = sigmoid where ``logits``, the identity otherwise.  src: contiguous fp32 [N * B, ...]; out: contiguous fp32
+        [B, ...] of the same row shape, overlapping no src and no other out of the call; best: int32 [B] -- a row whose index is
+        -1 (or anywhere outside [0, N)) is filled with NaN and reads nothing.  A taken row has the bits of :meth:`complete_select` (x = None) on it."""
+        name, N, B = "gather_best", int(N), int(B)
+        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
+            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
+                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
+        if N < 1 or B < 1:
+            raise ValueError(f"mmdyn_hip: {name}: N = {N} and B = {B} must be positive")
+        if not torch.is_tensor(best) or best.dtype != torch.int32 or tuple(best.shape) != (B,) or not best.is_contiguous():
+            raise ValueError(f"mmdyn_hip: {name}: best must be a contiguous int32 [B={B}] tensor")
+        arg = GatherGroups()
+        for g, grp in enumerate(groups):
+            src, out = grp["src"], grp["out"]
+            for t, rows, what in ((src, N * B, "src"), (out, B, "out")):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.shape[0] != rows:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor of {rows} rows, got "
+                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+            if src.numel() == 0 or tuple(src.shape[1:]) != tuple(out.shape[1:]) or src.device != best.device or out.device != best.device:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: src {tuple(src.shape)} on {src.device} and out {tuple(out.shape)} on "
+                                 f"{out.device} must share a non-empty row shape and the device of best")
+        for g, grp in enumerate(groups):
+            arg.src[g], arg.out[g] = _ptr(grp["src"]), _ptr(grp["out"])
+            arg.row_len[g], arg.logits[g] = grp["out"].numel() // B, int(bool(grp["logits"]))
+        check(self.lib.mmdyn_gather_best(ctypes.addressof(arg), len(groups), _ptr(best, torch.int32), N, B, _stream()),
+              "mmdyn_gather_best")
 
     # ---- importance-weighted K-sample bound (evaluation only) ----
     @staticmethod

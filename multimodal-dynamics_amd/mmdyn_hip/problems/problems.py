@@ -824,3 +824,47 @@ class DynModeling(SeqModeling):
             return {k: None if v is None else v.clone() for k, v in res.items()}
         finally:
             self._model.train(was_training)
+
+    def plan(self, data_input, data_target, candidates=None):
+        """Which of N candidate shocks takes each frame of one loader batch to its recorded next frame (cnn-mvae, ``--conditional``):
+        ``parse_input``, then :meth:`mmdyn_hip.engine.MVAEInference.plan` on the joint request with the batch's ``data[3]``
+        availability, goal = the batch's target frames (the pose too if the model uses it) with the dataset's availability column
+        as ``goal_available`` (the pose goal always counts), the problem's KL weight and pose multiplier, posterior-mean latents.
+        ``candidates``: as the engine takes them.  Eval-mode arithmetic: the model is put in ``eval()`` for the call and goes back
+        to the mode it was in; the engine is built on first use and re-packs the weights on every call.  Returns clones of the
+        engine's dict plus ``recorded``: the batch's own shock, to compare the choice with."""
+        if 'mvae' not in str(self.parameters.get('model_name')):
+            raise ValueError(f"plan() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
+        if not isinstance(data_input, (list, tuple)) or len(data_input) < 4 or self.parameters.get('input_type') != 'visuotactile':
+            raise ValueError("plan() takes a visuotactile batch in the loader's format (a list of tensors)")
+        if not self._conditional:
+            raise ValueError("plan() was called on an unconditional model: candidate conditions need --conditional")
+        if len(data_input) < 5:
+            raise ValueError("a conditional model needs the shock force of every frame (data[4])")
+        inputs, targets = self.parse_input(list(data_input), list(data_target))
+        use_pose = bool(self._model._use_pose)
+        has = inputs['input_available_modals']
+        goal = list(targets['target_output']) + [targets['target_object_pose'][0] if use_pose else None]
+        # the goal frame of row b is frame b + 1 (the roll of parse_input): so is its availability; the pose goal always counts
+        l, dev = int(self._seq_length), self._device
+        goal_has = torch.roll(has.to(torch.float32), -1, dims=0)
+        goal_has[l - 1::l] = 1.0                                   # the dataset's final target
+        goal_has = torch.cat((goal_has[:, :2], torch.ones(goal_has.shape[0], 1, device=dev)), 1)
+        from ..engine import MVAEInference
+        was_training = self._model.training
+        self._model.eval()
+        try:
+            eng = getattr(self, '_planner', None)
+            if eng is None or eng.model is not self._model:
+                eng = self._planner = MVAEInference(self._model)
+            else:
+                eng.refresh()
+            res = eng.plan(list(inputs['model_input']), pose=inputs['input_object_pose'][0] if use_pose else None, goal=goal,
+                           candidates=candidates, kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier,
+                           available=has, goal_available=goal_has)
+            clone = lambda v: None if v is None else ([clone(t) for t in v] if isinstance(v, (list, tuple)) else v.clone())
+            out = {k: clone(v) for k, v in res.items()}
+            out["recorded"] = inputs['shock']
+            return out
+        finally:
+            self._model.train(was_training)
