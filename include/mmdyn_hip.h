@@ -649,6 +649,45 @@ typedef struct {
 } mmdyn_feed_groups;
 int mmdyn_rollout_feed(const mmdyn_feed_groups* groups, int G, const uint8_t* obs_avail, int B, void* stream);
 
+/* ---- ensemble rollout: N sampled trajectories per request row, their statistics from the same read (the reference draws one z
+ * per forward, vae.py:126-165, and has no rollout) -------------------------------------------------------------------------
+ * The feed of N * B trajectory rows, sample-major (row n * B + b is trajectory n of request row b), under observations that
+ * exist once per request row, for up to MMDYN_FEED_GROUPS tensors at once.  With p = logits[g] ? 1 / (1 + expf(-r)) : r,
+ * r = recon[g][n * B + b][i], and observed(g, b) = obs[g] && (!obs_avail || obs_avail[b][column[g]]) on the B-row table:
+ *   out[g][n * B + b][i] = observed(g, b) ? obs[g][b][i] : p            the bits of mmdyn_rollout_feed on the same N * B rows with
+ *                                                                        obs[g] and the table repeated N times, for every N;
+ *   mean[g][b][i]        = (1 / N) sum_n p                               of the PREDICTION, observed or not;
+ *   var[g][b][i]         = (1 / N) sum_n (p - mean)^2                    the population variance; N = 1: 0;
+ *   spread[g][b]        += sum_i var[g][b][i]                            the fp32 values as written, widened; an ACCUMULATOR.
+ * The statistics are accumulated in fp64 in n order around c = p_0: d_n = p_n - c, S1 = sum d_n, S2 = sum d_n^2,
+ * mean = (float)(c + S1 / N), var = (float)max(0, (S2 - S1^2 / N) / N): mean within 2^-23 max_n |p_n| and var within 2^-22 relative
+ * (+ 2^-126) of the exact values; N identical samples give var == 0 and mean == p exactly; a NaN sample makes the element's mean and
+ * var NaN and nothing else.  spread is added by fp64 atomics (one per wavefront where its elements lie in one row): equal only to
+ * rounding between runs; everything else has the same bits in every run.
+ * A thread owns one quad (or element) of the [B][row_len] plane and walks n: every recon element is loaded exactly once (always:
+ * the statistics need it), the obs quad once before the walk and only where it is taken -- an obs row of an unobserved (row, group)
+ * is never loaded and may hold NaN / Inf.  16-byte accesses where recon, obs, out, mean and var of the group are 16-byte aligned and
+ * B * row_len % 4 == 0 (the sample stride keeps the alignment), element by element otherwise, any row_len (a quad that straddles
+ * rows selects per element).  A block works on one group.  No LDS beyond the wave reduction, no workspace.  out, mean and var are
+ * OUTPUTS: every element written, none read.
+ * Checked on the host before the launch: groups, or recon / out / mean of a group < G, null: MMDYN_ERR_NULL; G outside
+ * [1, MMDYN_FEED_GROUPS], N < 1, B < 1, a row_len < 1, a column outside [0, MMDYN_MAX_EXPERTS), a misaligned table, spread without
+ * var (or not 8-byte aligned), or an out / mean / var / spread of any group that overlaps the recon or obs of ANY group < G, the table
+ * or another output of the launch: MMDYN_ERR_SHAPE; N * B * row_len[g] >= 2^31: MMDYN_ERR_RANGE.  The struct is read during the call
+ * only.  Added without touching an existing signature or workspace: the revision stays 6. */
+typedef struct {
+  const float* recon[MMDYN_FEED_GROUPS];  /* [N * B][row_len[g]], sample-major: the step's decoder output */
+  const float* obs[MMDYN_FEED_GROUPS];    /* [B][row_len[g]]: one observation per request row; null: nothing observed in this group */
+  float* out[MMDYN_FEED_GROUPS];          /* [N * B][row_len[g]]: next state = trajectory slot */
+  float* mean[MMDYN_FEED_GROUPS];         /* [B][row_len[g]], required */
+  float* var[MMDYN_FEED_GROUPS];          /* [B][row_len[g]], may be null */
+  double* spread[MMDYN_FEED_GROUPS];      /* [B], may be null; the caller zeroes it; needs var */
+  int row_len[MMDYN_FEED_GROUPS];
+  int logits[MMDYN_FEED_GROUPS];          /* != 0: recon holds logits, the state is their sigmoid */
+  int column[MMDYN_FEED_GROUPS];          /* availability-table byte of the group */
+} mmdyn_ensemble_groups;
+int mmdyn_ensemble_feed(const mmdyn_ensemble_groups* groups, int G, const uint8_t* obs_avail, int N, int B, void* stream);
+
 /* ---- candidate conditions: N conditions scored per row, the best one picked on the device (the reference has no such operation:
  * with vae.py:126-165 a caller would run MVAE.forward once per candidate and take the argmin of the losses of problems.py:473-546
  * on the host) --------------------------------------------------------------------------------------------------------------

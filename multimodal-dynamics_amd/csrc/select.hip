@@ -17,7 +17,11 @@
 //     gather_best copies the winner's decoder rows out of the [N * B] candidate-major outputs, for up to MMDYN_FEED_GROUPS tensors
 //     in one launch (images through sigmoid_exact, so a taken row has the bits of mmdyn_complete_select(x = null) on that row).
 //     Both read best[] from device memory: the choice never visits the host and the request sits in one captured graph.
-// Memory-bound, no LDS, no atomics, no scratch.
+//   - ensemble_feed: the rollout feed of N sampled trajectories per request row (MVAEInference.rollout(samples=N)).  The N * B
+//     decoder rows of a step become the N * B next states under observations that exist once per request row, and the same read
+//     of the logits leaves the ensemble's per-element mean and variance and each row's summed variance.  An element scheme of
+//     its own (a thread walks the samples of one quad); its out has the bits of rollout_feed on the N * B rows.
+// Memory-bound, no LDS, no scratch; no atomics except ensemble_feed's spread accumulator.
 #include "common.h"
 
 namespace {
@@ -100,6 +104,151 @@ __global__ __launch_bounds__(256) void rollout_feed_kernel(const FeedArgs a, con
 bool overlap(const float* p, const float* q, int64_t n) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q, bytes = (uintptr_t)n * sizeof(float);
   return q != nullptr && a < b + bytes && b < a + bytes;
+}
+
+// ---- ensemble rollout: the feed of N trajectories per request row, with the ensemble's statistics from the same read ----
+
+// W consecutive floats: one 16-byte access (W = 4) or one element (W = 1)
+template <int W> __device__ __forceinline__ void ld_w(const float* p, float* v);
+template <> __device__ __forceinline__ void ld_w<4>(const float* p, float* v) {
+  const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = q[k];
+}
+template <> __device__ __forceinline__ void ld_w<1>(const float* p, float* v) { v[0] = p[0]; }
+template <int W> __device__ __forceinline__ void st_w(float* p, const float* v);
+template <> __device__ __forceinline__ void st_w<4>(float* p, const float* v) {
+  *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+}
+template <> __device__ __forceinline__ void st_w<1>(float* p, const float* v) { p[0] = v[0]; }
+
+struct EnsembleArgs {
+  const float* recon[MMDYN_FEED_GROUPS];
+  const float* obs[MMDYN_FEED_GROUPS];
+  float* out[MMDYN_FEED_GROUPS];
+  float* mean[MMDYN_FEED_GROUPS];
+  float* var[MMDYN_FEED_GROUPS];
+  double* spread[MMDYN_FEED_GROUPS];
+  int64_t plane[MMDYN_FEED_GROUPS];          // B * row_len: the floats of one sample, the stride between samples
+  int row_len[MMDYN_FEED_GROUPS], logits[MMDYN_FEED_GROUPS], column[MMDYN_FEED_GROUPS], vec[MMDYN_FEED_GROUPS];
+  int first_block[MMDYN_FEED_GROUPS + 1];
+};
+
+constexpr int ENSEMBLE_UNROLL = 8;           // loads of one thread in flight while it walks the samples
+
+// The [B][row_len] plane as items of W floats (W = 4: plane % 4 == 0 and every pointer 16-byte aligned; W = 1 otherwise).  A
+// thread owns one item and walks the samples n = 0 .. N-1 of recon [N][plane]: every recon element is loaded once, its p =
+// logits ? sigmoid_exact(r) : r goes to out[n] (or the observation, loaded once before the walk and only for the elements whose
+// row takes it) and into the fp64 sums around c = p_0: d = p_n - c, S1 += d, S2 += d * d, in n order;
+// mean = (float)(c + S1 / N), var = (float)max(0, (S2 - S1 * S1 / N) / N) (a NaN stays a NaN).  spread[b] += the fp32 var values
+// of row b, widened: one atomic per wave where the wave's items lie in one row, one per item inside a row, one per element of
+// an item that straddles rows.  `wave0` / `nthreads`: the first item of this wave and the items of one sweep of the group's
+// blocks, so the trip count is wave-uniform and every lane reaches the shuffles.
+template <int W>
+__device__ __forceinline__ void ensemble_rows(const float* recon, const float* obs, const uint32_t* avail, int column, float* out,
+                                              float* mean, float* var, double* spread, int64_t plane, int row_len, int logits,
+                                              int N, int64_t wave0, int64_t nthreads) {
+  const int64_t items = plane / W;
+  const int lane = threadIdx.x & 63;
+  const double inv_n = 1.0 / (double)N;
+  for (int64_t base = wave0; base < items; base += nthreads) {
+    const int64_t q = base + lane;
+    const bool active = q < items;
+    const int64_t e0 = active ? W * q : 0;
+    const int b0 = (int)(e0 / row_len), b3 = (int)((e0 + W - 1) / row_len);
+    float fvar[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) fvar[k] = 0.f;
+    if (active) {
+      bool taken[W];
+      float ob[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const int b = b0 == b3 ? b0 : (int)((e0 + k) / row_len);
+        taken[k] = obs != nullptr && (!avail || has(avail[b], column));
+        ob[k] = 0.f;
+      }
+      if (b0 == b3) {
+        if (taken[0]) ld_w<W>(obs + e0, ob);
+      } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k)
+          if (taken[k]) ob[k] = obs[e0 + k];
+      }
+      double c[W], s1[W], s2[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) c[k] = s1[k] = s2[k] = 0.0;
+      auto sample = [&](int n, float* p) {
+        float o[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          if (logits) p[k] = sigmoid_exact(p[k]);
+          if (n == 0) c[k] = (double)p[k];
+          const double d = (double)p[k] - c[k];
+          s1[k] += d;
+          s2[k] += d * d;
+          o[k] = taken[k] ? ob[k] : p[k];
+        }
+        st_w<W>(out + (int64_t)n * plane + e0, o);
+      };
+      const float* src = recon + e0;
+      int n = 0;
+      for (; n + ENSEMBLE_UNROLL <= N; n += ENSEMBLE_UNROLL) {
+        float r[ENSEMBLE_UNROLL][W];
+#pragma unroll
+        for (int u = 0; u < ENSEMBLE_UNROLL; ++u) ld_w<W>(src + (int64_t)(n + u) * plane, r[u]);
+#pragma unroll
+        for (int u = 0; u < ENSEMBLE_UNROLL; ++u) sample(n + u, r[u]);
+      }
+      for (; n < N; ++n) {
+        float r[W];
+        ld_w<W>(src + (int64_t)n * plane, r);
+        sample(n, r);
+      }
+      float fmean[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        fmean[k] = (float)(c[k] + s1[k] * inv_n);
+        const double v = (s2[k] - s1[k] * s1[k] * inv_n) * inv_n;
+        fvar[k] = (float)(v < 0.0 ? 0.0 : v);
+      }
+      st_w<W>(mean + e0, fmean);
+      if (var) st_w<W>(var + e0, fvar);
+    }
+    if (spread) {
+      // (wave-uniform: base and items are, and the vote covers every lane)
+      const int bw = __builtin_amdgcn_readfirstlane(b0);
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < W; ++k) s += (double)fvar[k];
+      if (__all(!active || (b0 == bw && b3 == bw))) {
+        s = wave_sum_d(s);
+        if (lane == 0) atomicAdd(spread + bw, s);
+      } else if (active) {
+        if (b0 == b3) {
+          atomicAdd(spread + b0, s);
+        } else {
+#pragma unroll
+          for (int k = 0; k < W; ++k) atomicAdd(spread + (int)((e0 + k) / row_len), (double)fvar[k]);
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void ensemble_feed_kernel(const EnsembleArgs a, const uint32_t* __restrict__ avail, int G, int N) {
+  int g = 0;
+#pragma unroll
+  for (int k = 1; k < MMDYN_FEED_GROUPS; ++k)
+    if (k < G && (int)blockIdx.x >= a.first_block[k]) g = k;
+  const int64_t wave0 = (int64_t)((int)blockIdx.x - a.first_block[g]) * blockDim.x + (threadIdx.x & ~63u);
+  const int64_t nthreads = (int64_t)(a.first_block[g + 1] - a.first_block[g]) * blockDim.x;
+  if (a.vec[g])
+    ensemble_rows<4>(a.recon[g], a.obs[g], avail, a.column[g], a.out[g], a.mean[g], a.var[g], a.spread[g], a.plane[g], a.row_len[g],
+                     a.logits[g], N, wave0, nthreads);
+  else
+    ensemble_rows<1>(a.recon[g], a.obs[g], avail, a.column[g], a.out[g], a.mean[g], a.var[g], a.spread[g], a.plane[g], a.row_len[g],
+                     a.logits[g], N, wave0, nthreads);
 }
 
 // ---- candidate conditions: the cost table, the winner of each row, and the winner's rows ----
@@ -326,5 +475,57 @@ extern "C" int mmdyn_gather_best(const mmdyn_gather_groups* groups, int G, const
   }
   const int blocks = split_blocks(work, G, a.first_block);
   hipLaunchKernelGGL(gather_best_kernel, dim3(blocks), dim3(256), 0, ST, a, best, G, N);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_ensemble_feed(const mmdyn_ensemble_groups* groups, int G, const uint8_t* obs_avail, int N, int B, void* stream) {
+  if (!groups) return MMDYN_ERR_NULL;
+  if (G < 1 || G > MMDYN_FEED_GROUPS || N < 1 || B < 1 || ((uintptr_t)obs_avail & 3)) return MMDYN_ERR_SHAPE;
+  EnsembleArgs a{};
+  int64_t work[MMDYN_FEED_GROUPS];
+  for (int g = 0; g < G; ++g) {
+    if (!groups->recon[g] || !groups->out[g] || !groups->mean[g]) return MMDYN_ERR_NULL;
+    if (groups->row_len[g] < 1 || groups->column[g] < 0 || groups->column[g] >= MMDYN_MAX_EXPERTS) return MMDYN_ERR_SHAPE;
+    if (groups->spread[g] && (!groups->var[g] || ((uintptr_t)groups->spread[g] & 7))) return MMDYN_ERR_SHAPE;
+    const int64_t plane = (int64_t)B * groups->row_len[g];
+    if (plane * N >= (1LL << 31)) return MMDYN_ERR_RANGE;
+    // 16-byte accesses: every pointer of the group aligned and a sample stride that keeps the alignment
+    const uintptr_t ptrs = (uintptr_t)groups->recon[g] | (uintptr_t)groups->obs[g] | (uintptr_t)groups->out[g] |
+                           (uintptr_t)groups->mean[g] | (uintptr_t)groups->var[g];
+    a.recon[g] = groups->recon[g];
+    a.obs[g] = groups->obs[g];
+    a.out[g] = groups->out[g];
+    a.mean[g] = groups->mean[g];
+    a.var[g] = groups->var[g];
+    a.spread[g] = groups->spread[g];
+    a.plane[g] = plane;
+    a.row_len[g] = groups->row_len[g];
+    a.logits[g] = groups->logits[g];
+    a.column[g] = groups->column[g];
+    a.vec[g] = (ptrs & 15) == 0 && plane % 4 == 0;
+    work[g] = ceil_div64(a.vec[g] ? plane / 4 : plane, 256);      // blocks of one item per thread
+  }
+  // the outputs of a group are written while other blocks read the inputs of EVERY group and the table and write the other
+  // outputs: an output may touch none of them
+  struct Range { const void* p; int64_t bytes; };
+  Range in[2 * MMDYN_FEED_GROUPS + 1], outs[4 * MMDYN_FEED_GROUPS];
+  int n_in = 0, n_out = 0;
+  for (int g = 0; g < G; ++g) {
+    in[n_in++] = {a.recon[g], a.plane[g] * N * 4};
+    if (a.obs[g]) in[n_in++] = {a.obs[g], a.plane[g] * 4};
+    outs[n_out++] = {a.out[g], a.plane[g] * N * 4};
+    outs[n_out++] = {a.mean[g], a.plane[g] * 4};
+    if (a.var[g]) outs[n_out++] = {a.var[g], a.plane[g] * 4};
+    if (a.spread[g]) outs[n_out++] = {a.spread[g], (int64_t)B * 8};
+  }
+  if (obs_avail) in[n_in++] = {obs_avail, (int64_t)B * MMDYN_MAX_EXPERTS};
+  for (int i = 0; i < n_out; ++i) {
+    for (int j = 0; j < n_in; ++j)
+      if (ranges_overlap(outs[i].p, outs[i].bytes, in[j].p, in[j].bytes)) return MMDYN_ERR_SHAPE;
+    for (int j = i + 1; j < n_out; ++j)
+      if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return MMDYN_ERR_SHAPE;
+  }
+  const int blocks = split_blocks(work, G, a.first_block);
+  hipLaunchKernelGGL(ensemble_feed_kernel, dim3(blocks), dim3(256), 0, ST, a, reinterpret_cast<const uint32_t*>(obs_avail), G, N);
   MMDYN_LAUNCH_CHECK();
 }

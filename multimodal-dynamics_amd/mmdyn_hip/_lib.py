@@ -34,6 +34,12 @@ class GatherGroups(ctypes.Structure):
     _fields_ = [("src", _P * 4), ("out", _P * 4), ("row_len", _I * 4), ("logits", _I * 4)]
 
 
+class EnsembleGroups(ctypes.Structure):
+    """mmdyn_ensemble_groups (include/mmdyn_hip.h)."""
+    _fields_ = [("recon", _P * 4), ("obs", _P * 4), ("out", _P * 4), ("mean", _P * 4), ("var", _P * 4), ("spread", _P * 4),
+                ("row_len", _I * 4), ("logits", _I * 4), ("column", _I * 4)]
+
+
 MAX_PASSES = 8
 MAX_EXPERTS = 4
 FEED_GROUPS = 4           # MMDYN_FEED_GROUPS
@@ -152,6 +158,7 @@ _SIGNATURES = {
     "mmdyn_concat_condition_tiled": "ppppp" + "iiiiii" + "p",
     "mmdyn_plan_select": "pppppp" + "i" + "ppppp" + "ii" + "ff" + "pp",
     "mmdyn_gather_best": "p" + "i" + "p" + "ii" + "p",
+    "mmdyn_ensemble_feed": "p" + "i" + "p" + "ii" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

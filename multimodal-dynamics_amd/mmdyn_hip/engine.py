@@ -2000,6 +2000,98 @@ class MVAEInference:
                        mse_pose=tab[:, 1, 0] if tp is not None else None, kl=tab[:, 2, 0], rows=rows)
         return res
 
+    def _rollout_ensemble(self, T, N, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
+        """N sampled trajectories per request row, sample-major (row n * B + b).  Step 0 has the structure of :meth:`_iw_score`: the
+        encoders, the heads and the PoE launch ONCE on the B rows (z not requested), one [N][B][L] draw, one iw_latent launch, the
+        decoders on the N * B rows; every later step is the joint forward of the N * B state rows with one [N * B][L] draw.  ONE
+        ensemble_feed launch closes a step: the N * B next states under the step's B observations, and the per-element mean and
+        variance of the prediction over n plus each row's summed variance, from the same read of the decoder outputs.  With
+        targets, the row kernels run with G = N passes against the one target (slots 0..N-1 of [N][B] tables, ops.ROW_GROUPS_MAX
+        passes per launch) and the assembly of :meth:`_score_tail` on the N * B rows; tables [T][3][2][N][B], cleared by one
+        fill, like ``spread``."""
+        feed, iw_latent = ops.backend_op("ensemble_feed"), ops.backend_op("iw_latent")
+        ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
+        B, L, dev, S = ref.shape[0], self.L, ref.device, self.model.visual_decoder.image_size
+        NB = N * B
+        traj = [torch.empty(T, N, B, 3, S, S, device=dev), torch.empty(T, N, B, 3, S, S, device=dev),
+                torch.empty(T, N, B, 7, device=dev) if self.use_pose else None]
+        shapes = ((T, B, 3, S, S), (T, B, 3, S, S)) + (((T, B, 7),) if self.use_pose else ())
+        mean = [torch.empty(s, device=dev) for s in shapes] + ([] if self.use_pose else [None])
+        var = [torch.empty(s, device=dev) for s in shapes] + ([] if self.use_pose else [None])
+        spread = torch.zeros(T, 3, B, dtype=torch.float64, device=dev)
+        means, log_var = torch.empty(T, N, B, L, device=dev), torch.empty(T, N, B, L, device=dev)
+        scoring = any(t is not None for t in (tv, tt, tp))
+        if scoring:
+            tab = torch.zeros(T, 3, 2, N, B, dtype=torch.float64, device=dev)
+            rows = torch.empty(T, N, B, device=dev)
+        state = [visual, tactile, pose]
+        step_of = lambda t, i: None if t is None else t[i]
+        rep = lambda t: None if t is None else t.repeat((N,) + (1,) * (t.dim() - 1))      # [B, ...] -> [N * B, ...], sample-major
+        with self._index_scope():
+            for i in range(T):
+                c_i = step_of(cond, i) if per_step_cond else cond
+                c_rows = rep(c_i)
+                if i == 0:
+                    mu, lv, _ = self._poe(self._heads(state[0], state[1], state[2], c_i), avail, None, B, dev)
+                    eps = self._draw_latent(NB).view(N, B, L)
+                    z, ratio = torch.empty(N, B, L, device=dev), torch.empty(N, B, dtype=torch.float64, device=dev)
+                    iw_latent(mu, lv, eps, z, ratio, N, B, L)
+                    means[0].copy_(mu)                       # the request's posterior in all N slots
+                    log_var[0].copy_(lv)
+                    z = z.view(NB, L)
+                else:
+                    mu, lv, z = self._poe(self._heads(state[0], state[1], state[2], c_rows), None, self._draw_latent(NB), NB, dev,
+                                          out=(means[i].view(NB, L), log_var[i].view(NB, L)))
+                v, t, pr = self._decode(z, c_rows)
+                if scoring:         # before the correction below: what each trajectory predicted for frame i + 1
+                    self._ensemble_tail(N, B, v, t, pr, mu, lv, step_of(tv, i), step_of(tt, i), step_of(tp, i), rep(step_of(tav, i)),
+                                        tab[i], rows[i])
+                flat = lambda x: x.view((NB,) + tuple(x.shape[2:]))
+                groups = [{"recon": v, "obs": step_of(ov, i), "out": flat(traj[0][i]), "mean": mean[0][i], "var": var[0][i],
+                           "spread": spread[i, 0], "logits": True, "column": 0},
+                          {"recon": t, "obs": step_of(ot, i), "out": flat(traj[1][i]), "mean": mean[1][i], "var": var[1][i],
+                           "spread": spread[i, 1], "logits": True, "column": 1}]
+                if self.use_pose:
+                    groups.append({"recon": pr, "obs": step_of(op, i), "out": flat(traj[2][i]), "mean": mean[2][i], "var": var[2][i],
+                                   "spread": spread[i, 2], "logits": False, "column": 2})
+                feed(groups, step_of(oav, i), N, B)
+                state = [g["out"] for g in groups] + ([] if self.use_pose else [None])
+        res = {"visual": traj[0], "tactile": traj[1], "pose": traj[2], "visual_mean": mean[0], "visual_var": var[0],
+               "tactile_mean": mean[1], "tactile_var": var[1], "pose_mean": mean[2], "pose_var": var[2], "spread": spread,
+               "means": means, "log_var": log_var, "bce_visual": None, "bce_tactile": None, "mse_pose": None, "kl": None, "rows": None}
+        if scoring:
+            res.update(bce_visual=tab[:, 0, 0] if tv is not None else None, bce_tactile=tab[:, 0, 1] if tt is not None else None,
+                       mse_pose=tab[:, 1, 0] if tp is not None else None, kl=tab[:, 2, 0], rows=rows)
+        return res
+
+    def _ensemble_tail(self, N, B, v, t, pr, mu, lv, tv, tt, tp, tavail, tab, rows):
+        """The terms of one step of N * B trajectory rows into its (zeroed) fp64 tables ``tab`` [3][2][N][B] = (bce: visual,
+        tactile; mse: pose, 0; kl: KL, 0) and ``rows`` [N][B]: the row kernels with G = N passes against the step's one target,
+        kl_rows on the posterior that exists ([B] at step 0, its N copies made by a broadcast; [N * B] afterwards), and the
+        assembly of :meth:`_score_tail` with P = 2 on the N * B rows (``tavail``: the table repeated N times, or None)."""
+        NB, L = N * B, self.L
+        chw, hw = v[0].numel(), v[0, 0].numel()
+        for g0 in range(0, N, ops.ROW_GROUPS_MAX):
+            slots = list(range(g0, min(N, g0 + ops.ROW_GROUPS_MAX)))
+            rows_of = slice(g0 * B, (slots[-1] + 1) * B)
+            for slot, (lg, tg) in enumerate(((v, tv), (t, tt))):
+                if tg is not None:
+                    ops.B.bce_logits_rows_groups(lg[rows_of], tg, tab[0, slot], slots, B, chw, mask=None, hw=hw, mask_channels=1)
+            if tp is not None:
+                ops.B.mse_rows_groups(pr[rows_of], tp, tab[1, 0], slots, B, tp.shape[1])
+        if mu.shape[0] == NB:
+            ops.B.kl_rows(mu, lv, tab[2, 0].view(1, NB), 1, NB, L)
+        else:
+            kl = torch.empty(1, B, dtype=torch.float64, device=mu.device)
+            ops.B.kl_rows(mu, lv, kl, 1, B, L)
+            tab[2, 0].copy_(kl)
+        bce, mse, kl = (tab[k].view(2, NB) for k in range(3))
+        if tavail is None:
+            ops.B.elbo_assemble_rows(bce, mse, kl, None, rows.view(NB), None, 2, NB, 1.0, self._pose_multiplier, self._klw, 1)
+        else:
+            ops.B.elbo_assemble_rows_avail(bce, mse, kl, None, rows.view(NB), None, tavail, [0, 1], [2, -1], 2, NB, 1.0,
+                                           self._pose_multiplier, self._klw, 1)
+
     def _step_tensors(self, name, given, T, B):
         """``observed`` / ``targets`` = [visual | None, tactile | None, pose | None], each [T, B, ...] -> three contiguous fp32
         tensors / None on the engine's device; ValueError for a wrong leading (T, B), a wrong row shape, or a pose for a model
@@ -2034,7 +2126,7 @@ class MVAEInference:
 
     @torch.no_grad()
     def rollout(self, x, pose=None, steps=1, available=None, condition=None, sample=False, observed=None, observed_available=None,
-                targets=None, target_available=None, kl_weight=1.0, pose_multiplier=1000.0):
+                targets=None, target_available=None, kl_weight=1.0, pose_multiplier=1000.0, samples=None):
         """The one-step dynamics model applied to its own output ``steps`` = T times, as ONE captured graph.  With s_0 the request
         (``x``, ``pose``, ``available`` as in :meth:`forward`), for t = 0 .. T-1: the eval-mode forward of s_t (step 0 on the
         request's subset / availability table, later steps on every modality); the prediction p_{t+1} = (sigmoid(visual logits),
@@ -2059,10 +2151,31 @@ class MVAEInference:
         / ``kl`` (fp64 [T, B]; each step's own KL) and ``rows`` (fp32 [T, B]) = bce_visual + bce_tactile + pose_multiplier *
         mse_pose + kl_weight * kl.  The KL weight is read from device memory: one graph serves every weight.  Nothing
         synchronises.  ValueError: ``steps`` no integer >= 1, a wrong leading (T, B), ``observed_available`` without ``observed``
-        (``target_available`` without ``targets``), a pose for a model without one, a trajectory tensor of 2^31 elements or more."""
+        (``target_available`` without ``targets``), a pose for a model without one, a trajectory tensor of 2^31 elements or more.
+
+        ``samples`` (None: everything above, launch for launch): an int N >= 1, with ``sample=True``, asks for an ENSEMBLE of N
+        sampled trajectories per request row and its statistics.  Step 0 runs the encoders once on the B rows and draws N latents
+        of the one posterior (the structure of ``score(samples=)``); the decoders and every later step run on the N * B
+        trajectory rows, sample-major, with one fresh [N * B, L] draw per step; an observation is taken by all N trajectories of
+        its row; a condition and ``target_available`` are repeated N times.  One launch per step writes the N * B next states and,
+        from the same read of the decoder outputs, the mean and the population variance over n of the PREDICTION p_{t+1} -- for
+        every row, observed or not: under filtering, the spread before the observation is taken is the signal.  The dict then
+        holds ``visual`` / ``tactile`` [T, N, B, 3, S, S] and ``pose`` [T, N, B, 7]; ``visual_mean`` / ``visual_var`` /
+        ``tactile_mean`` / ``tactile_var`` [T, B, 3, S, S] and ``pose_mean`` / ``pose_var`` [T, B, 7] (None without a pose model);
+        ``spread`` fp64 [T, 3, B] = the variance summed over each row's elements, per step and modality (the pose row 0 without a
+        pose model; accumulated by atomics: equal to rounding between runs); ``means`` / ``log_var`` [T, N, B, L] (step 0: the
+        request's posterior in all N slots); with targets ``bce_visual`` / ``bce_tactile`` / ``mse_pose`` / ``kl`` fp64 [T, N, B]
+        and ``rows`` fp32 [T, N, B], each trajectory against the one target.  The graph key carries N.  ValueError: N no integer
+        >= 1, ``sample=False`` (N identical trajectories), or N past what 32-bit element offsets allow."""
         if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or steps < 1:
             raise ValueError(f"steps must be an integer >= 1 (the number of model applications), got {steps!r}")
         T, sample = int(steps), bool(sample)
+        if samples is not None:
+            if isinstance(samples, bool) or not isinstance(samples, numbers.Integral) or samples < 1:
+                raise ValueError(f"samples must be an integer >= 1 (the number of trajectories per row), got {samples!r}")
+            if not sample:
+                raise ValueError("samples needs sample=True: the posterior-mean rollout would give N identical trajectories")
+            samples = int(samples)
         visual, tactile = x
         c = lambda t: None if t is None else t.to(torch.float32).contiguous()
         ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
@@ -2073,6 +2186,13 @@ class MVAEInference:
         if T * B * 3 * S * S >= 1 << 31:
             raise ValueError(f"steps = {T} of B = {B} rows make a trajectory tensor of {T * B} x {3 * S * S} elements, past 2^31; "
                              f"the largest steps for B = {B} is {((1 << 31) - 1) // (B * 3 * S * S)}")
+        if samples is not None:
+            # 32-bit element offsets: the trajectory tensors [T][N][B][3][S][S] and the decoders' largest activation, the last hidden
+            # layer's [N * B][32][S / 2][S / 2]
+            most = min(((1 << 31) - 1) // (T * B * 3 * S * S), ((1 << 31) - 1) // (B * 32 * (S // 2) ** 2))
+            if samples > most:
+                raise ValueError(f"samples = {samples} trajectories of B = {B} rows over steps = {T} make a tensor of 2^31 elements or "
+                                 f"more; the largest samples for B = {B} and steps = {T} is {most}")
         per_step_cond = False
         if self.conditional and torch.is_tensor(condition):
             per_step_cond = condition.dim() == 3 or (self.categorical and condition.dim() == 2 and tuple(condition.shape) != (B, 1))
@@ -2096,6 +2216,8 @@ class MVAEInference:
         args = ins + [cond, avail] + obs + [oav] + tg + [tav]
         key = ("rollout", T, sample, self._pose_multiplier, per_step_cond, None if cond is None else self._cond_key(cond)) + \
             tuple(None if t is None else (str(t.dtype),) + tuple(t.shape) for t in args)
+        if samples is not None:
+            return self._run(key + (("samples", samples),), lambda *a: self._rollout_ensemble(T, samples, per_step_cond, *a), None, args)
         return self._run(key, lambda *a: self._rollout(T, sample, per_step_cond, *a), None, args)
 
     @torch.no_grad()

@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import PassExperts, FeedGroups, GatherGroups, MAX_PASSES, MAX_EXPERTS, FEED_GROUPS, check
+from ._lib import PassExperts, FeedGroups, GatherGroups, EnsembleGroups, MAX_PASSES, MAX_EXPERTS, FEED_GROUPS, check
 
 ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
 DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0 = 0, 1, 2, 3, 4
@@ -1096,6 +1096,51 @@ class HipBackend:
             arg.row_len[g], arg.logits[g] = grp["out"].numel() // B, int(bool(grp["logits"]))
         check(self.lib.mmdyn_gather_best(ctypes.addressof(arg), len(groups), _ptr(best, torch.int32), N, B, _stream()),
               "mmdyn_gather_best")
+
+    # ---- ensemble rollout: the N * B decoder rows of a step -> the N * B next states + the ensemble's statistics ----
+    def ensemble_feed(self, groups, obs_avail, N, B):
+        """One launch for up to FEED_GROUPS tensors: ``groups`` is a list of dicts {recon, obs | None, out, mean, var | None,
+        spread | None, logits, column}.  recon / out: contiguous fp32 [N * B, ...], sample-major (row n * B + b); obs / mean / var:
+        contiguous fp32 [B, ...] of the same row shape; spread: contiguous fp64 [B], an accumulator the caller zeroes (needs var);
+        obs_avail: uint8 [B][4] or None.  With p = sigmoid(recon) where ``logits``, recon otherwise: out[n * B + b] = observed(b) ?
+        obs[b] : p (the bits of :meth:`rollout_feed` on the N * B rows with obs and the table repeated), mean / var = the mean and
+        population variance of p over n, spread[b] += sum of var[b]."""
+        name, N, B = "ensemble_feed", int(N), int(B)
+        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
+            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
+                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
+        if N < 1 or B < 1:
+            raise ValueError(f"mmdyn_hip: {name}: N = {N} and B = {B} must be positive")
+        arg = EnsembleGroups()
+        like = groups[0]["recon"]
+        for g, grp in enumerate(groups):
+            recon, spread = grp["recon"], grp.get("spread")
+            for t, rows, what in ((recon, N * B, "recon"), (grp["out"], N * B, "out"), (grp.get("obs"), B, "obs"),
+                                  (grp["mean"], B, "mean"), (grp.get("var"), B, "var")):
+                if t is None and what in ("obs", "var"):
+                    continue
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.shape[0] != rows:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor of {rows} rows, got "
+                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+                if tuple(t.shape[1:]) != tuple(recon.shape[1:]) or t.device != like.device:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} {tuple(t.shape)} on {t.device} does not match the rows "
+                                     f"of recon {tuple(recon.shape)} on {like.device}")
+            if recon.numel() == 0:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: empty rows")
+            if spread is not None:
+                if not torch.is_tensor(spread) or spread.dtype != torch.float64 or tuple(spread.shape) != (B,) or \
+                        not spread.is_contiguous() or spread.device != like.device:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: spread must be a contiguous fp64 [B={B}] tensor on {like.device}")
+                if grp.get("var") is None:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: spread is the row sum of var, which was not given")
+            if not 0 <= int(grp["column"]) < MAX_EXPERTS:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: column {grp['column']} is not a column of the availability table")
+        table = self._avail(obs_avail, B, name, like)
+        for g, grp in enumerate(groups):
+            arg.recon[g], arg.obs[g], arg.out[g] = _ptr(grp["recon"]), _ptr(grp.get("obs")), _ptr(grp["out"])
+            arg.mean[g], arg.var[g], arg.spread[g] = _ptr(grp["mean"]), _ptr(grp.get("var")), _ptr(grp.get("spread"), torch.float64)
+            arg.row_len[g], arg.logits[g], arg.column[g] = grp["mean"].numel() // B, int(bool(grp["logits"])), int(grp["column"])
+        check(self.lib.mmdyn_ensemble_feed(ctypes.addressof(arg), len(groups), table, N, B, _stream()), "mmdyn_ensemble_feed")
 
     # ---- importance-weighted K-sample bound (evaluation only) ----
     @staticmethod

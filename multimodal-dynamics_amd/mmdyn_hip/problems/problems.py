@@ -756,7 +756,7 @@ class DynModeling(SeqModeling):
                 {'target_output': to, 'target_object_pose': [torch.roll(data[2], -1, dims=0).to(dev)],
                  'loss_mask': target[3].to(dev)})
 
-    def rollout(self, data_input, data_target, steps=None, observe=(), sample=False):
+    def rollout(self, data_input, data_target, steps=None, observe=(), sample=False, samples=None):
         """The one-step predictor applied to its own output along each sequence of one loader batch (cnn-mvae; n sequences of l
         frames as flat [n*l, ...] tensors): :meth:`mmdyn_hip.engine.MVAEInference.rollout` from frame 0 of every sequence (with its
         ``data[3]`` availability) for ``steps`` <= l steps (default l), scored against the recorded sequence.  The target of step
@@ -766,7 +766,9 @@ class DynModeling(SeqModeling):
         "tactile", "pose") -- those modalities are fed back from the recorded frames t + 1 < l where the dataset has them (touch
         keeps arriving after vision is lost).  ``data[4]`` per frame is the per-step condition of a ``--conditional`` model.
         Eval-mode arithmetic: the model is put in ``eval()`` for the call and goes back to the mode it was in; the engine is
-        built on first use and re-packs the weights on every call.  Returns clones of the engine's dict."""
+        built on first use and re-packs the weights on every call.  ``samples`` = N (with ``sample=True``): an ensemble of N sampled
+        trajectories per sequence and its per-element mean / variance, as the engine's ``rollout(samples=N)`` returns them.
+        Returns clones of the engine's dict."""
         if 'mvae' not in str(self.parameters.get('model_name')):
             raise ValueError(f"rollout() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
         if not isinstance(data_input, (list, tuple)) or len(data_input) < 4 or self.parameters.get('input_type') != 'visuotactile':
@@ -820,7 +822,7 @@ class DynModeling(SeqModeling):
             res = eng.rollout([data[0][::l].to(dev), data[1][::l].to(dev)], pose=data[2][::l].to(dev) if use_pose else None,
                               steps=T, available=data[3][::l].to(dev), condition=cond, sample=sample, observed=observed,
                               observed_available=oavail, targets=targets, target_available=tavail, kl_weight=self._kl_weight,
-                              pose_multiplier=self._pose_multiplier)
+                              pose_multiplier=self._pose_multiplier, **({} if samples is None else {"samples": samples}))
             return {k: None if v is None else v.clone() for k, v in res.items()}
         finally:
             self._model.train(was_training)
