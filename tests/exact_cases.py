@@ -10,6 +10,9 @@ Family B -- selection weights.  One operand is arbitrary fp32 (24-bit mantissas,
     scaled by a power of two, or exactly +0 where the tap falls into the padding.  The reference is index arithmetic; compared bit
     for bit (the 16-bit matrix-core modes against the RNE-rounded element: this pins the rounding mode per element).
 
+16-bit stored operands (the `store` arguments; "bf16s" / "fp16s"): the integers and the +-2^k are exact in either type, so family A
+    applies unchanged; family B's arbitrary operand is the RNE-rounded element, stored or rounded on its way into the matrix cores.
+
 Every output of a launch is a slice in the middle of a larger buffer pre-filled with the JUNK pattern of tests/dirty.py (Guarded):
 at least 64 rows in front and behind, and the columns N..ldc of the rows inside, must hold that pattern bit for bit afterwards.
 
@@ -235,22 +238,26 @@ def _dev(t, dev):
     return None if t is None else t.to(dev)
 
 
-def run_igemm(be, dev, case, family, ld_extra=0, store=None, prep=None, planes=False, all16=False, what=""):
-    """One case on one backend / route.  store: the 16-bit storage type of A and C (the "bf16s" / "fp16s" modes); ld_extra: ldc - N
-    (fp32 outputs); prep(A, Bp) -> operands as the launch takes them (planes: as ops.Planes); all16: the packed weights are stored
-    in the 16-bit type as well.  Returns the number of launches."""
+def run_igemm(be, dev, case, family, ld_extra=0, store=None, prep=None, planes=False, all16=False, mixed=False, what=""):
+    """One case on one backend / route.  store: the 16-bit storage type of A and C (the "bf16s" / "fp16s" modes; the NCHW image of
+    MMDYN_IM2COL3 stays fp32: the first layer of the storage modes); ld_extra: ldc - N (fp32 outputs); prep(A, Bp) -> operands as
+    the launch takes them (planes: as ops.Planes); all16: the packed weights are stored in the 16-bit type as well; mixed (with
+    store, family A): the mixed-output form only -- C stays fp32, C_act alone is 16-bit (storage flag bit 6), ReLU so that it
+    stays exact.  Returns the number of launches."""
     g = Geo(case)
     h = operand_dtype(be)
-    c_dtype = store or torch.float32
+    assert not mixed or (store is not None and family == "A")
+    c_dtype = torch.float32 if mixed else store or torch.float32
+    ca_dtype = store or torch.float32
     ldc = g.N + ld_extra
     what = f"{what}{case} family {family}"
     T = be.igemm_stat_tiles(*g.dims, **({"planes": True} if planes else {"all16": True} if all16 else {}))
     prep = prep or (lambda a, b: (a, b))
 
     def launch(A, Bp, bias, act, want_stats):
-        a, b = prep(_dev(A.to(store) if store else A, dev), _dev(Bp, dev))
+        a, b = prep(_dev(A.to(store) if store and g.mode != IM2COL3 else A, dev), _dev(Bp, dev))
         C = Guarded(g.rows, g.N, c_dtype, dev, ldc)
-        Ca = Guarded(g.rows, g.N, c_dtype, dev, ldc) if act else None
+        Ca = Guarded(g.rows, g.N, ca_dtype, dev, ldc) if act else None
         st = Guarded(g.G * T * 2, g.N, torch.float32, dev) if want_stats else None
         be.igemm_nt(a, b, _dev(bias, dev), C.t, Ca.t if act else None, st.view(g.G, T, 2, g.N) if want_stats else None, None,
                     *g.dims, ldc, g.stride, g.offset, act, 1)
@@ -264,7 +271,12 @@ def run_igemm(be, dev, case, family, ld_extra=0, store=None, prep=None, planes=F
     key = (tuple(case), family, store, h)
     if key not in _JOBS:
         _JOBS[key] = igemm_jobs(g, family, store, h)
-    for A, Bp, bias, act, want_stats, ref, label in _JOBS[key]:
+    jobs = _JOBS[key]
+    if mixed:       # the job with a second output, with its bias and without (the specialised first-layer kernel declines a bias)
+        jobs = [j for j in jobs if j[3]]
+        jobs = jobs + [(A, Bp, None, act, ws_, ref - bias, label + ", bias dropped") for A, Bp, bias, act, ws_, ref, label in jobs]
+        assert len(jobs) == 2 and float(jobs[1][5].abs().max()) <= INT_MAX_16[store]
+    for A, Bp, bias, act, want_stats, ref, label in jobs:
         C, Ca, st = launch(A, Bp.to(store) if all16 else Bp, bias, act, want_stats)
         check_exact(C.values(), ref, f"{what}: C ({label})", bitwise=family == "B")
         if Ca is not None:
@@ -272,7 +284,7 @@ def run_igemm(be, dev, case, family, ld_extra=0, store=None, prep=None, planes=F
         if st is not None:
             check_exact(st.values().double().reshape(g.G, T, 2, g.N).sum(1).reshape(-1, g.N), stats_ref(g, ref.double()).reshape(-1, g.N),
                         f"{what}: stats summed over the {T} tiles, rows (group, sum | sum of squares)")
-    return len(_JOBS[key])
+    return len(jobs)
 
 
 _JOBS = {}      # (case, family, storage type, operand type) -> the launches of the case with their references, shared by the routes
@@ -295,15 +307,17 @@ def igemm_jobs(g, family, store, h):
     return [(A, Bp, None, 0, False, select_ref(g, Ar, tap, ci, scale), f"weight set {s}") for s, (Bp, tap, ci, scale) in enumerate(sets)]
 
 
-def run_dgrad_relu(be, dev, case, what=""):
-    """mmdyn_igemm_nt_dgrad_act with ReLU on integers: C = acc * [u > 0], u an integer tensor that contains zeros."""
+def run_dgrad_relu(be, dev, case, store=None, what=""):
+    """mmdyn_igemm_nt_dgrad_act with ReLU on integers: C = acc * [u > 0], u an integer tensor that contains zeros.  store: A, u and
+    C are stored in that 16-bit type (thinned {-1, 0, 1} operands, so that every |C| stays an exact integer of the type)."""
     g = Geo(case)
-    A, Bp = int_operands(g, 21, sparse=False)
-    ref = assert_int_exact(g, A, Bp)
+    A, Bp = int_operands(g, 21, sparse=store is not None)
+    ref = assert_int_exact(g, A, Bp, out16=store)
     u = ints((g.rows, g.N), 23, 2)
     assert bool((u == 0).any())
-    C = Guarded(g.rows, g.N, torch.float32, dev)
-    be.igemm_nt_dgrad_act(_dev(A, dev), _dev(Bp, dev), C.t, _dev(u, dev), 2, *g.dims, g.stride, g.offset)
+    cast = (lambda t: t.to(store)) if store else (lambda t: t)
+    C = Guarded(g.rows, g.N, store or torch.float32, dev)
+    be.igemm_nt_dgrad_act(_dev(cast(A), dev), _dev(Bp, dev), C.t, _dev(cast(u), dev), 2, *g.dims, g.stride, g.offset)
     C.check(f"{what}{case}: dgrad_act C")
     check_exact(C.values(), ref * (u > 0), f"{what}{case}: dgrad_act (ReLU) C")
 
@@ -336,14 +350,18 @@ def run_splitk(be, dev, rows, K, N, splitk, family, what=""):
             check_exact(Ca.values(), want.clamp_min(0), f"{what}: C_act (ReLU)")
 
 
-def run_grouped(be, dev, G, rows, K, N, family, what=""):
-    """mmdyn_igemm_nt_grouped: every group multiplies its OWN weights (a wrong b_group_stride shows) and adds its own bias."""
-    what = f"{what}grouped G={G} rows={rows} K={K} N={N} family {family}"
+def run_grouped(be, dev, G, rows, K, N, family, store=None, what=""):
+    """mmdyn_igemm_nt_grouped: every group multiplies its OWN weights (a wrong b_group_stride shows) and adds its own bias.
+    store: A, C and C_act are stored in that 16-bit type (family A then draws from {-1, 0, 1})."""
+    what = f"{what}grouped G={G} rows={rows} K={K} N={N} family {family}" + (f" {store}" if store else "")
     g1 = Geo((DENSE, 1, rows, 1, K, 1, N, 1, 0))
     h = operand_dtype(be)
+    cast = (lambda t: t.to(store)) if store else (lambda t: t)
     if family == "A":
-        A, Bp, bias = ints((G * rows, K), 41), ints((G, N, K), 42), ints((G, N), 43, 5)
-        want = torch.cat([assert_int_exact(g1, A[i * rows:(i + 1) * rows], Bp[i], bias=bias[i]) for i in range(G)])
+        mag = 1 if store else 3
+        A, Bp, bias = ints((G * rows, K), 41, mag), ints((G, N, K), 42, mag), ints((G, N), 43, 1 if store else 5)
+        want = torch.cat([assert_int_exact(g1, A[i * rows:(i + 1) * rows], Bp[i], bias=bias[i], out16=store) for i in range(G)])
+        assert G == 1 or not torch.equal(Bp[0], Bp[1])
         jobs = [(Bp, bias, want)]
     else:
         A = arbitrary((G * rows, K), 44, BINADES[h])
@@ -354,9 +372,9 @@ def run_grouped(be, dev, G, rows, K, N, family, what=""):
             jobs.append((torch.stack([p[0][0] for p in per]), None,
                          torch.cat([select_ref(g1, Ar[i * rows:(i + 1) * rows], *per[i][1:]) for i in range(G)])))
     for Bp, bias, want in jobs:
-        C = Guarded(G * rows, N, torch.float32, dev)
-        Ca = Guarded(G * rows, N, torch.float32, dev) if family == "A" else None
-        be.igemm_nt_grouped(_dev(A, dev), _dev(Bp, dev), _dev(bias, dev), C.t, Ca.t if Ca else None, None, G, rows, K, N, 2)
+        C = Guarded(G * rows, N, store or torch.float32, dev)
+        Ca = Guarded(G * rows, N, store or torch.float32, dev) if family == "A" else None
+        be.igemm_nt_grouped(_dev(cast(A), dev), _dev(Bp, dev), _dev(bias, dev), C.t, Ca.t if Ca else None, None, G, rows, K, N, 2)
         C.check(f"{what}: C")
         check_exact(C.values(), want, f"{what}: C", bitwise=family == "B")
         if Ca:
@@ -467,15 +485,11 @@ def wgrad_select_ref(w, D=None, row=None, Gt=None, pix=None, scale=None):
     return torch.where(ok[:, :, None], v * scale[None, :, None], torch.zeros(())).permute(0, 2, 1)
 
 
-def run_wgrad(be, dev, case, family, prep=None, planes=(False, False), what=""):
-    """mmdyn_wgrad_tn (partial summed over the chunks on the host in fp64), then mmdyn_wgrad_reduce with the case's permutation and
-    cg_canon, beta = 0 and the accumulate form."""
-    w = WGeo(case)
-    h = operand_dtype(be) if w.mode != IM2COL3 else None
-    what = f"{what}{case} family {family}"
-    prep = prep or (lambda d, g: (d, g))
-    chunks = be.wgrad_chunks(w.mode, w.rows, w.Cd, w.Cg, planes) if any(planes) else be.wgrad_chunks(w.mode, w.rows, w.Cd, w.Cg)
-    assert chunks % 4 == 0
+_WJOBS = {}     # (case, family, operand type) -> the launches of a weight-gradient case with their references, built once
+
+
+def wgrad_jobs(w, family, h):
+    """[(D, Gt, reference [taps][Cd][Cg])] of one case; h: the type the arbitrary operand of family B is rounded to."""
     if family == "A":
         D, Gt = ints((w.rows, w.Cd), 51), ints(w.g_shape, 52)
         mag = wgrad_ref(w, D.abs(), Gt.abs())
@@ -485,6 +499,8 @@ def run_wgrad(be, dev, case, family, prep=None, planes=(False, False), what=""):
         jobs = []
         Gt, D = arbitrary(w.g_shape, 53, BINADES[h]), arbitrary((w.rows, w.Cd), 54, BINADES[h])
         r16 = (lambda t: t.to(h).float()) if h is not None else (lambda t: t)
+        if w.mode == IM2COL3:
+            Gt = r16(Gt)
         for s in range(2):
             Ds, row, sc = onehot_rows(w, s)
             jobs.append((Ds, Gt, wgrad_select_ref(w, Gt=r16(Gt), row=row, scale=sc)))
@@ -494,6 +510,28 @@ def run_wgrad(be, dev, case, family, prep=None, planes=(False, False), what=""):
             jobs.append((D, Gs, wgrad_select_ref(w, D=r16(D), pix=pix, scale=sc)))
         hit = torch.cat([j[0].nonzero()[:, 0] for j in jobs if j[1] is Gt])     # the one-hot rows reach both ends of the row range
         assert int(hit.min()) <= w.rows // 4 and int(hit.max()) >= 3 * (w.rows - 1) // 4
+    return jobs
+
+
+def run_wgrad(be, dev, case, family, prep=None, planes=(False, False), store=(None, None), what=""):
+    """mmdyn_wgrad_tn (partial summed over the chunks on the host in fp64), then mmdyn_wgrad_reduce with the case's permutation and
+    cg_canon, beta = 0 and the accumulate form.  store = (type of D, type of Gt) in HBM, None: fp32 -- both 16-bit, D only or Gt
+    only (under "bf16s" / "fp16s" the six storage instances of wgrad_tn.hip; MMDYN_IM2COL3 takes a 16-bit D only, its gathered
+    operand is the fp32 image).  Integers up to 3 and +-2^k are exact in either type; the arbitrary operand of family B is the
+    RNE-rounded one whichever operand is stored in 16 bits, as in the 16-bit matrix-core modes."""
+    w = WGeo(case)
+    assert store[1] is None or w.mode != IM2COL3
+    h = operand_dtype(be) if w.mode != IM2COL3 else store[0]        # (a 16-bit D: the image may or may not be rounded on the way
+    what = f"{what}{case} family {family}" + (f" store {store}" if any(store) else "")     # into the matrix cores -- it is given rounded)
+    assert all(s in (None, operand_dtype(be)) for s in store)
+    to_store = lambda d, g: (d.to(store[0]) if store[0] else d, g.to(store[1]) if store[1] else g)
+    prep = prep or to_store
+    chunks = be.wgrad_chunks(w.mode, w.rows, w.Cd, w.Cg, planes) if any(planes) else be.wgrad_chunks(w.mode, w.rows, w.Cd, w.Cg)
+    assert chunks % 4 == 0
+    key = (tuple(case), family, h if family == "B" else None)
+    if key not in _WJOBS:
+        _WJOBS[key] = wgrad_jobs(w, family, h)
+    jobs = _WJOBS[key]
     bitwise = family == "B"
     for k, (D, Gt, want) in enumerate(jobs):
         d, gt = prep(_dev(D, dev), _dev(Gt, dev))
@@ -518,9 +556,11 @@ def wgrad_pairs(cases):
     return [(c, f) for c in cases for f in ("A", "B")]
 
 
-def run_wgrad_grouped(be, dev, G, rows, Cd, Cg, family, what=""):
-    """mmdyn_wgrad_tn_grouped: partial [chunks][G][Cd][Cg], one reduce over Cd' = G * Cd."""
-    what = f"{what}grouped wgrad G={G} rows={rows} Cd={Cd} Cg={Cg} family {family}"
+def run_wgrad_grouped(be, dev, G, rows, Cd, Cg, family, store=(None, None), what=""):
+    """mmdyn_wgrad_tn_grouped: partial [chunks][G][Cd][Cg], one reduce over Cd' = G * Cd.  store = (type of D, type of Gt) in HBM
+    as in run_wgrad; the grouped launch takes ONE 16-bit operand (both: MMDYN_ERR_SHAPE, include/mmdyn_hip.h)."""
+    what = f"{what}grouped wgrad G={G} rows={rows} Cd={Cd} Cg={Cg} family {family}" + (f" store {store}" if any(store) else "")
+    assert all(s in (None, operand_dtype(be)) for s in store) and not all(store)
     w = WGeo((DENSE, rows, 1, Cd, 1, Cg, 1, 0, None, 0))
     h = operand_dtype(be)
     chunks = be.wgrad_chunks(DENSE, rows, Cd, Cg)
@@ -535,7 +575,8 @@ def run_wgrad_grouped(be, dev, G, rows, Cd, Cg, family, what=""):
         D = torch.cat([p[0] for p in per])
         want = torch.cat([wgrad_select_ref(w, Gt=Gr[i * rows:(i + 1) * rows], row=per[i][1], scale=per[i][2]) for i in range(G)])
     P = Guarded(chunks * G * Cd, Cg, torch.float32, dev)
-    be.wgrad_tn_grouped(_dev(D, dev), _dev(Gt, dev), P.view(chunks, G, Cd, Cg), G, rows, Cd, Cg, chunks)
+    be.wgrad_tn_grouped(_dev(D.to(store[0]) if store[0] else D, dev), _dev(Gt.to(store[1]) if store[1] else Gt, dev),
+                        P.view(chunks, G, Cd, Cg), G, rows, Cd, Cg, chunks)
     P.check(f"{what}: partial")
     check_exact(P.values().double().reshape(chunks, G * Cd, Cg).sum(0).float(), want.reshape(G * Cd, Cg), f"{what}: partial summed",
                 bitwise=family == "B")
@@ -546,16 +587,19 @@ def run_wgrad_grouped(be, dev, G, rows, Cd, Cg, family, what=""):
 
 
 # ---- direct kernels -------------------------------------------------------------------------------------------------------------
-def run_tconv_out3(be, dev, Bt, Hi, Wi, family, what=""):
-    """mmdyn_tconv_out3_fwd: ConvTranspose2d(32, 3, 4, 2, 1) of an NHWC activation, NCHW logits."""
-    what = f"{what}tconv_out3_fwd Bt={Bt} {Hi}x{Wi} family {family}"
+def run_tconv_out3(be, dev, Bt, Hi, Wi, family, store=None, what=""):
+    """mmdyn_tconv_out3_fwd: ConvTranspose2d(32, 3, 4, 2, 1) of an NHWC activation, NCHW logits.  store: the activation is stored
+    in that 16-bit type (mmdyn_tconv_out3_fwd_b16; the arbitrary activation of family B is then one of its values); weights and
+    logits stay fp32."""
+    what = f"{what}tconv_out3_fwd Bt={Bt} {Hi}x{Wi} family {family}" + (f" {store}" if store else "")
     if family == "A":
         a, ws = ints((Bt * Hi * Wi, 32), 71), [ints((32, 3, 4, 4), 72)]
         x = a.double().reshape(Bt, Hi, Wi, 32).permute(0, 3, 1, 2)
         assert float(F.conv_transpose2d(x.abs(), ws[0].double().abs(), stride=2, padding=1).max()) < LIMIT
         wants = [F.conv_transpose2d(x, ws[0].double(), stride=2, padding=1)]
     else:                              # output channel co of weight set s selects one (ci, kh, kw): co + 3 s covers the 16 taps in 6 sets
-        a, ws, wants = arbitrary((Bt * Hi * Wi, 32), 73), [], []
+        a, ws, wants = arbitrary((Bt * Hi * Wi, 32), 73, BINADES[store]), [], []
+        a = a.to(store).float() if store else a
         g = Geo((TCONV_S2P1, 1, Bt, Hi, Wi, 32, 2 * Hi, 2 * Wi, 3, 1, 0))
         taps = set()
         for s in range(6):
@@ -568,7 +612,7 @@ def run_tconv_out3(be, dev, Bt, Hi, Wi, family, what=""):
         assert len(taps) == 16
     for w, want in zip(ws, wants):
         out = Guarded(Bt * 3 * 2 * Hi, 2 * Wi, torch.float32, dev)
-        be.tconv_out3_fwd(_dev(a, dev), _dev(w, dev), out.t, Bt, Hi, Wi)
+        be.tconv_out3_fwd(_dev(a.to(store) if store else a, dev), _dev(w, dev), out.t, Bt, Hi, Wi)
         out.check(f"{what}: out")
         check_exact(out.values(), want.reshape(-1, 2 * Wi), f"{what}: logits, rows (sample, channel, y)", bitwise=family == "B")
 
@@ -708,3 +752,28 @@ WGRAD_EXTRA = [
     (DENSE, 31, 1, 1, 64, 1, 1, 32, 1, 0, None, 0),
     (DENSE, 33, 1, 1, 32, 1, 1, 96, 1, 0, 80, 0),
 ]
+# ---- 16-bit stored operands ("bf16s" / "fp16s") -----------------------------------------------------------------------------------
+# weight gradient next to WGRAD_CASES[:7] of tests/test_kernels_gpu.py (channel tiles 128x128, 64x64, 64x32, 32x64, 32x32): the DENSE
+# cases of 1 / 31 / 33 rows, the non-square CONV cases and the MMDYN_IM2COL3 cases (16-bit D only; conv3.hip and the generic route)
+WGRAD_16 = WGRAD_EXTRA
+# G, rows, Cd, Cg / G, rows, K, N: the two smallest shapes of the fp32 tests and a ragged one
+WGRAD_GROUPED_16 = [(2, 1, 32, 32), (3, 100, 64, 32), (4, 33, 32, 96)]
+GROUPED_16 = [(2, 1, 32, 32), (3, 37, 64, 64), (4, 129, 512, 128)]
+TCONV_OUT3_16 = [(2, 16, 16), (1, 16, 32)]
+# one case per mode for the mixed-output form (fp32 C, 16-bit C_act)
+MIXED_OUT_CASES = [
+    (DENSE, 2, 50, 1, 32, 1, 64, 1, 0),
+    (CONV, 2, 3, 16, 64, 8, 128, 2, -1),
+    (TCONV_S2P1, 2, 3, 16, 64, 32, 32, 1, 0),
+    (TCONV_S1P0, 1, 5, 5, 256, 8, 128, 1, 0),
+] + IM2COL3_CASES
+
+
+def wgrad_store(which, t):
+    """(type of D, type of Gt) in HBM for `which` in "both" / "D" / "Gt"."""
+    return {"both": (t, t), "D": (t, None), "Gt": (None, t)}[which]
+
+
+def wgrad_store_triples(cases):
+    """(case, family, which): every storage combination the entry point takes -- MMDYN_IM2COL3 a 16-bit D only."""
+    return [(c, f, wh) for c in cases for f in ("A", "B") for wh in ("both", "D", "Gt") if c[0] != IM2COL3 or wh == "D"]

@@ -3,7 +3,9 @@ that tests/test_exact_gpu.py holds the kernels to are validated here, on a machi
 shares no code with them (EmuBackend gathers with torch indexing; the family A reference is fp64 ATen convolution, the family B
 reference index arithmetic).  Every comparison is `==` on values (family A) or on bits (family B); the guard rows around every
 output must keep their sentinel.  The last tests show the checks bite: a reference off by 1 (family A) or by one ulp (family B) in a
-single element, and a single overwritten guard element, are reported with their index."""
+single element, and a single overwritten guard element, are reported with their index; on the 16-bit stored paths, emulations
+that truncate their 16-bit stores, drop the last row of a ragged weight-gradient chunk or multiply every group of a grouped GEMM
+by the weights of group 0 are each reported."""
 import re
 
 import pytest
@@ -73,6 +75,55 @@ def test_igemm_16bit_storage(case, family, mode):
 @pytest.mark.parametrize("case", [IGEMM_CASES[2], IGEMM_CASES[5], IGEMM_CASES[8], IGEMM_CASES[12], X.NONSQUARE_CASES[3]])
 def test_dgrad_relu(case):
     X.run_dgrad_relu(EMU, DEV, case)
+
+
+# ---- 16-bit stored operands ("bf16s" / "fp16s"): the cases tests/test_exact_gpu.py runs, validated here --------------------------
+@pytest.fixture(params=["bf16s", "fp16s"])
+def storage(request):
+    """The storage type of the mode; the emulation rounds its matrix-core operands to it for the duration."""
+    EMU.precision = request.param
+    yield torch.float16 if request.param == "fp16s" else torch.bfloat16
+    EMU.precision = "fp32"
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("case", X.IM2COL3_CASES)
+def test_igemm_im2col3_16bit_output(case, family, storage):
+    X.run_igemm(EMU, DEV, case, family, store=storage)
+
+
+@pytest.mark.parametrize("case", X.MIXED_OUT_CASES)
+def test_igemm_mixed_output(case, storage):
+    X.run_igemm(EMU, DEV, case, "A", store=storage, mixed=True)
+
+
+@pytest.mark.parametrize("case", [IGEMM_CASES[2], IGEMM_CASES[5], IGEMM_CASES[8]])
+def test_dgrad_relu_16bit_storage(case, storage):
+    X.run_dgrad_relu(EMU, DEV, case, store=storage)
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("G,rows,K,N", X.GROUPED_16)
+def test_grouped_16bit_storage(G, rows, K, N, family, storage):
+    X.run_grouped(EMU, DEV, G, rows, K, N, family, store=storage)
+
+
+@pytest.mark.parametrize("case,family,which", X.wgrad_store_triples(WGRAD_CASES[:7] + X.WGRAD_16))
+def test_wgrad_16bit_storage(case, family, which, storage):
+    X.run_wgrad(EMU, DEV, case, family, store=X.wgrad_store(which, storage))
+
+
+@pytest.mark.parametrize("which", ["D", "Gt"])
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("G,rows,Cd,Cg", X.WGRAD_GROUPED_16)
+def test_wgrad_grouped_16bit_storage(G, rows, Cd, Cg, family, which, storage):
+    X.run_wgrad_grouped(EMU, DEV, G, rows, Cd, Cg, family, store=X.wgrad_store(which, storage))
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("Bt,Hi,Wi", X.TCONV_OUT3_16)
+def test_tconv_out3_16bit_activation(Bt, Hi, Wi, family, storage):
+    X.run_tconv_out3(EMU, DEV, Bt, Hi, Wi, family, store=storage)
 
 
 @pytest.mark.parametrize("family", FAMILIES)
@@ -182,3 +233,89 @@ def test_one_overwritten_guard_element_is_reported(where):
         C.check("guard")
     # ... also when the stray write stored the value the kernel would have computed next to it (any bit pattern but the sentinel's)
     assert int(bits(C.buf[C.front + i:C.front + i + 1])[0]) != int(bits(C.buf[:1])[0])
+
+
+# ---- ... and on the 16-bit stored paths: deliberately wrong emulations are reported ----------------------------------------------
+def _truncate(x, dtype):
+    """x -> dtype by dropping the low bits (round towards zero) instead of RNE."""
+    if dtype == torch.bfloat16:
+        return (x.contiguous().view(torch.int32) & -65536).view(torch.float32).to(dtype)
+    r = x.to(dtype)
+    over = r.float().abs() > x.abs()                       # RNE went away from zero: one step back
+    return torch.where(over, (r.view(torch.int16) - 1).view(dtype), r)
+
+
+class TruncatingStore(EmuBackend):
+    """Rounds what it stores into 16-bit tensors towards zero."""
+
+    @staticmethod
+    def _with_bf16(fn):
+        def wrapped(*args):
+            h16 = (torch.bfloat16, torch.float16)
+            conv = [a.float() if torch.is_tensor(a) and a.dtype in h16 else a for a in args]
+            r = fn(*conv)
+            for o, c in zip(args, conv):
+                if torch.is_tensor(o) and o.dtype in h16:
+                    o.copy_(_truncate(c, o.dtype))
+            return r
+        return wrapped
+
+
+class DropsLastRow(EmuBackend):
+    """A weight gradient that leaves out the last row of a chunk that does not fill its 32-row K-step."""
+
+    def __init__(self):
+        super().__init__()
+        inner = self.wgrad_tn
+
+        def wgrad_tn(D, Gt, partial, mode, Bt, Hr, Wr, Cd, *rest):
+            D = D.clone()
+            if (Bt * Hr * Wr) % 32:
+                D.reshape(Bt * Hr * Wr, Cd)[-1] = 0
+            return inner(D, Gt, partial, mode, Bt, Hr, Wr, Cd, *rest)
+        self.wgrad_tn = wgrad_tn
+
+
+class SharesGroupZeroWeights(EmuBackend):
+    """A grouped GEMM with b_group_stride = 0: every group multiplies the weights of group 0."""
+
+    def __init__(self):
+        super().__init__()
+        inner = self.igemm_nt_grouped
+
+        def igemm_nt_grouped(A, Bp, bias, C, C_act, u, G, rows, K, N, act):
+            return inner(A, Bp.reshape(G, N, K)[:1].expand(G, N, K).contiguous(), bias, C, C_act, u, G, rows, K, N, act)
+        self.igemm_nt_grouped = igemm_nt_grouped
+
+
+@pytest.mark.parametrize("mode", ["bf16s", "fp16s"])
+def test_a_truncating_16bit_store_is_reported(mode):
+    be, t = TruncatingStore(), torch.float16 if mode == "fp16s" else torch.bfloat16
+    be.precision = mode
+    X.run_igemm(be, DEV, X.IM2COL3_CASES[0], "A", store=t)                 # (integers are stored exactly either way)
+    with pytest.raises(AssertionError, match=r"C \(weight set 0\): \d+ of \d+ elements differ"):
+        X.run_igemm(be, DEV, X.IM2COL3_CASES[0], "B", store=t)
+    # (with a 16-bit A the selected element is a value of the type already and the store rounds nothing: the rounding mode of
+    #  those stores is pinned by rule 2 of tests/store16_cases.py)
+    X.run_igemm(be, DEV, IGEMM_CASES[9], "B", store=t)
+
+
+@pytest.mark.parametrize("which", ["both", "D", "Gt"])
+@pytest.mark.parametrize("mode", ["bf16s", "fp16s"])
+def test_a_weight_gradient_that_drops_the_last_row_of_a_ragged_chunk_is_reported(mode, which):
+    be, t = DropsLastRow(), torch.float16 if mode == "fp16s" else torch.bfloat16
+    be.precision = mode
+    X.run_wgrad(be, DEV, WGRAD_CASES[4], "A", store=X.wgrad_store(which, t))            # 768 rows: whole K-steps, nothing dropped
+    for case in (X.WGRAD_EXTRA[7], X.WGRAD_EXTRA[8], X.WGRAD_EXTRA[2]):                 # 31, 33 and 120 rows
+        with pytest.raises(AssertionError, match="partial summed over"):
+            X.run_wgrad(be, DEV, case, "A", store=X.wgrad_store(which, t))
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("mode", ["bf16s", "fp16s"])
+def test_a_grouped_gemm_on_the_weights_of_group_zero_is_reported(mode, family):
+    be, t = SharesGroupZeroWeights(), torch.float16 if mode == "fp16s" else torch.bfloat16
+    be.precision = mode
+    for shape in X.GROUPED_16:
+        with pytest.raises(AssertionError, match=r"C: \d+ of \d+ elements differ"):
+            X.run_grouped(be, DEV, *shape, family, store=t)

@@ -19,11 +19,21 @@ It hits the N = 64 cases under the forced 128 x 128 tile (they run under the for
   test_dgrad_relu_persistent: (DENSE, 2, 50, 1, 32, 1, 64, 1, 0), (TCONV_S2P1, 4, 33, 8, 128, 16, 64, 1, 0),
       (TCONV_S2P1, 1, 3, 8, 12, 128, 16, 24, 64, 1, 0).
 
-Not exact, and left with the tolerance tests of tests/test_kernels_gpu.py / tests/test_kernels_aten_gpu.py: the Swish epilogues
-(act = MMDYN_ACT_SWISH second output, mmdyn_igemm_nt_dgrad_act with Swish) and the BatchNorm-backward epilogue
-(mmdyn_igemm_nt_dgrad_bn, mmdyn_wgrad_out3_bn, mmdyn_tconv_out3_bn_fwd): they multiply by a sigmoid.  The fused last-layer loss
-kernels (mmdyn_tconv_out3_bn_bce, _bce_rows, _bce_rows_grad) evaluate log / exp per element and add into fp64 atomics: not covered
-here either.  The weight-gradient selection family runs both ways round (one-hot D, one-hot Gt) for the DENSE and CONV
+16-bit stored operands ("bf16s" / "fp16s", the *_16bit_* tests below): integers up to 256 (bf16) / 2048 (half) and +-2^k are exact
+in storage, so both families apply unchanged -- the weight gradient with both operands, D only or Gt only read as 16-bit values
+(the six storage instances of wgrad_tn.hip, wgrad_b16_kernel / wgrad_b16_tn4_kernel, conv3.hip's weight-gradient instances with
+a 16-bit D) on every channel tile, on 1 / 31 / 33 rows and on non-square extents; mmdyn_igemm_nt_grouped, mmdyn_wgrad_tn_grouped
+(one 16-bit operand: both is MMDYN_ERR_SHAPE, asserted), mmdyn_igemm_nt_dgrad_act (ReLU) and mmdyn_tconv_out3_fwd_b16; the
+MMDYN_IM2COL3 launch with a 16-bit C and the mixed-output form (fp32 C, 16-bit C_act) in every mode.
+
+Not exact, because they multiply by a sigmoid: the Swish epilogues (act = MMDYN_ACT_SWISH second output, mmdyn_igemm_nt_dgrad_act
+with Swish) and the BatchNorm-backward epilogue of mmdyn_igemm_nt_dgrad_bn.  They are held per element by
+tests/test_store16_gpu.py (rule of tests/store16_cases.py: half an ulp of the output type plus a measured multiple of 2^-24 of the
+largest intermediate, against the documented formula in fp64, on the integer operands of family A), with 16-bit and with fp32
+outputs, next to the 16-bit element-wise kernels (bn_swish_fwd / _bwd_reduce / _bwd_apply, act_bwd).  Still with the tolerance
+tests of tests/test_kernels_gpu.py / tests/test_kernels_aten_gpu.py only: mmdyn_wgrad_out3_bn and mmdyn_tconv_out3_bn_fwd, and the
+fused last-layer loss kernels (mmdyn_tconv_out3_bn_bce, _bce_rows, _bce_rows_grad), which evaluate log / exp per element and add
+into fp64 atomics.  The weight-gradient selection family runs both ways round (one-hot D, one-hot Gt) for the DENSE and CONV
 gathers; for MMDYN_IM2COL3, whose gathered operand is the NCHW image, with the one-hot D only.
 
 What reading the routes' address arithmetic for Hi != Wi found (before anything was launched):
@@ -35,7 +45,10 @@ What reading the routes' address arithmetic for Hi != Wi found (before anything 
     "Ho = Hi+3" and now states the refusal;
   - the patch-resident k4 s2 p1 kernel (tconv_patch.hip) and the 3-channel first / last-layer kernels (conv3.hip) decline
     Hi != Wi (return 1) and the launch falls back to the generic kernels: results exact through the fallback, asserted below.
-No kernel defect was found by these inputs.
+No kernel defect was found by these inputs.  Writing the mixed-output cases found one in the dispatch: an MMDYN_IM2COL3 launch of
+the mixed-output form without a bias was handed to the first-layer kernel of conv3.hip, which stores C and C_act in one type and
+would have written fp32 elements into the 16-bit C_act buffer (twice its size); the entry point now keeps that form on the
+generic kernels (test_igemm_mixed_output, with a bias and without).
 """
 import pytest
 import torch
@@ -204,6 +217,20 @@ def test_igemm_all16_persistent(case, family, wsp, store16, monkeypatch):
     igemm(case, family, store=K.S16, all16=True)
 
 
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("case", X.IM2COL3_CASES)
+def test_igemm_im2col3_16bit_output(case, family, store16):
+    """The first layer of the storage modes: fp32 NCHW image, 16-bit C (conv3.hip and the generic route)."""
+    igemm(case, family, store=K.S16)
+
+
+@pytest.mark.parametrize("case", X.MIXED_OUT_CASES)
+def test_igemm_mixed_output(case, store16):
+    """fp32 C + 16-bit C_act (storage flag bit 6), ReLU, with a bias and without.  The 3-channel first-layer kernel stores both
+    outputs in one type: the entry point keeps this form away from it (without a bias it used to be taken there)."""
+    igemm(case, "A", store=K.S16, mixed=True)
+
+
 # ---- epilogues, split-K, grouped -------------------------------------------------------------------------------------------------
 DGRAD = [IGEMM_CASES[2], IGEMM_CASES[3], IGEMM_CASES[5], IGEMM_CASES[6], IGEMM_CASES[8], (TCONV_S2P1, 1, 3, 16, 64, 32, 32, 1, 0)] + NOT_IM2COL3[:4]
 
@@ -223,6 +250,12 @@ def test_dgrad_relu_persistent(case, wsp):
     if X.Geo(case).N % int(wsp.split(",")[1]):
         pytest.skip("N is not a multiple of the forced tile width")
     X.run_dgrad_relu(K.HIP, DEV, case)
+
+
+@pytest.mark.parametrize("case", [DGRAD[0], DGRAD[2], DGRAD[4]])
+def test_dgrad_relu_16bit_storage(case, store16):
+    """A, u and C 16-bit in HBM, one case per mode."""
+    X.run_dgrad_relu(K.HIP, DEV, case, store=K.S16)
 
 
 SPLITK = [(256, 6400, 512, 25), (64, 512, 256, 3), (5, 64, 32, 2), (129, 6400, 256, 8)]
@@ -256,6 +289,12 @@ def test_grouped_bf16(G, rows, K_, N, family, bf16_mode):
     X.run_grouped(K.HIP, DEV, G, rows, K_, N, family)
 
 
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("G,rows,K_,N", X.GROUPED_16)
+def test_grouped_16bit_storage(G, rows, K_, N, family, store16):
+    X.run_grouped(K.HIP, DEV, G, rows, K_, N, family, store=K.S16)
+
+
 # ---- weight gradient -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case,family", X.wgrad_pairs(WGRAD_CASES[:7] + X.WGRAD_EXTRA))
 def test_wgrad(case, family):
@@ -265,6 +304,33 @@ def test_wgrad(case, family):
 @pytest.mark.parametrize("case,family", X.wgrad_pairs([WGRAD_CASES[0], WGRAD_CASES[4], WGRAD_CASES[6]] + X.WGRAD_EXTRA[:3]))
 def test_wgrad_bf16(case, family, bf16_mode):
     X.run_wgrad(K.HIP, DEV, case, family)
+
+
+@pytest.mark.parametrize("case,family,which", X.wgrad_store_triples(WGRAD_CASES[:7] + X.WGRAD_16))
+def test_wgrad_16bit_storage(case, family, which, store16):
+    """Operands read as 16-bit values from HBM: both (wgrad_b16_kernel / wgrad_b16_tn4_kernel and their transposing LDS reads), D
+    only or Gt only (the storage instances of wgrad_tn.hip), in both formats; MMDYN_IM2COL3 with a 16-bit D (conv3.hip's
+    weight-gradient instances and, for Hi != Wi or other extents, the generic route)."""
+    X.run_wgrad(K.HIP, DEV, case, family, store=X.wgrad_store(which, K.S16))
+
+
+@pytest.mark.parametrize("which", ["D", "Gt"])
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("G,rows,Cd,Cg", X.WGRAD_GROUPED_16)
+def test_wgrad_grouped_16bit_storage(G, rows, Cd, Cg, family, which, store16):
+    X.run_wgrad_grouped(K.HIP, DEV, G, rows, Cd, Cg, family, store=X.wgrad_store(which, K.S16))
+
+
+def test_wgrad_grouped_refuses_two_16bit_operands(store16):
+    """The grouped launch runs the register-staged kernel only: both operands 16-bit is MMDYN_ERR_SHAPE, nothing is launched."""
+    G, rows, Cd, Cg = X.WGRAD_GROUPED_16[0]
+    chunks = K.HIP.wgrad_chunks(DENSE, rows, Cd, Cg)
+    P = X.Guarded(chunks * G * Cd, Cg, torch.float32, DEV)
+    D, Gt = torch.zeros(G * rows, Cd, dtype=K.S16, device=DEV), torch.zeros(G * rows, Cg, dtype=K.S16, device=DEV)
+    with pytest.raises(MmdynError, match="MMDYN_ERR_SHAPE"):
+        K.HIP.wgrad_tn_grouped(D, Gt, P.view(chunks, G, Cd, Cg), G, rows, Cd, Cg, chunks)
+    torch.cuda.synchronize()
+    assert torch.equal(P.buf.cpu(), X.Guarded(chunks * G * Cd, Cg).buf)
 
 
 # mode, Bt, Hr, Wr, Cd, Hi, Wi, Cg, stride, offset: the tiles of test_weight_gradient_on_operands_that_arrive_split + a non-square one
@@ -293,6 +359,13 @@ def test_wgrad_grouped(G, rows, Cd, Cg, family):
 @pytest.mark.parametrize("Bt,Hi,Wi", [(2, 16, 16), (1, 16, 32), (1, 32, 16), (3, 32, 32), (1, 48, 16)])
 def test_tconv_out3_fwd(Bt, Hi, Wi, family):
     X.run_tconv_out3(K.HIP, DEV, Bt, Hi, Wi, family)
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+@pytest.mark.parametrize("Bt,Hi,Wi", X.TCONV_OUT3_16)
+def test_tconv_out3_fwd_16bit_activation(Bt, Hi, Wi, family, store16):
+    """mmdyn_tconv_out3_fwd_b16: the activation 16-bit in HBM, fp32 weights and logits."""
+    X.run_tconv_out3(K.HIP, DEV, Bt, Hi, Wi, family, store=K.S16)
 
 
 @pytest.mark.parametrize("family", FAMILIES)
