@@ -1457,16 +1457,18 @@ class MVAEInference:
                                                              training=False))
         return layers.heads_forward(self.P[key], h, self.pk[key[0] + "h"], cond=cond, x_rows=x_rows)[0]
 
+    @staticmethod
+    def _rows_of(visual, tactile, pose, avail):
+        """(B, device) of a request: from the first modality given, or from the table of a request of prior-only rows."""
+        ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
+        return ref.shape[0], ref.device
+
     def _forward(self, visual, tactile, pose, cond=None, avail=None, sample=True):
         with self._index_scope():
-            return self._forward_scoped(visual, tactile, pose, cond, avail, sample)
-
-    def _forward_scoped(self, visual, tactile, pose, cond, avail=None, sample=True):
-        ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
-        B = ref.shape[0]
-        heads = self._heads(visual, tactile, pose, cond)
-        mu, lv, z = self._poe(heads, avail, self._draw_latent(B) if sample else self._zero_latent(B), B, ref.device)
-        return self._decode(z, cond) + (mu, lv)
+            B, dev = self._rows_of(visual, tactile, pose, avail)
+            heads = self._heads(visual, tactile, pose, cond)
+            mu, lv, z = self._poe(heads, avail, self._draw_latent(B) if sample else self._zero_latent(B), B, dev)
+            return self._decode(z, cond) + (mu, lv)
 
     def _heads(self, visual, tactile, pose, cond, x_rows=None):
         """The fused (means | log_var) head outputs [B][2L] of the modalities given, None for the others.  ``x_rows`` = B with
@@ -1533,7 +1535,7 @@ class MVAEInference:
         return z
 
     # ---- graph capture / replay ---------------------------------------------------------------------------
-    def _run(self, key, fn, static_inputs, new_inputs):
+    def _run(self, key, fn, new_inputs):
         prev_act, prev_w = layers.ACT_DTYPE, layers.W_DTYPE
         prev = _select_precision(self.precision)
         layers.ACT_DTYPE = act_dtype(self.precision)
@@ -1575,14 +1577,46 @@ class MVAEInference:
         from .models.functional import availability_table
         return availability_table(available, B, self.dev)
 
-    @staticmethod
-    def _batch_of(ins, available):
+    def _request(self, who, x, pose, available, cast=False):
+        """The prologue of every request: ``x = [visual | None, tactile | None]`` and ``pose`` -> (three contiguous tensors / None,
+        the pose dropped for a model without one; B).  ``cast``: to fp32 as well, for the requests whose inputs come back in the
+        result.  ValueError when there is neither a modality nor a table to take B from."""
+        visual, tactile = x
+        if cast:
+            c = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        else:
+            c = lambda t: None if t is None else t.contiguous()
+        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
         ref = next((t for t in ins if t is not None), None)
         if ref is not None:
-            return ref.shape[0]
+            return ins, ref.shape[0]
         if available is None:
-            raise ValueError("a request needs at least one modality")
-        return len(available)                                  # a request of prior-only rows
+            raise ValueError(f"{who} needs at least one modality")
+        return ins, len(available)                             # a request of prior-only rows
+
+    @staticmethod
+    def _shapes(tensors, *tag, dtype=False):
+        """The shape part of a graph key: per tensor ``tag`` + (its dtype) + its shape, None for one that is not given."""
+        return tuple(None if t is None else tag + ((str(t.dtype),) if dtype else ()) + tuple(t.shape) for t in tensors)
+
+    @staticmethod
+    def _count(name, value, what):
+        """``value`` as an int; ValueError unless it is an integer >= 1 (no bool)."""
+        if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < 1:
+            raise ValueError(f"{name} must be an integer >= 1 (the number of {what}), got {value!r}")
+        return int(value)
+
+    def _decoder_row(self):
+        """Elements per row of the decoders' largest activation, the last hidden layer's [rows][32][S / 2][S / 2] (32 * 32 * 32 at
+        the reference's 64 x 64)."""
+        return 32 * (self.model.visual_decoder.image_size // 2) ** 2
+
+    @staticmethod
+    def _fits(name, count, unit, B, per_row, tensor, largest):
+        """The kernels index with 32-bit element offsets: ValueError when ``count`` * B rows of ``per_row`` elements reach 2^31."""
+        if count * B * per_row >= 1 << 31:
+            raise ValueError(f"{name} = {count} {unit}of B = {B} rows make a {tensor} of {count * B} x {per_row} elements, past 2^31; "
+                             f"the largest {largest} for B = {B} is {((1 << 31) - 1) // (B * per_row)}")
 
     @torch.no_grad()
     def forward(self, x, pose=None, condition=None, available=None):
@@ -1602,18 +1636,13 @@ class MVAEInference:
         may hold anything finite.  The table is one more static input of the captured graph: the key carries its presence, not
         its contents, so one graph serves every mixture of a batch shape, with the launches of the joint request (the PoE launch
         is replaced one for one).  The values are not inspected and nothing synchronises; wrong shape / dtype: ValueError."""
-        visual, tactile = x
-        c = lambda t: None if t is None else t.contiguous()
-        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        if all(t is None for t in ins) and available is None:
-            raise ValueError("forward needs at least one modality")
-        B = self._batch_of(ins, available)
+        ins, B = self._request("forward", x, pose, available)
         cond = self._condition(condition, B)
-        key = ("fwd",) + tuple(None if t is None else tuple(t.shape) for t in ins) + (self._cond_key(cond),)
+        key = ("fwd",) + self._shapes(ins) + (self._cond_key(cond),)
         if available is None:
-            return self._run(key, self._forward, None, ins + [cond])
+            return self._run(key, self._forward, ins + [cond])
         avail = self._availability(available, B)
-        return self._run(key + (("avail",) + tuple(avail.shape),), self._forward, None, ins + [cond, avail])
+        return self._run(key + self._shapes([avail], "avail"), self._forward, ins + [cond, avail])
 
     __call__ = forward
 
@@ -1627,9 +1656,39 @@ class MVAEInference:
         B = mu.shape[0]
         bce, mse, kl = torch.zeros(3, 2, B, dtype=torch.float64, device=mu.device)
         rows = self._score_tail(v, t, pr, mu, lv, tv, tt, tp, mask, tavail, bce, mse, kl)
-        return {"rows": rows, "bce_visual": bce[0] if tv is not None else None, "bce_tactile": bce[1] if tt is not None else None,
-                "mse_pose": mse[0] if tp is not None else None, "kl": kl[0],
-                "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
+        return {"rows": rows, **self._terms((bce[0], bce[1], mse[0]), (tv, tt, tp), (v, t, pr)), "kl": kl[0], "means": mu, "log_var": lv}
+
+    def _terms(self, tables, targets, recon=None):
+        """The per-term part of a result dict: each term's table, None for a term without a target; with ``recon`` = (visual
+        logits, tactile logits, pose output) also ``recon_x``."""
+        res = {k: tab if tg is not None else None for k, tab, tg in zip(("bce_visual", "bce_tactile", "mse_pose"), tables, targets)}
+        if recon is not None:
+            res["recon_x"] = list(recon[:2]) + ([recon[2]] if self.use_pose else [])
+        return res
+
+    def _row_terms(self, G, B, v, t, pr, tv, tt, tp, mask, tables):
+        """The row kernels with G passes of B rows against the one target: pass g reads rows [g * B, (g + 1) * B) of the logits / the
+        pose output and adds into slot g of ``tables`` = (visual, tactile, pose), each fp64 [G][B] and zeroed; ops.ROW_GROUPS_MAX
+        passes per launch.  A term without a target is left out."""
+        chw, hw = v[0].numel(), v[0, 0].numel()
+        mc = 1 if mask is None else mask.shape[1]
+        for g0 in range(0, G, ops.ROW_GROUPS_MAX):
+            slots = list(range(g0, min(G, g0 + ops.ROW_GROUPS_MAX)))
+            rows_of = slice(g0 * B, (slots[-1] + 1) * B)
+            for lg, tg, tab in ((v, tv, tables[0]), (t, tt, tables[1])):
+                if tg is not None:
+                    ops.B.bce_logits_rows_groups(lg[rows_of], tg, tab, slots, B, chw, mask=mask, hw=hw, mask_channels=mc)
+            if tp is not None:
+                ops.B.mse_rows_groups(pr[rows_of], tp, tables[2], slots, B, tp.shape[1])
+
+    def _assemble(self, bce, mse, kl, rows, tavail, B):
+        """The assembly launch of B rows from their fp64 [2][B] tables; ``tavail``: its sibling -- a (row, term) whose target is absent
+        leaves the row sum and its table entry becomes 0."""
+        if tavail is None:
+            ops.B.elbo_assemble_rows(bce, mse, kl, None, rows, None, 2, B, 1.0, self._pose_multiplier, self._klw, 1)
+        else:
+            ops.B.elbo_assemble_rows_avail(bce, mse, kl, None, rows, None, tavail, [0, 1], [2, -1], 2, B, 1.0,
+                                           self._pose_multiplier, self._klw, 1)
 
     def _score_tail(self, v, t, pr, mu, lv, tv, tt, tp, mask, tavail, bce, mse, kl, rows=None):
         """The row kernels and the assembly of one pass into the (zeroed) fp64 [2][B] tables of :meth:`_score`; ``rows``: the fp32 [B]
@@ -1645,11 +1704,7 @@ class MVAEInference:
         ops.B.kl_rows(mu, lv, kl[0:1], 1, B, L)
         if rows is None:
             rows = torch.empty(B, device=mu.device)
-        if tavail is None:
-            ops.B.elbo_assemble_rows(bce, mse, kl, None, rows, None, 2, B, 1.0, self._pose_multiplier, self._klw, 1)
-        else:       # the assembly's sibling: a (row, term) whose target is absent leaves the row sum and its table entry becomes 0
-            ops.B.elbo_assemble_rows_avail(bce, mse, kl, None, rows, None, tavail, [0, 1], [2, -1], 2, B, 1.0,
-                                           self._pose_multiplier, self._klw, 1)
+        self._assemble(bce, mse, kl, rows, tavail, B)
         return rows
 
     def _iw_score(self, K, self_target, visual, tactile, pose, tv, tt, tp, mask, cond=None, avail=None, tavail=None):
@@ -1660,8 +1715,7 @@ class MVAEInference:
         replays."""
         iw_latent, iw_assemble_rows = ops.backend_op("iw_latent"), ops.backend_op("iw_assemble_rows")
         with self._index_scope():
-            ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
-            B, L, dev = ref.shape[0], self.L, ref.device
+            (B, dev), L = self._rows_of(visual, tactile, pose, avail), self.L
             mu, lv, _ = self._poe(self._heads(visual, tactile, pose, cond), avail, None, B, dev)
             eps = self.noise.eps((K, B, L), dev)
             self.noise.commit()
@@ -1674,24 +1728,14 @@ class MVAEInference:
             tv, tt, tp = visual, tactile, pose if self.use_pose else None
         tab = torch.zeros(3, K, B, dtype=torch.float64, device=dev)
         kl = torch.empty(1, B, dtype=torch.float64, device=dev)
-        chw, hw = v[0].numel(), v[0, 0].numel()
-        mc = 1 if mask is None else mask.shape[1]
-        for g0 in range(0, K, ops.ROW_GROUPS_MAX):
-            slots = list(range(g0, min(K, g0 + ops.ROW_GROUPS_MAX)))
-            rows_of = slice(g0 * B, (slots[-1] + 1) * B)
-            for slot, (lg, tg) in enumerate(((v, tv), (t, tt))):
-                if tg is not None:
-                    ops.B.bce_logits_rows_groups(lg[rows_of], tg, tab[slot], slots, B, chw, mask=mask, hw=hw, mask_channels=mc)
-            if tp is not None:
-                ops.B.mse_rows_groups(pr[rows_of], tp, tab[2], slots, B, tp.shape[1])
+        self._row_terms(K, B, v, t, pr, tv, tt, tp, mask, tab)
         ops.B.kl_rows(mu, lv, kl, 1, B, L)
         rows, ess = torch.empty(B, device=dev), torch.empty(B, device=dev)
         log_w = torch.empty(K, B, dtype=torch.float64, device=dev)
         iw_assemble_rows(tab[:2] if tv is not None or tt is not None else None, tab[2] if tp is not None else None, ratio, tavail,
                          rows, ess, log_w, K, B, self._pose_multiplier, 1.0, self._klw)
-        return {"rows": rows, "ess": ess, "log_w": log_w, "ratio": ratio, "bce_visual": tab[0] if tv is not None else None,
-                "bce_tactile": tab[1] if tt is not None else None, "mse_pose": tab[2] if tp is not None else None, "kl": kl[0],
-                "recon_x": [v, t] + ([pr] if self.use_pose else []), "means": mu, "log_var": lv}
+        return {"rows": rows, "ess": ess, "log_w": log_w, "ratio": ratio, **self._terms(tab, (tv, tt, tp), (v, t, pr)), "kl": kl[0],
+                "means": mu, "log_var": lv}
 
     def _targets(self, what, given, B):
         """``targets`` of :meth:`score` / ``goal`` of :meth:`plan`: [visual | None, tactile | None, pose | None] -> three contiguous
@@ -1754,42 +1798,29 @@ class MVAEInference:
         target, an absent (row, term) 0 in all K entries); ``kl``: the analytic KL, fp64 [B]; ``means`` / ``log_var``; ``recon_x``:
         the logits of the K * B rows, draw-major.  Captured and replayed under a key that carries K; everything else as above.
         ValueError: K < 1 or no integer, or K * B rows of the largest decoder activation reaching 2^31 elements."""
-        visual, tactile = x
-        c = lambda t: None if t is None else t.contiguous()
-        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        if all(t is None for t in ins) and available is None:
-            raise ValueError("score needs at least one modality")
-        B = self._batch_of(ins, available)
+        ins, B = self._request("score", x, pose, available)
         if samples is not None:
-            if isinstance(samples, bool) or not isinstance(samples, numbers.Integral) or samples < 1:
-                raise ValueError(f"samples must be an integer >= 1 (the number of latent draws per row), got {samples!r}")
-            samples = int(samples)
-            # the decoders index their activations with 32-bit element offsets; the largest is the last hidden layer's
-            # [K * B][32][S / 2][S / 2] (32 * 32 * 32 per row at the reference's 64 x 64)
-            per_row = 32 * (self.model.visual_decoder.image_size // 2) ** 2
-            if samples * B * per_row >= 1 << 31:
-                raise ValueError(f"samples = {samples} draws of B = {B} rows make a decoder activation of {samples * B} x {per_row} "
-                                 f"elements, past 2^31; the largest samples for B = {B} is {((1 << 31) - 1) // (B * per_row)}")
+            samples = self._count("samples", samples, "latent draws per row")
+            self._fits("samples", samples, "draws ", B, self._decoder_row(), "decoder activation", "samples")
         cond = self._condition(condition, B)
         self_target = targets is None
         tg = [None] * 3 if self_target else self._targets("target", targets, B)
         loss_mask = self._loss_mask(loss_mask, (ins[2] is not None) if self_target else (tg[2] is not None), B, "score", "target")
         self._set_weights(kl_weight, pose_multiplier)
         args = ins + tg + [loss_mask]
-        key = ("score", self_target, self._pose_multiplier) + tuple(None if t is None else tuple(t.shape) for t in args)
-        key, args = key + (self._cond_key(cond),), args + [cond]
+        key = ("score", self_target, self._pose_multiplier) + self._shapes(args) + (self._cond_key(cond),)
+        args = args + [cond]
         if samples is None:
-            fn = lambda *a: self._score(self_target, *a)
+            fn, tail = (lambda *a: self._score(self_target, *a)), ()
         else:
-            fn = lambda *a: self._iw_score(samples, self_target, *a)
+            fn, tail = (lambda *a: self._iw_score(samples, self_target, *a)), (("samples", samples),)
         if available is None and target_available is None:
-            return self._run(key if samples is None else key + (("samples", samples),), fn, None, args)
+            return self._run(key + tail, fn, args)
         avail = self._availability(available, B)
         if target_available is None and self_target:
             target_available = available
         tavail = self._availability(target_available, B)
-        key = key + tuple(None if t is None else ("avail",) + tuple(t.shape) for t in (avail, tavail))
-        return self._run(key if samples is None else key + (("samples", samples),), fn, None, args + [avail, tavail])
+        return self._run(key + self._shapes((avail, tavail), "avail") + tail, fn, args + [avail, tavail])
 
     def _complete(self, sample, visual, tactile, pose, cond, avail):
         """One (mixed) forward, then one select launch per returned modality."""
@@ -1812,18 +1843,12 @@ class MVAEInference:
         posterior mean (eps = 0); ``sample=True`` draws from the engine's Philox stream like :meth:`forward`.  Captured and
         replayed under a key of its own: the launches of :meth:`forward` plus one select launch per returned modality.  The
         tensors are the graph's static outputs; nothing synchronises."""
-        visual, tactile = x
-        c = lambda t: None if t is None else t.to(torch.float32).contiguous()
-        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        if all(t is None for t in ins) and available is None:
-            raise ValueError("complete needs at least one modality")
-        B = self._batch_of(ins, available)
+        ins, B = self._request("complete", x, pose, available, cast=True)
         cond = self._condition(condition, B)
         avail = self._availability(available, B)
         sample = bool(sample)
-        key = ("complete", sample) + tuple(None if t is None else tuple(t.shape) for t in ins) + \
-            (self._cond_key(cond), None if avail is None else ("avail",) + tuple(avail.shape))
-        return self._run(key, lambda *a: self._complete(sample, *a), None, ins + [cond, avail])
+        key = ("complete", sample) + self._shapes(ins) + (self._cond_key(cond),) + self._shapes([avail], "avail")
+        return self._run(key, lambda *a: self._complete(sample, *a), ins + [cond, avail])
 
     def _candidates(self, candidates, B):
         """The request's candidate conditions laid out candidate-major for the kernels: (fp32 [N * B][condition_dim], or int64
@@ -1866,8 +1891,7 @@ class MVAEInference:
         plan_select, gather_best = ops.backend_op("plan_select"), ops.backend_op("gather_best")
         ops.backend_op("concat_condition_tiled")        # (a backend without the join: an error before anything is launched)
         with self._index_scope():
-            ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
-            B, L, dev = ref.shape[0], self.L, ref.device
+            (B, dev), L = self._rows_of(visual, tactile, pose, avail), self.L
             heads = self._heads(visual, tactile, pose, cand, x_rows=B)
             if heads[2] is not None:
                 heads[2] = heads[2].repeat(N, 1)
@@ -1876,16 +1900,7 @@ class MVAEInference:
             v, t, pr = self._decode(z, cand)
         tab = torch.zeros(3, N, B, dtype=torch.float64, device=dev)
         kl = torch.empty(N, B, dtype=torch.float64, device=dev)
-        chw, hw = v[0].numel(), v[0, 0].numel()
-        mc = 1 if mask is None else mask.shape[1]
-        for g0 in range(0, N, ops.ROW_GROUPS_MAX):
-            slots = list(range(g0, min(N, g0 + ops.ROW_GROUPS_MAX)))
-            rows_of = slice(g0 * B, (slots[-1] + 1) * B)
-            for slot, (lg, tg) in enumerate(((v, gv), (t, gt))):
-                if tg is not None:
-                    ops.B.bce_logits_rows_groups(lg[rows_of], tg, tab[slot], slots, B, chw, mask=mask, hw=hw, mask_channels=mc)
-            if gp is not None:
-                ops.B.mse_rows_groups(pr[rows_of], gp, tab[2], slots, B, gp.shape[1])
+        self._row_terms(N, B, v, t, pr, gv, gt, gp, mask, tab)
         ops.B.kl_rows(mu, lv, kl.view(1, N * B), 1, N * B, L)
         cost, best, best_cost = torch.empty(N, B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev)
         best_cond = torch.empty((B,) + tuple(cand.shape[1:]), dtype=cand.dtype, device=dev)
@@ -1898,9 +1913,7 @@ class MVAEInference:
         gather_best(groups, best, N, B)
         return {"cost": cost, "best": best, "best_cost": best_cost, "best_condition": best_cond,
                 "prediction": [g["out"] for g in groups] + ([] if self.use_pose else [None]),
-                "bce_visual": tab[0] if gv is not None else None, "bce_tactile": tab[1] if gt is not None else None,
-                "mse_pose": tab[2] if gp is not None else None, "kl": kl, "means": mu.view(N, B, L), "log_var": lv.view(N, B, L),
-                "recon_x": [v, t] + ([pr] if self.use_pose else [])}
+                **self._terms(tab, (gv, gt, gp), (v, t, pr)), "kl": kl, "means": mu.view(N, B, L), "log_var": lv.view(N, B, L)}
 
     @torch.no_grad()
     def plan(self, x, pose=None, goal=None, candidates=None, loss_mask=None, kl_weight=0.0, pose_multiplier=1000.0, available=None,
@@ -1935,17 +1948,9 @@ class MVAEInference:
         or N * B rows of the largest decoder activation reaching 2^31 elements."""
         if not self.conditional:
             raise ValueError("candidate conditions were passed to an unconditional model")
-        visual, tactile = x
-        c = lambda t: None if t is None else t.contiguous()
-        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        if all(t is None for t in ins) and available is None:
-            raise ValueError("plan needs at least one modality")
-        B = self._batch_of(ins, available)
+        ins, B = self._request("plan", x, pose, available)
         cand, N, per_row = self._candidates(candidates, B)
-        per = 32 * (self.model.visual_decoder.image_size // 2) ** 2
-        if N * B * per >= 1 << 31:
-            raise ValueError(f"candidates = {N} conditions of B = {B} rows make a decoder activation of {N * B} x {per} "
-                             f"elements, past 2^31; the largest N for B = {B} is {((1 << 31) - 1) // (B * per)}")
+        self._fits("candidates", N, "conditions ", B, self._decoder_row(), "decoder activation", "N")
         if not isinstance(goal, (list, tuple)) or len(goal) > 3:
             raise ValueError("goal must be a list [visual | None, tactile | None, pose | None]")
         tg = self._targets("goal", goal, B)
@@ -1956,18 +1961,17 @@ class MVAEInference:
         sample = bool(sample)
         avail, tavail = self._availability(available, B), self._availability(goal_available, B)
         args = ins + tg + [loss_mask, cand, avail, tavail]
-        key = ("plan",) + tuple(None if t is None else tuple(t.shape) for t in ins + tg + [loss_mask]) + \
+        key = ("plan",) + self._shapes(ins + tg + [loss_mask]) + \
             ("index" if self.categorical else "real", ("candidates", N, per_row), sample, self._pose_multiplier) + \
-            tuple(None if t is None else ("avail",) + tuple(t.shape) for t in (avail, tavail))
-        return self._run(key, lambda *a: self._plan_candidates(N, sample, *a), None, args)
+            self._shapes((avail, tavail), "avail")
+        return self._run(key, lambda *a: self._plan_candidates(N, sample, *a), args)
 
     def _rollout(self, T, sample, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
         """T forwards in a row, each followed by ONE feed launch that writes the next state into its trajectory slot, where the
         next step's encoders read it; with targets, the tail of :meth:`_score` per step on tables [T][3][2][B] that one fill
         clears.  Step 0 serves the request's subset / table, every later step is the joint request."""
         feed = ops.backend_op("rollout_feed")
-        ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
-        B, L, dev, S = ref.shape[0], self.L, ref.device, self.model.visual_decoder.image_size
+        (B, dev), L, S = self._rows_of(visual, tactile, pose, avail), self.L, self.model.visual_decoder.image_size
         traj = [torch.empty(T, B, 3, S, S, device=dev), torch.empty(T, B, 3, S, S, device=dev),
                 torch.empty(T, B, 7, device=dev) if self.use_pose else None]
         means, log_var = torch.empty(T, B, L, device=dev), torch.empty(T, B, L, device=dev)
@@ -1996,8 +2000,7 @@ class MVAEInference:
         res = {"visual": traj[0], "tactile": traj[1], "pose": traj[2], "means": means, "log_var": log_var,
                "bce_visual": None, "bce_tactile": None, "mse_pose": None, "kl": None, "rows": None}
         if scoring:
-            res.update(bce_visual=tab[:, 0, 0] if tv is not None else None, bce_tactile=tab[:, 0, 1] if tt is not None else None,
-                       mse_pose=tab[:, 1, 0] if tp is not None else None, kl=tab[:, 2, 0], rows=rows)
+            res.update(self._terms((tab[:, 0, 0], tab[:, 0, 1], tab[:, 1, 0]), (tv, tt, tp)), kl=tab[:, 2, 0], rows=rows)
         return res
 
     def _rollout_ensemble(self, T, N, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
@@ -2010,8 +2013,7 @@ class MVAEInference:
         passes per launch) and the assembly of :meth:`_score_tail` on the N * B rows; tables [T][3][2][N][B], cleared by one
         fill, like ``spread``."""
         feed, iw_latent = ops.backend_op("ensemble_feed"), ops.backend_op("iw_latent")
-        ref = visual if visual is not None else (tactile if tactile is not None else (pose if pose is not None else avail))
-        B, L, dev, S = ref.shape[0], self.L, ref.device, self.model.visual_decoder.image_size
+        (B, dev), L, S = self._rows_of(visual, tactile, pose, avail), self.L, self.model.visual_decoder.image_size
         NB = N * B
         traj = [torch.empty(T, N, B, 3, S, S, device=dev), torch.empty(T, N, B, 3, S, S, device=dev),
                 torch.empty(T, N, B, 7, device=dev) if self.use_pose else None]
@@ -2060,8 +2062,7 @@ class MVAEInference:
                "tactile_mean": mean[1], "tactile_var": var[1], "pose_mean": mean[2], "pose_var": var[2], "spread": spread,
                "means": means, "log_var": log_var, "bce_visual": None, "bce_tactile": None, "mse_pose": None, "kl": None, "rows": None}
         if scoring:
-            res.update(bce_visual=tab[:, 0, 0] if tv is not None else None, bce_tactile=tab[:, 0, 1] if tt is not None else None,
-                       mse_pose=tab[:, 1, 0] if tp is not None else None, kl=tab[:, 2, 0], rows=rows)
+            res.update(self._terms((tab[:, 0, 0], tab[:, 0, 1], tab[:, 1, 0]), (tv, tt, tp)), kl=tab[:, 2, 0], rows=rows)
         return res
 
     def _ensemble_tail(self, N, B, v, t, pr, mu, lv, tv, tt, tp, tavail, tab, rows):
@@ -2070,15 +2071,7 @@ class MVAEInference:
         kl_rows on the posterior that exists ([B] at step 0, its N copies made by a broadcast; [N * B] afterwards), and the
         assembly of :meth:`_score_tail` with P = 2 on the N * B rows (``tavail``: the table repeated N times, or None)."""
         NB, L = N * B, self.L
-        chw, hw = v[0].numel(), v[0, 0].numel()
-        for g0 in range(0, N, ops.ROW_GROUPS_MAX):
-            slots = list(range(g0, min(N, g0 + ops.ROW_GROUPS_MAX)))
-            rows_of = slice(g0 * B, (slots[-1] + 1) * B)
-            for slot, (lg, tg) in enumerate(((v, tv), (t, tt))):
-                if tg is not None:
-                    ops.B.bce_logits_rows_groups(lg[rows_of], tg, tab[0, slot], slots, B, chw, mask=None, hw=hw, mask_channels=1)
-            if tp is not None:
-                ops.B.mse_rows_groups(pr[rows_of], tp, tab[1, 0], slots, B, tp.shape[1])
+        self._row_terms(N, B, v, t, pr, tv, tt, tp, None, (tab[0, 0], tab[0, 1], tab[1, 0]))
         if mu.shape[0] == NB:
             ops.B.kl_rows(mu, lv, tab[2, 0].view(1, NB), 1, NB, L)
         else:
@@ -2086,11 +2079,7 @@ class MVAEInference:
             ops.B.kl_rows(mu, lv, kl, 1, B, L)
             tab[2, 0].copy_(kl)
         bce, mse, kl = (tab[k].view(2, NB) for k in range(3))
-        if tavail is None:
-            ops.B.elbo_assemble_rows(bce, mse, kl, None, rows.view(NB), None, 2, NB, 1.0, self._pose_multiplier, self._klw, 1)
-        else:
-            ops.B.elbo_assemble_rows_avail(bce, mse, kl, None, rows.view(NB), None, tavail, [0, 1], [2, -1], 2, NB, 1.0,
-                                           self._pose_multiplier, self._klw, 1)
+        self._assemble(bce, mse, kl, rows.view(NB), tavail, NB)
 
     def _step_tensors(self, name, given, T, B):
         """``observed`` / ``targets`` = [visual | None, tactile | None, pose | None], each [T, B, ...] -> three contiguous fp32
@@ -2167,29 +2156,17 @@ class MVAEInference:
         request's posterior in all N slots); with targets ``bce_visual`` / ``bce_tactile`` / ``mse_pose`` / ``kl`` fp64 [T, N, B]
         and ``rows`` fp32 [T, N, B], each trajectory against the one target.  The graph key carries N.  ValueError: N no integer
         >= 1, ``sample=False`` (N identical trajectories), or N past what 32-bit element offsets allow."""
-        if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or steps < 1:
-            raise ValueError(f"steps must be an integer >= 1 (the number of model applications), got {steps!r}")
-        T, sample = int(steps), bool(sample)
+        T, sample = self._count("steps", steps, "model applications"), bool(sample)
         if samples is not None:
-            if isinstance(samples, bool) or not isinstance(samples, numbers.Integral) or samples < 1:
-                raise ValueError(f"samples must be an integer >= 1 (the number of trajectories per row), got {samples!r}")
+            samples = self._count("samples", samples, "trajectories per row")
             if not sample:
                 raise ValueError("samples needs sample=True: the posterior-mean rollout would give N identical trajectories")
-            samples = int(samples)
-        visual, tactile = x
-        c = lambda t: None if t is None else t.to(torch.float32).contiguous()
-        ins = [c(visual), c(tactile), c(pose) if self.use_pose else None]
-        if all(t is None for t in ins) and available is None:
-            raise ValueError("rollout needs at least one modality")
-        B = self._batch_of(ins, available)
+        ins, B = self._request("rollout", x, pose, available, cast=True)
         S = self.model.visual_decoder.image_size
-        if T * B * 3 * S * S >= 1 << 31:
-            raise ValueError(f"steps = {T} of B = {B} rows make a trajectory tensor of {T * B} x {3 * S * S} elements, past 2^31; "
-                             f"the largest steps for B = {B} is {((1 << 31) - 1) // (B * 3 * S * S)}")
+        self._fits("steps", T, "", B, 3 * S * S, "trajectory tensor", "steps")
         if samples is not None:
-            # 32-bit element offsets: the trajectory tensors [T][N][B][3][S][S] and the decoders' largest activation, the last hidden
-            # layer's [N * B][32][S / 2][S / 2]
-            most = min(((1 << 31) - 1) // (T * B * 3 * S * S), ((1 << 31) - 1) // (B * 32 * (S // 2) ** 2))
+            # 32-bit element offsets: the trajectory tensors [T][N][B][3][S][S] and the decoders' largest activation [N * B] rows
+            most = min(((1 << 31) - 1) // (T * B * 3 * S * S), ((1 << 31) - 1) // (B * self._decoder_row()))
             if samples > most:
                 raise ValueError(f"samples = {samples} trajectories of B = {B} rows over steps = {T} make a tensor of 2^31 elements or "
                                  f"more; the largest samples for B = {B} and steps = {T} is {most}")
@@ -2214,15 +2191,14 @@ class MVAEInference:
         self._set_weights(kl_weight, pose_multiplier)
         avail = self._availability(available, B)
         args = ins + [cond, avail] + obs + [oav] + tg + [tav]
-        key = ("rollout", T, sample, self._pose_multiplier, per_step_cond, None if cond is None else self._cond_key(cond)) + \
-            tuple(None if t is None else (str(t.dtype),) + tuple(t.shape) for t in args)
+        key = ("rollout", T, sample, self._pose_multiplier, per_step_cond, self._cond_key(cond)) + self._shapes(args, dtype=True)
         if samples is not None:
-            return self._run(key + (("samples", samples),), lambda *a: self._rollout_ensemble(T, samples, per_step_cond, *a), None, args)
-        return self._run(key, lambda *a: self._rollout(T, sample, per_step_cond, *a), None, args)
+            return self._run(key + (("samples", samples),), lambda *a: self._rollout_ensemble(T, samples, per_step_cond, *a), args)
+        return self._run(key, lambda *a: self._rollout(T, sample, per_step_cond, *a), args)
 
     @torch.no_grad()
     def inference(self, n=1, c=None):
         """``MVAE.inference(n, c)`` (vae.py:167-176): z ~ N(0, I) -> (visual, tactile) logits; ``c``: the n conditions of a
         conditional model, as in :meth:`forward`."""
         cond = self._condition(c, int(n))
-        return self._run(("sample", int(n), self._cond_key(cond)), lambda c_: self._sample(int(n), c_), None, [cond])
+        return self._run(("sample", int(n), self._cond_key(cond)), lambda c_: self._sample(int(n), c_), [cond])

@@ -23,6 +23,7 @@ import os
 import pickle
 import time
 from collections import defaultdict
+from contextlib import contextmanager
 from datetime import datetime
 from pathlib import Path
 
@@ -601,6 +602,26 @@ class Reconstruction(Problem):
                 return self._model.inference(n=n, c=y)
             return self._model.inference(n=n)
 
+    @contextmanager
+    def _serving(self, slot, eval_mode=True):
+        """The serving engine kept in the attribute ``slot``: built on first use or for a new model, its weights re-packed
+        otherwise.  ``eval_mode``: the model is in ``eval()`` inside the block and goes back to the mode it was in."""
+        from ..engine import MVAEInference
+        was_training = self._model.training
+        if eval_mode:
+            self._model.eval()
+        try:
+            eng = getattr(self, slot, None)
+            if eng is None or eng.model is not self._model:
+                eng = MVAEInference(self._model)
+                setattr(self, slot, eng)
+            else:
+                eng.refresh()
+            yield eng
+        finally:
+            if eval_mode:
+                self._model.train(was_training)
+
     def complete(self, x, sample=False):
         """The completed frames of a mixed-modality batch (cnn-mvae): ``x`` is the dict ``parse_input`` returns; its
         ``input_available_modals`` ([B, 2]: visual, tactile present per frame -- the dataset counts a constant image as missing)
@@ -612,17 +633,12 @@ class Reconstruction(Problem):
             raise ValueError(f"complete() serves cnn-mvae models, not {self.parameters.get('model_name')!r}")
         if not isinstance(x, dict) or not isinstance(x.get('model_input'), (list, tuple)) or len(x['model_input']) != 2:
             raise ValueError("complete() takes the dict parse_input returns for a visuotactile batch")
-        from ..engine import MVAEInference
-        eng = getattr(self, '_completer', None)
-        if eng is None or eng.model is not self._model:
-            eng = self._completer = MVAEInference(self._model)
-        else:
-            eng.refresh()
         pose = x.get('input_object_pose')
         pose = pose[0] if isinstance(pose, (list, tuple)) else pose
-        out = eng.complete(list(x['model_input']), pose=pose, available=x.get('input_available_modals'),
-                           condition=x.get('shock') if self._conditional else None, sample=sample)
-        return tuple(None if t is None else t.clone() for t in out)
+        with self._serving('_completer', eval_mode=False) as eng:
+            out = eng.complete(list(x['model_input']), pose=pose, available=x.get('input_available_modals'),
+                               condition=x.get('shock') if self._conditional else None, sample=sample)
+            return tuple(None if t is None else t.clone() for t in out)
 
     def iw_score(self, data_input, data_target, samples=16):
         """The importance-weighted bound of one batch in the loader's format (cnn-mvae): ``parse_input``, then
@@ -637,22 +653,12 @@ class Reconstruction(Problem):
         inputs, targets = self.parse_input(data_input, data_target)
         if not self._fused_applicable(inputs):
             raise ValueError("iw_score() takes a visuotactile batch in the loader's format (a list of tensors)")
-        from ..engine import MVAEInference
-        was_training = self._model.training
-        self._model.eval()
-        try:
-            eng = getattr(self, '_iw_scorer', None)
-            if eng is None or eng.model is not self._model:
-                eng = self._iw_scorer = MVAEInference(self._model)
-            else:
-                eng.refresh()
+        with self._serving('_iw_scorer') as eng:
             xs, ts = self._fused_io(inputs, targets)
             res = eng.score(list(xs[:2]), pose=xs[2] if len(xs) > 2 else None, targets=list(ts), loss_mask=self._fused_mask(targets),
                             kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier,
                             condition=inputs.get('shock') if self._conditional else None, samples=samples)
             return {"rows": res["rows"].clone(), "ess": res["ess"].clone()}
-        finally:
-            self._model.train(was_training)
 
     def parse_input(self, data, target):
         if not isinstance(data, list):
@@ -810,22 +816,12 @@ class DynModeling(SeqModeling):
             if len(data) < 5:
                 raise ValueError("a conditional model needs the shock force of every frame (data[4])")
             cond = data[4].reshape((n, l) + tuple(data[4].shape[1:]))[:, :T].transpose(0, 1).to(dev)
-        from ..engine import MVAEInference
-        was_training = self._model.training
-        self._model.eval()
-        try:
-            eng = getattr(self, '_roller', None)
-            if eng is None or eng.model is not self._model:
-                eng = self._roller = MVAEInference(self._model)
-            else:
-                eng.refresh()
+        with self._serving('_roller') as eng:
             res = eng.rollout([data[0][::l].to(dev), data[1][::l].to(dev)], pose=data[2][::l].to(dev) if use_pose else None,
                               steps=T, available=data[3][::l].to(dev), condition=cond, sample=sample, observed=observed,
                               observed_available=oavail, targets=targets, target_available=tavail, kl_weight=self._kl_weight,
                               pose_multiplier=self._pose_multiplier, **({} if samples is None else {"samples": samples}))
             return {k: None if v is None else v.clone() for k, v in res.items()}
-        finally:
-            self._model.train(was_training)
 
     def plan(self, data_input, data_target, candidates=None):
         """Which of N candidate shocks takes each frame of one loader batch to its recorded next frame (cnn-mvae, ``--conditional``):
@@ -852,15 +848,7 @@ class DynModeling(SeqModeling):
         goal_has = torch.roll(has.to(torch.float32), -1, dims=0)
         goal_has[l - 1::l] = 1.0                                   # the dataset's final target
         goal_has = torch.cat((goal_has[:, :2], torch.ones(goal_has.shape[0], 1, device=dev)), 1)
-        from ..engine import MVAEInference
-        was_training = self._model.training
-        self._model.eval()
-        try:
-            eng = getattr(self, '_planner', None)
-            if eng is None or eng.model is not self._model:
-                eng = self._planner = MVAEInference(self._model)
-            else:
-                eng.refresh()
+        with self._serving('_planner') as eng:
             res = eng.plan(list(inputs['model_input']), pose=inputs['input_object_pose'][0] if use_pose else None, goal=goal,
                            candidates=candidates, kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier,
                            available=has, goal_available=goal_has)
@@ -868,5 +856,3 @@ class DynModeling(SeqModeling):
             out = {k: clone(v) for k, v in res.items()}
             out["recorded"] = inputs['shock']
             return out
-        finally:
-            self._model.train(was_training)
