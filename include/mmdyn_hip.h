@@ -223,7 +223,9 @@ int mmdyn_wgrad_tn_grouped(const void* D, const void* Gt, float* partial, int G,
  * the decoder's last layer nn.ConvTranspose2d(32, 3, 4, 2, 1) (vae.py:277) with the BatchNorm2d + Swish in front of it
  * (vae.py:275-276) recomputed on the operand fetch.  y [G*Bg][Hr][Hr][32]: the pre-BatchNorm tensor (fp32; y_b16 = 1 bf16,
  * 2 IEEE half); mean / rstd [G][32]; Gt: the NCHW logit gradient [G*Bg][3][2Hr][2Hr]; partial [chunks][32][64] as
- * mmdyn_wgrad_tn(MMDYN_IM2COL3) writes it (chunks = mmdyn_wgrad_chunks(MMDYN_IM2COL3, ...)).  Hr = 32, 64 or 128. */
+ * mmdyn_wgrad_tn(MMDYN_IM2COL3) writes it (chunks = mmdyn_wgrad_chunks(MMDYN_IM2COL3, ...); any chunks >= 1 is taken, slab c holds
+ * the c-th range of ceil(units / chunks) units, a unit being a 32-pixel segment of a row of y).  Square images of Hr = 32, 64 or 128
+ * only: there is one extent argument, and every other Hr is MMDYN_ERR_SHAPE before anything is launched. */
 int mmdyn_wgrad_out3_bn(const void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                         const float* Gt, float* partial, int G, int Bg, int Hr, int chunks, int y_b16, void* stream);
 int mmdyn_wgrad_chunks(int mode, int rows, int Cd, int Cg);
@@ -289,7 +291,9 @@ int mmdyn_col2im_k4(const float* col, float* out, int Bt, int Hi, int Wi, int Ho
 int mmdyn_tconv_out3_fwd(const float* a, const float* w, float* out, int Bt, int Hi, int Wi, void* stream);
 /* ... fused with the BatchNorm2d + Swish in front of it (vae.py:275-277): y [G*Bg][Hi][Wi][32] is the pre-BatchNorm output of the
  * layer below (fp32; b16 = 1 bf16, 2 IEEE half), mean / rstd [G][32] its batch statistics; the activation is applied while
- * the input tile is staged, the activated tensor never exists in HBM. */
+ * the input tile is staged, the activated tensor never exists in HBM.  Like mmdyn_tconv_out3_fwd this form and the three loss forms
+ * below take any Hi, Wi that are multiples of 16, Hi != Wi included (anything else: MMDYN_ERR_SHAPE); the padding around the image is
+ * zero AFTER the activation. */
 int mmdyn_tconv_out3_bn_fwd(const void* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                             const float* w, float* out, int G, int Bg, int Hi, int Wi, int b16, void* stream);
 /* ... and with the reconstruction term of the ELBO in its epilogue (round 6): F.binary_cross_entropy_with_logits(recon, target,

@@ -300,13 +300,21 @@ class EmuBackend:
             logits.reshape(-1).copy_(src.reshape(-1))
 
     def wgrad_out3_bn(self, y, mean, rstd, gamma, beta, Gt, partial, G, Bg, Hr, chunks):
+        """mmdyn_wgrad_out3_bn: fp32 matrix cores in every mode; any chunks >= 1.  Slab c holds the units (32-pixel segments of the
+        rows of y, numbered (sample, row, segment)) [c * rows_per_chunk, (c + 1) * rows_per_chunk), a slab past the last unit zeros.
+        The split is the one of mmdyn_conv3_wgrad_try (csrc/conv3.hip: rows_per_chunk = ceil_div(img_rows, chunks)), as the header
+        states it."""
+        if Hr not in (32, 64, 128) or G <= 0 or Bg <= 0 or chunks < 1:
+            raise _lib.MmdynError("mmdyn_wgrad_out3_bn failed: MMDYN_ERR_SHAPE (unsupported dimensions)")
         a = torch.empty(y.shape, dtype=torch.float32)
         EmuBackend.bn_swish_fwd(self, y.float(), mean, rstd, gamma, beta, a, G, Bg * Hr * Hr, 32)
-        prev, self.precision = self.precision, "fp32"            # (the 3-channel layers keep fp32 matrix cores in every mode)
-        try:
-            EmuBackend.wgrad_tn(self, a, Gt, partial, IM2COL3, G * Bg, Hr, Hr, 32, 2 * Hr, 2 * Hr, 64, 1, 0, chunks)
-        finally:
-            self.precision = prev
+        a, g = a.reshape(-1, 32), self._unfold3(Gt, G * Bg, 2 * Hr, 2 * Hr)
+        units = a.shape[0] // 32
+        per = -(-units // chunks)
+        p = partial.reshape(chunks, 32, 64)
+        for c in range(chunks):
+            lo, hi = min(units, c * per) * 32, min(units, (c + 1) * per) * 32
+            p[c] = a[lo:hi].t() @ g[lo:hi]
 
     def nchw_to_nhwc(self, src, dst, B, C, HW):
         dst.reshape(-1).copy_(src.reshape(B, C, HW).permute(0, 2, 1).reshape(-1))
@@ -559,7 +567,7 @@ class EmuBackend:
             assert mask_channels in (1, c) and mask.numel() == (n // chw) * mask_channels * hw
             mk = mask.reshape(-1, mask_channels, hw).expand(-1, c, hw).reshape(-1)
             x, t = x * mk, t * mk
-        loss_sum += F.binary_cross_entropy_with_logits(x, t, reduction="sum").double()
+        loss_sum += F.binary_cross_entropy_with_logits(x, t, reduction="none").double().sum()      # (fp64 from the element on)
         if dlogit is not None:
             d = (torch.sigmoid(x) - t) * grad_scale
             if mask is not None:

@@ -587,6 +587,20 @@ def run_wgrad_grouped(be, dev, G, rows, Cd, Cg, family, store=(None, None), what
 
 
 # ---- direct kernels -------------------------------------------------------------------------------------------------------------
+def out3_weight_sets():
+    """The six selection weight sets of the last decoder layer, [(w [32][3][4][4], tap [3], ci [3], scale [3])]: output channel co
+    of set s selects one (ci, kh, kw) with value +-2^k; co + 3 s covers the 16 taps in 6 sets."""
+    sets, taps = [], set()
+    for s in range(6):
+        tap, ci, scale = (torch.arange(3) + 3 * s) % 16, (torch.arange(3) * 11 + 5 * s) % 32, pow2(3, 500 + s)
+        w = torch.zeros(32, 3, 4, 4)
+        w[ci, torch.arange(3), tap >> 2, tap & 3] = scale
+        sets.append((w, tap, ci, scale))
+        taps |= set(tap.tolist())
+    assert len(taps) == 16
+    return sets
+
+
 def run_tconv_out3(be, dev, Bt, Hi, Wi, family, store=None, what=""):
     """mmdyn_tconv_out3_fwd: ConvTranspose2d(32, 3, 4, 2, 1) of an NHWC activation, NCHW logits.  store: the activation is stored
     in that 16-bit type (mmdyn_tconv_out3_fwd_b16; the arbitrary activation of family B is then one of its values); weights and
@@ -597,19 +611,13 @@ def run_tconv_out3(be, dev, Bt, Hi, Wi, family, store=None, what=""):
         x = a.double().reshape(Bt, Hi, Wi, 32).permute(0, 3, 1, 2)
         assert float(F.conv_transpose2d(x.abs(), ws[0].double().abs(), stride=2, padding=1).max()) < LIMIT
         wants = [F.conv_transpose2d(x, ws[0].double(), stride=2, padding=1)]
-    else:                              # output channel co of weight set s selects one (ci, kh, kw): co + 3 s covers the 16 taps in 6 sets
+    else:                              # the six selection sets: every logit is one activation times +-2^k, or +0 in the padding
         a, ws, wants = arbitrary((Bt * Hi * Wi, 32), 73, BINADES[store]), [], []
         a = a.to(store).float() if store else a
         g = Geo((TCONV_S2P1, 1, Bt, Hi, Wi, 32, 2 * Hi, 2 * Wi, 3, 1, 0))
-        taps = set()
-        for s in range(6):
-            tap, ci, scale = (torch.arange(3) + 3 * s) % 16, (torch.arange(3) * 11 + 5 * s) % 32, pow2(3, 500 + s)
-            w = torch.zeros(32, 3, 4, 4)
-            w[ci, torch.arange(3), tap >> 2, tap & 3] = scale
+        for w, tap, ci, scale in out3_weight_sets():
             ws.append(w)
             wants.append(select_ref(g, a, tap, ci, scale).reshape(Bt, 2 * Hi, 2 * Wi, 3).permute(0, 3, 1, 2))
-            taps |= set(tap.tolist())
-        assert len(taps) == 16
     for w, want in zip(ws, wants):
         out = Guarded(Bt * 3 * 2 * Hi, 2 * Wi, torch.float32, dev)
         be.tconv_out3_fwd(_dev(a.to(store) if store else a, dev), _dev(w, dev), out.t, Bt, Hi, Wi)

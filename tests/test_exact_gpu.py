@@ -30,11 +30,12 @@ Not exact, because they multiply by a sigmoid: the Swish epilogues (act = MMDYN_
 with Swish) and the BatchNorm-backward epilogue of mmdyn_igemm_nt_dgrad_bn.  They are held per element by
 tests/test_store16_gpu.py (rule of tests/store16_cases.py: half an ulp of the output type plus a measured multiple of 2^-24 of the
 largest intermediate, against the documented formula in fp64, on the integer operands of family A), with 16-bit and with fp32
-outputs, next to the 16-bit element-wise kernels (bn_swish_fwd / _bwd_reduce / _bwd_apply, act_bwd).  Still with the tolerance
-tests of tests/test_kernels_gpu.py / tests/test_kernels_aten_gpu.py only: mmdyn_wgrad_out3_bn and mmdyn_tconv_out3_bn_fwd, and the
-fused last-layer loss kernels (mmdyn_tconv_out3_bn_bce, _bce_rows, _bce_rows_grad), which evaluate log / exp per element and add
-into fp64 atomics.  The weight-gradient selection family runs both ways round (one-hot D, one-hot Gt) for the DENSE and CONV
-gathers; for MMDYN_IM2COL3, whose gathered operand is the NCHW image, with the one-hot D only.
+outputs, next to the 16-bit element-wise kernels (bn_swish_fwd / _bwd_reduce / _bwd_apply, act_bwd).  The fused last
+decoder layer -- mmdyn_tconv_out3_bn_fwd, mmdyn_wgrad_out3_bn and the loss kernels mmdyn_tconv_out3_bn_bce, _bce_rows,
+_bce_rows_grad, which evaluate log / exp per element and add into fp64 atomics -- is held by the same rule, with the selection
+weights of family B, in tests/test_out3_gpu.py (cases and references: tests/out3_cases.py).  The weight-gradient selection
+family runs both ways round (one-hot D, one-hot Gt) for the DENSE and CONV gathers; for MMDYN_IM2COL3, whose gathered operand is
+the NCHW image, with the one-hot D only.
 
 What reading the routes' address arithmetic for Hi != Wi found (before anything was launched):
   - the register-staged (igemm_nt.hip), wave-specialised (igemm_ws.hip), persistent (igemm_wsp.hip) and direct-fragment
