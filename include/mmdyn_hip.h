@@ -735,6 +735,54 @@ typedef struct {
 } mmdyn_gather_groups;
 int mmdyn_gather_best(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, void* stream);
 
+/* ---- candidate condition SEQUENCES over T steps (MVAEInference.plan_rollout: N candidate sequences per row rolled out open loop,
+ * the best one picked on the device; the reference has no such operation) ---------------------------------------------------
+ * mmdyn_plan_select_steps: the step costs, the weighted total and each row's winner from the row tables of the Tg scored steps:
+ *   c[t][n][b]         = ((bce_rows[0][t][n][b] + bce_rows[1][t][n][b]) + pose_multiplier * mse_rows[t][n][b])
+ *                        + kl_weight * kl_rows[t][n][b]                  -- the cost of mmdyn_plan_select, the same function;
+ *   step_cost[t][n][b] = (float)c[t][n][b];
+ *   total[n][b]        = w[0] * c[0][n][b] + w[1] * c[1][n][b] + ... in fp64, t ascending, w[t] = (double)step_weight[t]; every
+ *                        product and every sum rounded to nearest on its own (no fused multiply-add), the first term starts the
+ *                        sum; step_weight null: the plain sum c[0] + c[1] + ..., with no multiplication;
+ *   cost[n][b]         = (float)total[n][b];  best[b] = the n of the smallest total;  best_cost[b] = (float)total[best[b]][b].
+ * Selection on the fp64 total by the rules of mmdyn_plan_select: the smallest wins; equal totals: the lowest n; a NaN total never
+ * wins (a NaN in one step makes the total NaN); +Inf / -Inf are ordinary values.  All N totals of a row NaN: best[b] = -1,
+ * best_cost[b] = NaN, the T rows of best_cond NaN (best_idx -1).
+ * Tg is 1 (a final goal: the tables hold the one scored step) or T (every step scored).  bce_rows: [2][Tg][N][B] double or null;
+ * mse_rows: [Tg][N][B] double or null; kl_rows: [Tg][N][B] double, required; a null table enters as +0.0.  tavail (may be null):
+ * [Tg][B][4] bytes, the TARGET-availability table of each scored step; an absent (step, row, term) enters as +0.0 for every n and
+ * its N table entries are overwritten with 0.  step_weight: [Tg] float in DEVICE memory or null; the values are not looked at on
+ * the host (NaN / Inf propagate into the totals).  Candidates, step-major and candidate-major, exactly one kind:
+ *   cand [T][N * B][cd] float  -> best_cond [B][T][cd] float = cand[t][best[b] * B + b] for all T steps;
+ *   cand_idx [T][N * B] int64  -> best_idx [B][T] int64      (cd is not used).
+ * top / top_cost (both or neither): [K][B] int / float, K in [1, MMDYN_PLAN_TOP_MAX]: the K smallest totals of each row in
+ * ascending order under the same rules -- equal totals in n order, a NaN total never listed; entries past the number of non-NaN
+ * candidates are -1 / NaN; top[0][b] == best[b].  cost [N][B], step_cost [Tg][N][B], best [B], best_cost [B]: OUTPUTS.
+ * kl_weight_dev as in mmdyn_elbo_assemble.  One thread per row b; no atomics, no LDS: the same bits in every run.
+ * With Tg = T = 1 and step_weight null, cost / best / best_cost / best_cond (best_idx) have the bits of mmdyn_plan_select on the
+ * same tables, and step_cost those of cost.
+ * Checked on the host: kl_rows, cost, step_cost, best or best_cost null, not exactly one kind of candidates with its output, or
+ * top without top_cost (or the reverse): MMDYN_ERR_NULL; N, B, T, Tg or cd < 1, Tg neither 1 nor T, K outside
+ * [1, MMDYN_PLAN_TOP_MAX] with top given, or a misaligned table: MMDYN_ERR_SHAPE; T * N * B * cd >= 2^31: MMDYN_ERR_RANGE. */
+#define MMDYN_PLAN_TOP_MAX 8
+int mmdyn_plan_select_steps(double* bce_rows, double* mse_rows, const double* kl_rows, const uint8_t* tavail,
+                            const float* step_weight, const float* cand, const int64_t* cand_idx, int cd, float* cost,
+                            float* step_cost, int* best, float* best_cost, float* best_cond, int64_t* best_idx, int* top,
+                            float* top_cost, int K, int N, int B, int T, int Tg, float pose_multiplier, float kl_weight,
+                            const float* kl_weight_dev, void* stream);
+/* mmdyn_gather_best_steps: the winner's rows of all T steps out of step-major, candidate-major tensors, in one launch:
+ *   out[g][t][b][i] = f(src[g][t][best[b] * B + b][i]),  f as in mmdyn_gather_best,
+ * src[g]: fp32 [T][N * B][row_len[g]], out[g]: fp32 [T][B][row_len[g]] (mmdyn_gather_groups with these shapes).  The element scheme
+ * of mmdyn_gather_best on every step slice (16-byte accesses where the slice's src and out are 16-byte aligned, element by element
+ * otherwise; a block works on one group and one step at a time; a row whose index lies outside [0, N) is filled with NaN and
+ * reads nothing): the result has the bits of T mmdyn_gather_best calls on the slices src[g] + t * N * B * row_len[g], out[g] +
+ * t * B * row_len[g].  No LDS, no atomics.
+ * Checked on the host: groups, best, or src / out of a group < G, null: MMDYN_ERR_NULL; G outside [1, MMDYN_FEED_GROUPS], N, B or
+ * T < 1, a row_len < 1, or an out[g] that overlaps best, the src of ANY group < G or the out of another group < G:
+ * MMDYN_ERR_SHAPE; T * N * B * row_len[g] >= 2^31: MMDYN_ERR_RANGE.
+ * Both added without touching an existing signature or workspace: the revision stays 6. */
+int mmdyn_gather_best_steps(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, int T, void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call
  * (graph-replay safe); p/g/m/v: flat fp32 buffers of n elements; g is multiplied by grad_scale first */

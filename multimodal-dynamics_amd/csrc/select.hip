@@ -17,6 +17,10 @@
 //     gather_best copies the winner's decoder rows out of the [N * B] candidate-major outputs, for up to MMDYN_FEED_GROUPS tensors
 //     in one launch (images through sigmoid_exact, so a taken row has the bits of mmdyn_complete_select(x = null) on that row).
 //     Both read best[] from device memory: the choice never visits the host and the request sits in one captured graph.
+//   - plan_select_steps / gather_best_steps: N candidate condition SEQUENCES per request rolled out over T steps
+//     (MVAEInference.plan_rollout).  plan_select_steps forms plan_select's cost per scored step, the weighted total over the steps
+//     in fp64 and each row's winner (and, on request, the K best); gather_best_steps copies the winner's rows of all T steps out of
+//     the [T][N * B] trajectory tensors in one launch, with gather_best's element scheme on every step slice.
 //   - ensemble_feed: the rollout feed of N sampled trajectories per request row (MVAEInference.rollout(samples=N)).  The N * B
 //     decoder rows of a step become the N * B next states under observations that exist once per request row, and the same read
 //     of the logits leaves the ensemble's per-element mean and variance and each row's summed variance.  An element scheme of
@@ -360,6 +364,140 @@ __global__ __launch_bounds__(256) void gather_best_kernel(const GatherArgs a, co
               (int64_t)(a.first_block[g + 1] - a.first_block[g]) * blockDim.x);
 }
 
+// ---- candidate condition SEQUENCES over T steps: the weighted total, the winner of each row, the winner's trajectory ----
+
+// total + w * c (weighted) or total + c, the product and the sum rounded on their own: the pragma as in plan_cost.  `first`: the
+// term starts the sum (w * c or c itself, no 0.0 + ...).
+__device__ __forceinline__ double add_step(double total, double c, double w, bool weighted, bool first) {
+#pragma clang fp contract(off)
+  const double term = weighted ? w * c : c;
+  return first ? term : total + term;
+}
+
+// The running list of the TOP smallest totals, ascending, equal totals in the order they came (n ascending): a fixed register
+// array walked by fully unrolled loops only, so no element is addressed by a run-time index.  An empty slot holds index -1.
+struct TopList {
+  double c[MMDYN_PLAN_TOP_MAX];
+  int n[MMDYN_PLAN_TOP_MAX];
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int k = 0; k < MMDYN_PLAN_TOP_MAX; ++k) {
+      c[k] = NAN;
+      n[k] = -1;
+    }
+  }
+  // v is no NaN.  From the last slot down: a slot that v goes in front of takes its left neighbour if v goes in front of that one
+  // too, and v otherwise (the left neighbour is read before its own turn changes it).
+  __device__ __forceinline__ void insert(double v, int idx) {
+#pragma unroll
+    for (int k = MMDYN_PLAN_TOP_MAX - 1; k > 0; --k) {
+      const bool before = n[k] < 0 || v < c[k], before_left = n[k - 1] < 0 || v < c[k - 1];
+      if (before) {
+        c[k] = before_left ? c[k - 1] : v;
+        n[k] = before_left ? n[k - 1] : idx;
+      }
+    }
+    if (n[0] < 0 || v < c[0]) {
+      c[0] = v;
+      n[0] = idx;
+    }
+  }
+};
+
+// One thread per row b walks the candidates n and, inside, the scored steps t: c_t = plan_cost of the step's table entries,
+// total = sum_t w_t * c_t in t order.  The tables are [Tg][N][B] (bce: [2][Tg][N][B]), tavail [Tg][B] words, so every read
+// coalesces across b.  Selection on the fp64 total by plan_select_kernel's rules; Tg = T = 1 without weights is that kernel.
+template <bool TOP>
+__global__ __launch_bounds__(256) void plan_select_steps_kernel(double* __restrict__ bce, double* __restrict__ mse,
+                                                                const double* __restrict__ kl, const uint32_t* __restrict__ tavail,
+                                                                const float* __restrict__ step_weight, const float* __restrict__ cand,
+                                                                const int64_t* __restrict__ cand_idx, int cd, float* __restrict__ cost,
+                                                                float* __restrict__ step_cost, int* __restrict__ best,
+                                                                float* __restrict__ best_cost, float* __restrict__ best_cond,
+                                                                int64_t* __restrict__ best_idx, int* __restrict__ top,
+                                                                float* __restrict__ top_cost, int K, int N, int B, int T, int Tg,
+                                                                float pose_multiplier, float kl_weight_arg,
+                                                                const float* __restrict__ kl_weight_dev) {
+  const float kl_weight = kl_weight_dev ? kl_weight_arg * kl_weight_dev[0] : kl_weight_arg;
+  const double pm = (double)pose_multiplier, klw = (double)kl_weight;
+  const size_t NB = (size_t)N * B, TNB = (size_t)Tg * NB;
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    double low = NAN;
+    int win = -1;
+    TopList list;
+    if (TOP) list.clear();
+    for (int n = 0; n < N; ++n) {
+      double total = 0.0;
+      for (int t = 0; t < Tg; ++t) {
+        const uint32_t word = tavail ? tavail[(size_t)t * B + b] : ALL_PRESENT;
+        const bool has0 = has(word, 0), has1 = has(word, 1), has2 = has(word, 2);
+        const size_t o = ((size_t)t * N + n) * B + b;
+        const double v = bce && has0 ? bce[o] : 0.0, u = bce && has1 ? bce[TNB + o] : 0.0, p = mse && has2 ? mse[o] : 0.0;
+        if (bce && !has0) bce[o] = 0.0;
+        if (bce && !has1) bce[TNB + o] = 0.0;
+        if (mse && !has2) mse[o] = 0.0;
+        const double c = plan_cost(v, u, p, kl[o], pm, klw);
+        step_cost[o] = (float)c;
+        total = add_step(total, c, step_weight ? (double)step_weight[t] : 1.0, step_weight != nullptr, t == 0);
+      }
+      cost[(size_t)n * B + b] = (float)total;
+      if (total == total) {
+        if (win < 0 || total < low) {
+          low = total;
+          win = n;
+        }
+        if (TOP) list.insert(total, n);
+      }
+    }
+    best[b] = win;
+    best_cost[b] = (float)low;
+    for (int t = 0; t < T; ++t) {
+      const size_t src = ((size_t)t * N + (win < 0 ? 0 : win)) * B + b, dst = (size_t)b * T + t;
+      if (best_idx) best_idx[dst] = win < 0 ? (int64_t)-1 : cand_idx[src];
+      if (best_cond)
+        for (int j = 0; j < cd; ++j) best_cond[dst * cd + j] = win < 0 ? NAN : cand[src * cd + j];
+    }
+    if (TOP) {
+#pragma unroll
+      for (int k = 0; k < MMDYN_PLAN_TOP_MAX; ++k)
+        if (k < K) {
+          top[(size_t)k * B + b] = list.n[k];
+          top_cost[(size_t)k * B + b] = (float)list.c[k];
+        }
+    }
+  }
+}
+
+struct GatherStepsArgs {
+  const float* src[MMDYN_FEED_GROUPS];
+  float* out[MMDYN_FEED_GROUPS];
+  int64_t n[MMDYN_FEED_GROUPS];               // B * row_len: the floats of one step's out; N * n those of one step's src
+  int row_len[MMDYN_FEED_GROUPS], logits[MMDYN_FEED_GROUPS];
+  int per_step[MMDYN_FEED_GROUPS];            // blocks that cover one step with one item per thread
+  int first_block[MMDYN_FEED_GROUPS + 1];
+};
+
+// gather_rows on every step slice: the group's blocks walk its T * per_step (step, chunk) pieces, so the step -- and with it the
+// slice pointers and whether they allow 16-byte accesses -- is block-uniform.  A piece is what one block of a per_step-block
+// gather_best launch on that slice does.
+__global__ __launch_bounds__(256) void gather_best_steps_kernel(const GatherStepsArgs a, const int* __restrict__ best, int G, int N,
+                                                                int T) {
+  int g = 0;
+#pragma unroll
+  for (int k = 1; k < MMDYN_FEED_GROUPS; ++k)
+    if (k < G && (int)blockIdx.x >= a.first_block[k]) g = k;
+  const int blocks = a.first_block[g + 1] - a.first_block[g], per_step = a.per_step[g];
+  const int64_t n = a.n[g];
+  for (int64_t piece = (int)blockIdx.x - a.first_block[g]; piece < (int64_t)T * per_step; piece += blocks) {
+    const int t = (int)(piece / per_step), chunk = (int)(piece % per_step);
+    const float* src = a.src[g] + (int64_t)t * N * n;
+    float* out = a.out[g] + (int64_t)t * n;
+    const bool vec = (((uintptr_t)src | (uintptr_t)out) & 15) == 0;
+    gather_rows(src, best, out, n, vec ? n / 4 : 0, a.row_len[g], N, a.logits[g], (int64_t)chunk * blockDim.x + threadIdx.x,
+                (int64_t)per_step * blockDim.x);
+  }
+}
+
 bool ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
   return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
@@ -527,5 +665,63 @@ extern "C" int mmdyn_ensemble_feed(const mmdyn_ensemble_groups* groups, int G, c
   }
   const int blocks = split_blocks(work, G, a.first_block);
   hipLaunchKernelGGL(ensemble_feed_kernel, dim3(blocks), dim3(256), 0, ST, a, reinterpret_cast<const uint32_t*>(obs_avail), G, N);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_plan_select_steps(double* bce_rows, double* mse_rows, const double* kl_rows, const uint8_t* tavail,
+                                       const float* step_weight, const float* cand, const int64_t* cand_idx, int cd, float* cost,
+                                       float* step_cost, int* best, float* best_cost, float* best_cond, int64_t* best_idx, int* top,
+                                       float* top_cost, int K, int N, int B, int T, int Tg, float pose_multiplier, float kl_weight,
+                                       const float* kl_weight_dev, void* stream) {
+  if (!kl_rows || !cost || !step_cost || !best || !best_cost) return MMDYN_ERR_NULL;
+  // exactly one kind of candidates, and the winner's conditions in that kind; the list and its costs together
+  if ((cand == nullptr) == (cand_idx == nullptr) || (cand != nullptr) != (best_cond != nullptr) ||
+      (cand_idx != nullptr) != (best_idx != nullptr) || (top == nullptr) != (top_cost == nullptr))
+    return MMDYN_ERR_NULL;
+  if (N < 1 || B < 1 || T < 1 || Tg < 1 || cd < 1 || (Tg != 1 && Tg != T) || ((uintptr_t)tavail & 3)) return MMDYN_ERR_SHAPE;
+  if (top && (K < 1 || K > MMDYN_PLAN_TOP_MAX)) return MMDYN_ERR_SHAPE;
+  if ((int64_t)T * N * B * (cand ? cd : 1) >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  const uint32_t* tab = reinterpret_cast<const uint32_t*>(tavail);
+  if (top)
+    hipLaunchKernelGGL(plan_select_steps_kernel<true>, dim3(ew_grid(B)), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows, tab,
+                       step_weight, cand, cand_idx, cd, cost, step_cost, best, best_cost, best_cond, best_idx, top, top_cost, K, N, B, T,
+                       Tg, pose_multiplier, kl_weight, kl_weight_dev);
+  else
+    hipLaunchKernelGGL(plan_select_steps_kernel<false>, dim3(ew_grid(B)), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows, tab,
+                       step_weight, cand, cand_idx, cd, cost, step_cost, best, best_cost, best_cond, best_idx, top, top_cost, 0, N, B, T,
+                       Tg, pose_multiplier, kl_weight, kl_weight_dev);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_gather_best_steps(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, int T, void* stream) {
+  if (!groups || !best) return MMDYN_ERR_NULL;
+  if (G < 1 || G > MMDYN_FEED_GROUPS || N < 1 || B < 1 || T < 1) return MMDYN_ERR_SHAPE;
+  GatherStepsArgs a{};
+  int64_t work[MMDYN_FEED_GROUPS];
+  for (int g = 0; g < G; ++g) {
+    if (!groups->src[g] || !groups->out[g]) return MMDYN_ERR_NULL;
+    if (groups->row_len[g] < 1) return MMDYN_ERR_SHAPE;
+    const int64_t n = (int64_t)B * groups->row_len[g];
+    if (n * N * T >= (1LL << 31)) return MMDYN_ERR_RANGE;
+    // (16-byte accesses are decided per step slice in the kernel; the blocks are counted for the slices that allow them)
+    const bool vec = (((uintptr_t)groups->src[g] | (uintptr_t)groups->out[g]) & 15) == 0;
+    a.src[g] = groups->src[g];
+    a.out[g] = groups->out[g];
+    a.n[g] = n;
+    a.row_len[g] = groups->row_len[g];
+    a.logits[g] = groups->logits[g];
+    a.per_step[g] = (int)ceil_div64(vec && n >= 4 ? n / 4 : n, 256);
+    work[g] = (int64_t)T * a.per_step[g];
+  }
+  // as in mmdyn_gather_best, over all T steps: an out[g] may touch neither the indices, nor any src, nor another out
+  for (int g = 0; g < G; ++g) {
+    if (ranges_overlap(a.out[g], a.n[g] * T * 4, best, (int64_t)B * 4)) return MMDYN_ERR_SHAPE;
+    for (int h = 0; h < G; ++h)
+      if (ranges_overlap(a.out[g], a.n[g] * T * 4, a.src[h], a.n[h] * N * T * 4) ||
+          (h != g && ranges_overlap(a.out[g], a.n[g] * T * 4, a.out[h], a.n[h] * T * 4)))
+        return MMDYN_ERR_SHAPE;
+  }
+  const int blocks = split_blocks(work, G, a.first_block);
+  hipLaunchKernelGGL(gather_best_steps_kernel, dim3(blocks), dim3(256), 0, ST, a, best, G, N, T);
   MMDYN_LAUNCH_CHECK();
 }

@@ -159,6 +159,8 @@ _SIGNATURES = {
     "mmdyn_plan_select": "pppppp" + "i" + "ppppp" + "ii" + "ff" + "pp",
     "mmdyn_gather_best": "p" + "i" + "p" + "ii" + "p",
     "mmdyn_ensemble_feed": "p" + "i" + "p" + "ii" + "p",
+    "mmdyn_plan_select_steps": "ppppppp" + "i" + "pppppppp" + "iiiii" + "ff" + "pp",
+    "mmdyn_gather_best_steps": "p" + "i" + "p" + "iii" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

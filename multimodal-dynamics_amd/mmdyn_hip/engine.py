@@ -1343,7 +1343,8 @@ class MVAEInference:
     packed head / up-sampling weights carry the condition columns, zero-padded to the GEMM's K-step.  A categorical model takes
     class indices; its one-hot rows are written by the join kernel.  :meth:`bad_condition` reports an index out of range.
     :meth:`plan` asks the inverse question: N candidate conditions per row are scored against a goal state and the best one is
-    picked on the device, in one graph whose launch count does not grow with N (up to 8 candidates)."""
+    picked on the device, in one graph whose launch count does not grow with N (up to 8 candidates); :meth:`plan_rollout` asks it
+    over a horizon: N candidate condition sequences are rolled out T steps, and the best one comes back with its trajectory."""
 
     def __init__(self, model, precision="fp32x3", use_graph=True, seed=0):
         from .models.vae import NoiseSource
@@ -1965,6 +1966,189 @@ class MVAEInference:
             ("index" if self.categorical else "real", ("candidates", N, per_row), sample, self._pose_multiplier) + \
             self._shapes((avail, tavail), "avail")
         return self._run(key, lambda *a: self._plan_candidates(N, sample, *a), args)
+
+    def _candidate_steps(self, candidates, B, T):
+        """The request's candidate condition SEQUENCES laid out step-major and candidate-major for the kernels: (fp32
+        [T][N * B][condition_dim], or int64 [T][N * B] for a categorical model; N; whether they were given per row).  A few torch ops
+        on a tiny tensor, before the captured region; the values are not looked at."""
+        cd = self.condition_dim
+        if self.categorical:
+            from .models.vae import _INDEX_DTYPES
+            if not torch.is_tensor(candidates) or candidates.dtype not in _INDEX_DTYPES:
+                raise ValueError("categorical candidates are class indices of an integer dtype, [N, T] or [B, N, T]; got "
+                                 f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
+            per_row = candidates.dim() == 3
+            if candidates.dim() not in (2, 3) or candidates.shape[-1] != T or (per_row and candidates.shape[0] != B):
+                raise ValueError(f"categorical candidates are [N, T={T}] (shared) or [B={B}, N, T={T}] (per row), got "
+                                 f"{tuple(candidates.shape)}")
+            N = candidates.shape[-2]
+            c = candidates.detach().to(device=self.dev, dtype=torch.int64)
+            rows = (c.permute(2, 1, 0) if per_row else c.t().unsqueeze(2).expand(T, N, B)).reshape(T, N * B)
+        else:
+            if not torch.is_tensor(candidates) or not candidates.dtype.is_floating_point:
+                raise ValueError(f"real-valued candidates are a floating-point tensor [N, T, {cd}] or [B, N, T, {cd}], got "
+                                 f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
+            per_row = candidates.dim() == 4
+            if candidates.dim() not in (3, 4) or candidates.shape[-1] != cd or candidates.shape[-2] != T or \
+                    (per_row and candidates.shape[0] != B):
+                raise ValueError(f"real-valued candidates are [N, T={T}, {cd}] (shared) or [B={B}, N, T={T}, {cd}] (per row), got "
+                                 f"{tuple(candidates.shape)}")
+            N = candidates.shape[-3]
+            c = candidates.detach().to(device=self.dev, dtype=torch.float32)
+            rows = (c.permute(2, 1, 0, 3) if per_row else c.transpose(0, 1).unsqueeze(2).expand(T, N, B, cd)).reshape(T, N * B, cd)
+        if N < 1:
+            raise ValueError("plan_rollout needs at least one candidate condition sequence (N >= 1)")
+        return rows.contiguous(), N, per_row
+
+    def _plan_rollout(self, N, T, Tg, sample, top, visual, tactile, pose, gv, gt, gp, cand, avail, tavail, weight):
+        """N candidate condition sequences per row rolled out open loop over T steps on the N * B (candidate, row) rows.  Step 0 is
+        the front half of :meth:`_plan_candidates` (the trunks and the pose heads ONCE on the B rows, the image heads through the
+        tiled join, PoE and the decoders on N * B rows); every later step is the joint forward of the N * B state rows with the
+        step's slice of the candidates; ONE rollout_feed per step writes slot t of the [T][N * B][...] trajectory tensors, which the
+        next step reads.  A scored step (the last one for a final goal, Tg = 1; every one for Tg = T) adds the row kernels with G = N
+        passes against its one goal and kl_rows; tables fp64 [4][Tg][N][B] = (visual, tactile, pose, KL), cleared by one fill.  One
+        plan_select_steps and one gather_best_steps launch close the request."""
+        select, gather, feed = (ops.backend_op(k) for k in ("plan_select_steps", "gather_best_steps", "rollout_feed"))
+        ops.backend_op("concat_condition_tiled")        # (a backend without the join: an error before anything is launched)
+        (B, dev), L, S = self._rows_of(visual, tactile, pose, avail), self.L, self.model.visual_decoder.image_size
+        NB = N * B
+        traj = [torch.empty(T, NB, 3, S, S, device=dev), torch.empty(T, NB, 3, S, S, device=dev),
+                torch.empty(T, NB, 7, device=dev) if self.use_pose else None]
+        means, log_var = torch.empty(T, NB, L, device=dev), torch.empty(T, NB, L, device=dev)
+        tab = torch.zeros(4, Tg, N, B, dtype=torch.float64, device=dev)
+        kl = tab[3]
+        step_of = lambda t, i: None if t is None else t[i]
+        state = [visual, tactile, pose]
+        with self._index_scope():
+            for i in range(T):
+                c_i = cand[i]
+                if i == 0:
+                    heads = self._heads(state[0], state[1], state[2], c_i, x_rows=B)
+                    if heads[2] is not None:
+                        heads[2] = heads[2].repeat(N, 1)
+                else:
+                    heads = self._heads(state[0], state[1], state[2], c_i)
+                # one draw per row and step, shared by the row's candidates
+                eps = (self._draw_latent(B) if sample else self._zero_latent(B)).repeat(N, 1)
+                mu, lv, z = self._poe(heads, avail.repeat(N, 1) if i == 0 and avail is not None else None, eps, NB, dev,
+                                      out=(means[i], log_var[i]))
+                v, t, pr = self._decode(z, c_i)
+                if Tg == T or i == T - 1:
+                    s = i if Tg == T else 0
+                    self._row_terms(N, B, v, t, pr, step_of(gv, s), step_of(gt, s), step_of(gp, s), None, (tab[0, s], tab[1, s], tab[2, s]))
+                    ops.B.kl_rows(mu, lv, kl[s].view(1, NB), 1, NB, L)
+                groups = [{"recon": v, "obs": None, "out": traj[0][i], "logits": True, "column": 0},
+                          {"recon": t, "obs": None, "out": traj[1][i], "logits": True, "column": 1}]
+                if self.use_pose:
+                    groups.append({"recon": pr, "obs": None, "out": traj[2][i], "logits": False, "column": 2})
+                feed(groups, None, NB)
+                state = [traj[0][i], traj[1][i], traj[2][i] if self.use_pose else None]
+        cost, step_cost = torch.empty(N, B, device=dev), torch.empty(Tg, N, B, device=dev)
+        best, best_cost = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev)
+        best_cond = torch.empty((B, T) + tuple(cand.shape[2:]), dtype=cand.dtype, device=dev)
+        top_idx = top_cost = None
+        if top is not None:
+            top_idx, top_cost = torch.empty(top, B, dtype=torch.int32, device=dev), torch.empty(top, B, device=dev)
+        select(tab[:2] if gv is not None or gt is not None else None, tab[2] if gp is not None else None, kl, tavail, weight, cand,
+               cost, step_cost, best, best_cost, best_cond, top_idx, top_cost, N, B, T, Tg, self._pose_multiplier, 1.0, self._klw)
+        outs = [{"src": x, "out": torch.empty((T, B) + tuple(x.shape[2:]), device=dev), "logits": False} for x in traj if x is not None]
+        gather(outs, best, N, B, T)
+        split = lambda x: None if x is None else x.view((T, N, B) + tuple(x.shape[2:]))
+        res = {"cost": cost, "step_cost": step_cost, "best": best, "best_cost": best_cost, "best_condition": best_cond,
+               "trajectory": [g["out"] for g in outs] + ([] if self.use_pose else [None]),
+               "visual": split(traj[0]), "tactile": split(traj[1]), "pose": split(traj[2]),
+               **self._terms(tab[:3], (gv, gt, gp)), "kl": kl, "means": split(means), "log_var": split(log_var)}
+        if top is not None:
+            res.update(top=top_idx, top_cost=top_cost)
+        return res
+
+    @torch.no_grad()
+    def plan_rollout(self, x, pose=None, steps=1, goal=None, candidates=None, step_weight=None, top=None, kl_weight=0.0,
+                     pose_multiplier=1000.0, available=None, goal_available=None, sample=False):
+        """:meth:`plan` over a horizon: which of N candidate condition SEQUENCES takes the state ``x`` (+ ``pose``, ``available``:
+        as in :meth:`forward`) to the goal over the next ``steps`` = T applications of the model?  Every sequence is rolled out open
+        loop (:meth:`rollout` with nothing observed) on the N * B (candidate, row) rows, scored against the goal, and the best one
+        is picked on the device together with its trajectory -- ONE captured graph, the random-shooting planner of model-predictive
+        control.  Step 0 runs the encoder trunks once on the B rows (the image heads, the PoE launch and the decoders on N * B
+        rows); every later step is the joint forward of the N * B state rows under the step's conditions.
+
+        ``candidates`` (required): fp [N, T, condition_dim] (shared by every row) or [B, N, T, condition_dim] (per row); for a
+        categorical model class indices of any integer dtype, [N, T] or [B, N, T].  A static input of the graph: the key carries N,
+        T, the kind and whether they are per row, never the values; :meth:`bad_condition` covers the whole call.  ``goal`` =
+        [visual | None, tactile | None, pose | None] with at least one entry; every given tensor [B, ...] -- a FINAL goal, only
+        step T-1 is scored (Tg = 1) -- or every one [T, B, ...] -- every step is scored against its own goal (Tg = T);
+        ``goal_available``: [B, 2 | 3] or [T, B, 2 | 3] to match, in the forms ``target_available`` of :meth:`score` takes.  An
+        unscored step issues no row kernel.  ``step_weight``: fp [Tg] or None (all ones); it lives in device memory, its values
+        are never looked at (NaN / Inf propagate).  ``sample=False`` decodes posterior means; ``sample=True`` draws ONE [B, L]
+        block per step from the engine's Philox stream, shared by the N candidates of a row (common random numbers, as in
+        :meth:`plan`); the stream advances as :meth:`rollout`'s does.
+
+        step_cost[t][n][b] = the cost of :meth:`plan` for step t of candidate n, in fp64; cost[n][b] = sum_t step_weight[t] *
+        step_cost[t][n][b] in fp64, t ascending.  The smallest total wins under the rules of :meth:`plan` (ties: the lowest n; a
+        NaN total never wins; all NaN: best = -1, NaN outputs).  ``top`` = K in [1, MMDYN_PLAN_TOP_MAX = 8] also returns the K best
+        candidates per row in ascending order (the building block of iterative refitting; -1 / NaN past the non-NaN candidates).
+
+        Returns a dict of the graph's static outputs (copy what must survive the next call of the same shapes): ``cost`` fp32
+        [N, B]; ``step_cost`` fp32 [Tg, N, B]; ``best`` int32 [B]; ``best_cost`` fp32 [B]; ``best_condition`` fp32 [B, T,
+        condition_dim] (categorical: int64 [B, T]); ``trajectory`` = [visual, tactile, pose | None], the winner's states [T, B, ...]
+        (slot t = s_{t+1}, image space); ``visual`` / ``tactile`` / ``pose``: all states, [T, N, B, ...]; ``bce_visual`` /
+        ``bce_tactile`` / ``mse_pose`` (fp64 [Tg, N, B], None without that goal; an absent (step, row, term) is 0) and ``kl`` (fp64
+        [Tg, N, B]); ``means`` / ``log_var`` [T, N, B, L]; with ``top``: ``top`` int32 [K, B] and ``top_cost`` fp32 [K, B].  Nothing
+        synchronises.  ValueError: an unconditional model, no goal, goals of both forms, N < 1, ``steps`` no integer >= 1, wrong
+        shapes or dtypes, ``top`` outside [1, 8], or a trajectory tensor / the decoders' largest N * B-row activation reaching 2^31
+        elements.  Out of scope: observations inside a plan, ``loss_mask``."""
+        if not self.conditional:
+            raise ValueError("candidate conditions were passed to an unconditional model")
+        T = self._count("steps", steps, "model applications")
+        ins, B = self._request("plan_rollout", x, pose, available, cast=True)
+        cand, N, per_row = self._candidate_steps(candidates, B, T)
+        S = self.model.visual_decoder.image_size
+        most = min(((1 << 31) - 1) // (T * B * 3 * S * S), ((1 << 31) - 1) // (B * self._decoder_row()))
+        if N > most:
+            raise ValueError(f"candidates = {N} condition sequences of B = {B} rows over steps = {T} make a trajectory tensor or a "
+                             f"decoder activation of 2^31 elements or more; the largest N for B = {B} and steps = {T} is {most}")
+        if top is not None:
+            if isinstance(top, bool) or not isinstance(top, numbers.Integral) or not 1 <= top <= ops.PLAN_TOP_MAX:
+                raise ValueError(f"top must be an integer in [1, {ops.PLAN_TOP_MAX}] (the best candidates listed per row), got {top!r}")
+            top = int(top)
+        if not isinstance(goal, (list, tuple)) or len(goal) > 3:
+            raise ValueError("goal must be a list [visual | None, tactile | None, pose | None]")
+        goal = (list(goal) + [None] * 3)[:3]
+        if not self.use_pose:
+            goal[2] = None
+        given = [(i, t) for i, t in enumerate(goal) if t is not None]
+        if not given:
+            raise ValueError("plan_rollout needs a goal: at least one of [visual, tactile, pose]")
+        if not all(torch.is_tensor(t) for _, t in given):
+            raise ValueError("goal must hold tensors")
+        # an image [B, 3, S, S] / a pose [B, 7] is a final goal, one more leading dimension a goal per step
+        forms = {t.dim() - (4 if i < 2 else 2) for i, t in given}
+        if not forms <= {0, 1}:
+            raise ValueError("goal tensors are [B, ...] (a final goal) or [T, B, ...] (one per step)")
+        if len(forms) > 1:
+            raise ValueError("goal mixes the two forms: every tensor is [B, ...] (a final goal) or every one [T, B, ...] (one per step)")
+        Tg = 1 if forms == {0} else T
+        if forms == {0}:
+            tg = [None if t is None else t.to(device=self.dev, dtype=torch.float32).unsqueeze(0)
+                  for t in self._targets("goal", goal, B)]
+            tavail = self._availability(goal_available, B)
+            tavail = None if tavail is None else tavail.view(1, B, -1)
+        else:
+            tg = self._step_tensors("goal", goal, T, B)
+            tavail = self._step_availability("goal_available", goal_available, T, B)
+        weight = None
+        if step_weight is not None:
+            if not torch.is_tensor(step_weight) or not step_weight.dtype.is_floating_point or tuple(step_weight.shape) != (Tg,):
+                raise ValueError(f"step_weight must be a floating-point tensor [Tg={Tg}] (one weight per scored step), got "
+                                 f"{tuple(step_weight.shape) if torch.is_tensor(step_weight) else type(step_weight).__name__}")
+            weight = step_weight.detach().to(device=self.dev, dtype=torch.float32).contiguous()
+        self._set_weights(kl_weight, pose_multiplier)
+        sample = bool(sample)
+        avail = self._availability(available, B)
+        args = ins + tg + [cand, avail, tavail, weight]
+        key = ("plan_rollout", T, Tg, top, sample, self._pose_multiplier, "index" if self.categorical else "real",
+               ("candidates", N, per_row)) + self._shapes(ins + tg + [weight]) + self._shapes((avail, tavail), "avail")
+        return self._run(key, lambda *a: self._plan_rollout(N, T, Tg, sample, top, *a), args)
 
     def _rollout(self, T, sample, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
         """T forwards in a row, each followed by ONE feed launch that writes the next state into its trajectory slot, where the

@@ -20,6 +20,7 @@ from ._lib import PassExperts, FeedGroups, GatherGroups, EnsembleGroups, MAX_PAS
 ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
 DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0 = 0, 1, 2, 3, 4
 ROW_GROUPS_MAX = 8         # MMDYN_BCE_GROUPS_MAX: the passes one launch of a *_groups kernel walks over its target
+PLAN_TOP_MAX = 8           # MMDYN_PLAN_TOP_MAX: the longest list of best candidates mmdyn_plan_select_steps keeps per row
 
 
 def _ptr(t, dtype=torch.float32):
@@ -1096,6 +1097,89 @@ class HipBackend:
             arg.row_len[g], arg.logits[g] = grp["out"].numel() // B, int(bool(grp["logits"]))
         check(self.lib.mmdyn_gather_best(ctypes.addressof(arg), len(groups), _ptr(best, torch.int32), N, B, _stream()),
               "mmdyn_gather_best")
+
+    # ---- candidate condition sequences over T steps: the weighted total, the winner of each row, the winner's trajectory ----
+    def plan_select_steps(self, bce_rows, mse_rows, kl_rows, tavail, step_weight, candidates, cost, step_cost, best, best_cost,
+                          best_condition, top, top_cost, N, B, T, Tg, pose_multiplier, kl_weight=1.0, kl_weight_dev=None):
+        """:meth:`plan_select` over Tg scored steps (Tg = 1: a final goal; Tg = T: every step): step_cost [Tg][N][B] fp32 = the
+        cost of :meth:`plan_select` per step; cost [N][B] fp32 = sum_t step_weight[t] * c_t in fp64, t ascending, nothing fused
+        (step_weight None: the plain sum); best / best_cost: the smallest fp64 total under the rules there.  bce_rows: fp64
+        [2][Tg][N][B] or None; mse_rows: fp64 [Tg][N][B] or None; kl_rows: fp64 [Tg][N][B]; tavail: uint8 [Tg][B][4] or None;
+        step_weight: fp32 [Tg] on the device or None.  candidates, step-major and candidate-major: fp32 [T][N * B][cd] with
+        best_condition fp32 [B][T][cd], or int64 [T][N * B] with best_condition int64 [B][T].  top / top_cost (both or neither):
+        int32 / fp32 [K][B], K <= PLAN_TOP_MAX -- the K smallest totals in ascending order, -1 / NaN past the non-NaN candidates."""
+        name, N, B, T, Tg = "plan_select_steps", int(N), int(B), int(T), int(Tg)
+        if N < 1 or B < 1 or T < 1 or Tg not in (1, T):
+            raise ValueError(f"mmdyn_plan_select_steps: N = {N}, B = {B} and T = {T} must be positive and Tg = {Tg} be 1 or T")
+        if not torch.is_tensor(candidates) or candidates.dtype not in (torch.float32, torch.int64):
+            raise ValueError(f"mmdyn_plan_select_steps: candidates must be fp32 [T][N * B][cd] or int64 [T][N * B], got "
+                             f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
+        index = candidates.dtype == torch.int64
+        if index:
+            cd, shapes = 1, ((T, N * B), (B, T))
+        else:
+            if candidates.dim() != 3 or candidates.shape[2] < 1:
+                raise ValueError(f"mmdyn_plan_select_steps: real-valued candidates must be [T = {T}][N * B = {N * B}][cd], got "
+                                 f"{tuple(candidates.shape)}")
+            cd = candidates.shape[2]
+            shapes = ((T, N * B, cd), (B, T, cd))
+        if any(t is None for t in (kl_rows, cost, step_cost, best, best_cost, best_condition)):
+            raise ValueError("mmdyn_plan_select_steps: kl_rows, cost, step_cost, best, best_cost and best_condition are required")
+        if (top is None) != (top_cost is None):
+            raise ValueError("mmdyn_plan_select_steps: top and top_cost come together")
+        K = 0
+        if top is not None:
+            K = top.shape[0] if torch.is_tensor(top) and top.dim() == 2 else 0
+            if not 1 <= K <= PLAN_TOP_MAX:
+                raise ValueError(f"mmdyn_plan_select_steps: top must be int32 [K][B = {B}] with K in [1, {PLAN_TOP_MAX}], got "
+                                 f"{tuple(top.shape) if torch.is_tensor(top) else type(top).__name__}")
+        f32, f64, i32, ctype = torch.float32, torch.float64, torch.int32, candidates.dtype
+        tp = None
+        if tavail is not None:
+            if not torch.is_tensor(tavail) or tavail.dim() != 3 or tuple(tavail.shape[:2]) != (Tg, B) or not tavail.is_contiguous():
+                raise ValueError(f"mmdyn_hip: {name}: the availability tables must be a contiguous uint8 [Tg={Tg}][B={B}][{MAX_EXPERTS}] "
+                                 f"tensor, got {tuple(tavail.shape) if torch.is_tensor(tavail) else type(tavail).__name__}")
+            tp = self._avail(tavail.view(Tg * B, tavail.shape[2]), Tg * B, name, cost)
+        bp, mp, kp, wp, cp, op, scp, sp, bcp, qp, tkp, tcp = self._iw_tables(
+            name, (bce_rows, (2, Tg, N, B), "bce_rows", f64), (mse_rows, (Tg, N, B), "mse_rows", f64),
+            (kl_rows, (Tg, N, B), "kl_rows", f64), (step_weight, (Tg,), "step_weight", f32), (candidates, shapes[0], "candidates", ctype),
+            (cost, (N, B), "cost", f32), (step_cost, (Tg, N, B), "step_cost", f32), (best, (B,), "best", i32),
+            (best_cost, (B,), "best_cost", f32), (best_condition, shapes[1], "best_condition", ctype), (top, (K, B), "top", i32),
+            (top_cost, (K, B), "top_cost", f32))
+        check(self.lib.mmdyn_plan_select_steps(bp, mp, kp, tp, wp, None if index else cp, cp if index else None, cd, op, scp, sp, bcp,
+                                               None if index else qp, qp if index else None, tkp, tcp, K, N, B, T, Tg,
+                                               float(pose_multiplier), float(kl_weight), _ptr(kl_weight_dev), _stream()),
+              "mmdyn_plan_select_steps")
+
+    def gather_best_steps(self, groups, best, N, B, T):
+        """:meth:`gather_best` on all T steps in one launch: ``groups`` is a list of dicts {src, out, logits}; out[t][b] =
+        f(src[t][best[b] * B + b]).  src: contiguous fp32 [T, N * B, ...]; out: contiguous fp32 [T, B, ...] of the same row shape,
+        overlapping no src and no other out of the call; best: int32 [B] -- a row whose index lies outside [0, N) is filled with
+        NaN in every step and reads nothing.  The bits of T :meth:`gather_best` calls on the step slices."""
+        name, N, B, T = "gather_best_steps", int(N), int(B), int(T)
+        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
+            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
+                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
+        if N < 1 or B < 1 or T < 1:
+            raise ValueError(f"mmdyn_hip: {name}: N = {N}, B = {B} and T = {T} must be positive")
+        if not torch.is_tensor(best) or best.dtype != torch.int32 or tuple(best.shape) != (B,) or not best.is_contiguous():
+            raise ValueError(f"mmdyn_hip: {name}: best must be a contiguous int32 [B={B}] tensor")
+        arg = GatherGroups()
+        for g, grp in enumerate(groups):
+            src, out = grp["src"], grp["out"]
+            for t, rows, what in ((src, N * B, "src"), (out, B, "out")):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 2 or \
+                        tuple(t.shape[:2]) != (T, rows):
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor [T={T}][{rows}][...], got "
+                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+            if src.numel() == 0 or tuple(src.shape[2:]) != tuple(out.shape[2:]) or src.device != best.device or out.device != best.device:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: src {tuple(src.shape)} on {src.device} and out {tuple(out.shape)} on "
+                                 f"{out.device} must share a non-empty row shape and the device of best")
+        for g, grp in enumerate(groups):
+            arg.src[g], arg.out[g] = _ptr(grp["src"]), _ptr(grp["out"])
+            arg.row_len[g], arg.logits[g] = grp["out"].numel() // (T * B), int(bool(grp["logits"]))
+        check(self.lib.mmdyn_gather_best_steps(ctypes.addressof(arg), len(groups), _ptr(best, torch.int32), N, B, T, _stream()),
+              "mmdyn_gather_best_steps")
 
     # ---- ensemble rollout: the N * B decoder rows of a step -> the N * B next states + the ensemble's statistics ----
     def ensemble_feed(self, groups, obs_avail, N, B):

@@ -762,6 +762,23 @@ class DynModeling(SeqModeling):
                 {'target_output': to, 'target_object_pose': [torch.roll(data[2], -1, dims=0).to(dev)],
                  'loss_mask': target[3].to(dev)})
 
+    def _recorded_steps(self, data, target, T, n):
+        """The recorded continuation of the n sequences of a loader batch over T steps: (``steps_of``, targets [visual, tactile,
+        pose | None] each [T, n, ...], their availability [T, n, 3]).  The target of step t is frame t + 1 and, for t + 1 = l, the
+        dataset's final target, counted as present; the pose target always counts."""
+        l, dev = int(self._seq_length), self._device
+
+        def steps_of(frames, last):
+            """[T, n, ...]: frame t + 1 of every sequence for t + 1 < l, ``last`` [n, ...] for t + 1 = l."""
+            f = frames.reshape((n, l) + tuple(frames.shape[1:]))[:, 1:T + 1].transpose(0, 1)
+            return (f if T < l else torch.cat((f, last.unsqueeze(0).to(f.dtype)), 0)).to(dev)
+
+        targets = [steps_of(data[0], target[0][l - 1::l]), steps_of(data[1], target[1][l - 1::l]),
+                   steps_of(data[2], target[2][l - 1::l]) if self._model._use_pose else None]
+        has = data[3].to(torch.float32)
+        tavail = torch.cat((steps_of(has[:, :2], torch.ones(n, 2)), torch.ones(T, n, 1, device=dev)), 2)
+        return steps_of, targets, tavail
+
     def rollout(self, data_input, data_target, steps=None, observe=(), sample=False, samples=None):
         """The one-step predictor applied to its own output along each sequence of one loader batch (cnn-mvae; n sequences of l
         frames as flat [n*l, ...] tensors): :meth:`mmdyn_hip.engine.MVAEInference.rollout` from frame 0 of every sequence (with its
@@ -792,16 +809,8 @@ class DynModeling(SeqModeling):
             raise ValueError(f"a batch of {data[0].shape[0]} frames does not hold whole sequences of {l}")
         n = data[0].shape[0] // l
         use_pose = bool(self._model._use_pose)
-
-        def steps_of(frames, last):
-            """[T, n, ...]: frame t + 1 of every sequence for t + 1 < l, ``last`` [n, ...] for t + 1 = l."""
-            f = frames.reshape((n, l) + tuple(frames.shape[1:]))[:, 1:T + 1].transpose(0, 1)
-            return (f if T < l else torch.cat((f, last.unsqueeze(0).to(f.dtype)), 0)).to(dev)
-
-        targets = [steps_of(data[0], target[0][l - 1::l]), steps_of(data[1], target[1][l - 1::l]),
-                   steps_of(data[2], target[2][l - 1::l]) if use_pose else None]
+        steps_of, targets, tavail = self._recorded_steps(data, target, T, n)
         has = data[3].to(torch.float32)
-        tavail = torch.cat((steps_of(has[:, :2], torch.ones(n, 2)), torch.ones(T, n, 1, device=dev)), 2)
         observed = oavail = None
         if observe:
             # past the recorded frames (t + 1 = l) nothing is observed: a zero frame the table switches off
@@ -855,4 +864,44 @@ class DynModeling(SeqModeling):
             clone = lambda v: None if v is None else ([clone(t) for t in v] if isinstance(v, (list, tuple)) else v.clone())
             out = {k: clone(v) for k, v in res.items()}
             out["recorded"] = inputs['shock']
+            return out
+
+    def plan_rollout(self, data_input, data_target, candidates=None, steps=None, step_weight=None, top=None):
+        """Which of N candidate shock SEQUENCES takes frame 0 of each of the n sequences of one loader batch along its recorded
+        continuation (cnn-mvae, ``--conditional``): :meth:`mmdyn_hip.engine.MVAEInference.plan_rollout` with the batch built as
+        :meth:`rollout` builds it -- start = frame 0 of every sequence with its ``data[3]`` availability, goal = frames 1 .. T with
+        their availability (the dataset's final target for t + 1 = l; the pose goal always counts), every step scored --, the
+        problem's KL weight and pose multiplier, posterior-mean latents.  ``candidates``: as the engine takes them; None: the
+        batch's own n recorded shock sequences (``data[4]``, [n, T, ...]), shared by every row, so the row's own sequence is
+        candidate b.  ``steps`` <= l (default l), ``step_weight`` [T], ``top``: as the engine takes them.  Eval-mode arithmetic as
+        in :meth:`plan`.  Returns clones of the engine's dict plus ``recorded``: the [n, T, ...] shocks."""
+        if 'mvae' not in str(self.parameters.get('model_name')):
+            raise ValueError(f"plan_rollout() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
+        if not isinstance(data_input, (list, tuple)) or len(data_input) < 4 or self.parameters.get('input_type') != 'visuotactile':
+            raise ValueError("plan_rollout() takes a visuotactile batch in the loader's format (a list of tensors)")
+        if not self._conditional:
+            raise ValueError("plan_rollout() was called on an unconditional model: candidate conditions need --conditional")
+        if len(data_input) < 5:
+            raise ValueError("a conditional model needs the shock force of every frame (data[4])")
+        l = int(self._seq_length)
+        T = l if steps is None else steps
+        if isinstance(T, bool) or not isinstance(T, int) or T < 1 or T > l:
+            raise ValueError(f"steps must be an integer in [1, {l}] (the sequences hold {l} frames), got {steps!r}")
+        data, target, dev = list(data_input), list(data_target), self._device
+        if data[0].shape[0] % l:
+            raise ValueError(f"a batch of {data[0].shape[0]} frames does not hold whole sequences of {l}")
+        n = data[0].shape[0] // l
+        _, goal, goal_has = self._recorded_steps(data, target, T, n)
+        recorded = data[4].reshape((n, l) + tuple(data[4].shape[1:]))[:, :T].to(dev)
+        if recorded.dim() == 3 and self._model.categorical_conditions and recorded.shape[2] == 1:
+            recorded = recorded[:, :, 0]
+        with self._serving('_horizon_planner') as eng:
+            res = eng.plan_rollout([data[0][::l].to(dev), data[1][::l].to(dev)],
+                                   pose=data[2][::l].to(dev) if self._model._use_pose else None, steps=T, goal=goal,
+                                   candidates=recorded if candidates is None else candidates, step_weight=step_weight, top=top,
+                                   kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier, available=data[3][::l].to(dev),
+                                   goal_available=goal_has)
+            clone = lambda v: None if v is None else ([clone(t) for t in v] if isinstance(v, (list, tuple)) else v.clone())
+            out = {k: clone(v) for k, v in res.items()}
+            out["recorded"] = recorded
             return out
