@@ -783,6 +783,44 @@ int mmdyn_plan_select_steps(double* bce_rows, double* mse_rows, const double* kl
  * Both added without touching an existing signature or workspace: the revision stays 6. */
 int mmdyn_gather_best_steps(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, int T, void* stream);
 
+/* ---- iterative refinement of a candidate distribution (MVAEInference.plan_refine: the cross-entropy method on the horizon
+ * planner -- sample N condition sequences per row from N(mean, std^2), roll them out, refit mean / std to the K best, repeat; the
+ * reference has no such operation) ----------------------------------------------------------------------------------------
+ * mmdyn_plan_sample: the candidates of one iteration, in the layout mmdyn_plan_select_steps and the planner's steps read:
+ *   cand[t][n * B + b][d] = clamp(n == 0 ? (keep && keep[b][t][d] is no NaN ? keep[b][t][d] : mean[b][t][d])
+ *                                        : mean[b][t][d] + std[b][t][d] * eps[n][b][t][d]),
+ * the product rounded to fp32, then the sum rounded to fp32 (no fused multiply-add); clamp(c) = c < lo[d] ? lo[d] : (c > hi[d] ?
+ * hi[d] : c) with bounds, c without -- a NaN stays a NaN.  Slot n = 0 is the incumbent (the best sequence of the previous
+ * iteration, or the mean): its eps is never read.  mean, std: [B][T][cd]; eps: [N][B][T][cd]; keep: [B][T][cd] or null; lo, hi:
+ * [cd], both or neither; cand: [T][N * B][cd], an OUTPUT that overlaps no input.  All fp32.  One element per thread, or 16-byte
+ * accesses where cd % 4 == 0 and every pointer is 16-byte aligned (the same values either way).  No LDS, no atomics.
+ * Checked on the host: mean, std, eps or cand null, or one bound without the other: MMDYN_ERR_NULL; N, B, T or cd < 1, or cand
+ * overlapping an input: MMDYN_ERR_SHAPE; N * B * T * cd >= 2^31: MMDYN_ERR_RANGE.
+ *
+ * mmdyn_plan_refit: the elites of every row and the distribution refitted to them.  cost: [N][B] float, as
+ * mmdyn_plan_select_steps writes it; cand: [T][N * B][cd]; mean_in, std_in: [B][T][cd].  Per row b:
+ *   candidate n is an ELITE iff cost[n][b] is no NaN and fewer than K candidates m have cost[m][b] < cost[n][b], or cost[m][b] ==
+ *   cost[n][b] with m < n: the K smallest, ties to the lower n, a NaN never, +Inf / -Inf ordinary values (the rules of
+ *   mmdyn_plan_select, on the fp32 cost).  K' = the number of elites (K' < K when fewer than K costs are no NaN).
+ *   K' == 0: mean_out = mean_in, std_out = std_in, bit for bit.  Otherwise per element (t, d), in fp64, over the elites in
+ *   ascending n, every sum, product, quotient and root rounded on its own (no fused multiply-add):
+ *     m = (sum (double)c_n) / K';  v = (sum ((double)c_n - m)^2) / K';  s = sqrt(v);
+ *     mean_out = (float)((double)alpha * (double)mean_in + (1.0 - (double)alpha) * m);
+ *     std_out  = fmaxf((float)((double)alpha * (double)std_in + (1.0 - (double)alpha) * s), std_min).
+ * mean_out, std_out: [B][T][cd], each may be exactly its input; elite (may be null): [N][B] bytes, 1 = elite; count (may be null):
+ * [B] int = K'.  One block of 256 threads per row: the cost column and the flags in LDS (MMDYN_REFIT_N_MAX * 5 bytes), ranks by
+ * counting, one fixed summation order; no atomics: the same bits in every run.  Candidates that are no elites are not loaded.
+ * Checked on the host: cost, cand, mean_in, std_in, mean_out or std_out null: MMDYN_ERR_NULL; B, T or cd < 1, N outside
+ * [1, MMDYN_REFIT_N_MAX], K outside [1, N], alpha outside [0, 1), std_min < 0 (or either a NaN), or an output that overlaps
+ * anything but its own input: MMDYN_ERR_SHAPE; N * B * T * cd >= 2^31: MMDYN_ERR_RANGE.
+ * Both added without touching an existing signature or workspace: the revision stays 6. */
+#define MMDYN_REFIT_N_MAX 4096
+int mmdyn_plan_sample(const float* mean, const float* std, const float* eps, const float* keep, const float* lo, const float* hi,
+                      float* cand, int N, int B, int T, int cd, void* stream);
+int mmdyn_plan_refit(const float* cost, const float* cand, const float* mean_in, const float* std_in, float* mean_out,
+                     float* std_out, uint8_t* elite, int* count, int K, int N, int B, int T, int cd, float alpha, float std_min,
+                     void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call
  * (graph-replay safe); p/g/m/v: flat fp32 buffers of n elements; g is multiplied by grad_scale first */

@@ -25,7 +25,11 @@
 //     decoder rows of a step become the N * B next states under observations that exist once per request row, and the same read
 //     of the logits leaves the ensemble's per-element mean and variance and each row's summed variance.  An element scheme of
 //     its own (a thread walks the samples of one quad); its out has the bits of rollout_feed on the N * B rows.
-// Memory-bound, no LDS, no scratch; no atomics except ensemble_feed's spread accumulator.
+//   - plan_sample / plan_refit: the two launches that turn the horizon planner into the cross-entropy method
+//     (MVAEInference.plan_refine).  plan_sample writes an iteration's candidates mean + std * eps (slot 0: the incumbent), clamped,
+//     straight into the [T][N * B][cd] layout the steps read; plan_refit ranks a row's [N] cost column in LDS, flags the K smallest
+//     and refits mean / std over them in fp64, one block per row.
+// Memory-bound, no LDS (plan_refit: 20 KB), no scratch; no atomics except ensemble_feed's spread accumulator.
 #include "common.h"
 
 namespace {
@@ -498,6 +502,138 @@ __global__ __launch_bounds__(256) void gather_best_steps_kernel(const GatherStep
   }
 }
 
+// ---- iterative refinement of a candidate distribution (CEM): the candidates of an iteration, the elites and the refit ----
+
+// c = mean + std * eps, the product and the sum rounded on their own: the pragma as in plan_cost.
+__device__ __forceinline__ float sample_value(float mean, float std, float eps) {
+#pragma clang fp contract(off)
+  const float p = std * eps;
+  return mean + p;
+}
+
+// cand [T][N * B][cd] as items of W floats (W = 4: cd % 4 == 0 and every pointer 16-byte aligned, so an item lies in one (t, n, b)
+// row and every operand's offset is a multiple of four; W = 1 otherwise), one item per thread.  Item i of the output sits at
+// ((t * N + n) * B + b) * cd + d; mean / std / keep are [B][T][cd], eps [N][B][T][cd].  Slot n = 0 is the incumbent: keep where it
+// is given and no NaN, mean otherwise, and its eps is not loaded.
+template <int W>
+__global__ __launch_bounds__(256) void plan_sample_kernel(const float* __restrict__ mean, const float* __restrict__ std,
+                                                          const float* __restrict__ eps, const float* __restrict__ keep,
+                                                          const float* __restrict__ lo, const float* __restrict__ hi,
+                                                          float* __restrict__ cand, int N, int B, int T, int cd, int64_t items) {
+  const int per_row = cd / W;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    const int d = (int)(i % per_row) * W;
+    const int64_t row = i / per_row;                     // (t * N + n) * B + b
+    const int b = (int)(row % B);
+    const int64_t tn = row / B;
+    const int n = (int)(tn % N), t = (int)(tn / N);
+    const int64_t src = ((int64_t)b * T + t) * cd + d;
+    float m[W], c[W];
+    ld_w<W>(mean + src, m);
+    if (n == 0) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) c[k] = m[k];
+      if (keep) {
+        float kp[W];
+        ld_w<W>(keep + src, kp);
+#pragma unroll
+        for (int k = 0; k < W; ++k) c[k] = kp[k] == kp[k] ? kp[k] : m[k];
+      }
+    } else {
+      float s[W], e[W];
+      ld_w<W>(std + src, s);
+      ld_w<W>(eps + (((int64_t)n * B + b) * T + t) * cd + d, e);
+#pragma unroll
+      for (int k = 0; k < W; ++k) c[k] = sample_value(m[k], s[k], e[k]);
+    }
+    if (lo) {
+      float l[W], h[W];
+      ld_w<W>(lo + d, l);
+      ld_w<W>(hi + d, h);
+#pragma unroll
+      for (int k = 0; k < W; ++k) c[k] = c[k] < l[k] ? l[k] : (c[k] > h[k] ? h[k] : c[k]);
+    }
+    st_w<W>(cand + row * cd + d, c);
+  }
+}
+
+// The refit's arithmetic in its written order, every product, quotient and sum rounded on its own (the pragma as in plan_cost).
+__device__ __forceinline__ double add_square(double acc, double c, double m) {
+#pragma clang fp contract(off)
+  const double d = c - m;
+  const double sq = d * d;
+  return acc + sq;
+}
+__device__ __forceinline__ double blend(double alpha, double prev, double fit) {
+#pragma clang fp contract(off)
+  const double a = alpha * prev;
+  const double rest = 1.0 - alpha;
+  const double f = rest * fit;
+  return a + f;
+}
+
+// One block of 256 threads per row b.  The row's cost column goes into LDS (padded with NaN to a multiple of four, so the rank
+// walk reads quads; every lane reads the same address: a broadcast); thread n counts the candidates in front of n -- a smaller
+// cost, or an equal one with a smaller index; a NaN is in front of nothing and is itself never an elite -- and n is an elite iff
+// fewer than K are.  The flags stay in LDS; their number K' is summed by the shuffle and four LDS words.  Each thread then owns
+// elements (t, d) and walks n = 0 .. N-1 twice, loading the candidates of the elites only: one fixed summation order, no
+// compaction.  mean_out / std_out may be mean_in / std_in (an element is read and written by the same thread).
+__global__ __launch_bounds__(256) void plan_refit_kernel(const float* __restrict__ cost, const float* __restrict__ cand,
+                                                         const float* mean_in, const float* std_in, float* mean_out, float* std_out,
+                                                         uint8_t* __restrict__ elite, int* __restrict__ count, int K, int N, int B,
+                                                         int T, int cd, float alpha, float std_min) {
+  __shared__ __attribute__((aligned(16))) float cost_s[MMDYN_REFIT_N_MAX];
+  __shared__ uint8_t flag_s[MMDYN_REFIT_N_MAX];
+  __shared__ int part_s[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int N4 = (N + 3) & ~3;
+  for (int n = tid; n < N4; n += 256) cost_s[n] = n < N ? cost[(size_t)n * B + b] : NAN;
+  __syncthreads();
+  int mine = 0;
+  for (int n = tid; n < N; n += 256) {
+    const float c = cost_s[n];
+    int ahead = 0;
+    for (int m = 0; m < N4; m += 4) {
+      const f32x4 q = *reinterpret_cast<const f32x4*>(cost_s + m);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ahead += (q[k] < c || (q[k] == c && m + k < n)) ? 1 : 0;
+    }
+    const int flag = (c == c && ahead < K) ? 1 : 0;
+    flag_s[n] = (uint8_t)flag;
+    if (elite) elite[(size_t)n * B + b] = (uint8_t)flag;
+    mine += flag;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  if ((tid & 63) == 0) part_s[tid >> 6] = mine;
+  __syncthreads();
+  const int kp = part_s[0] + part_s[1] + part_s[2] + part_s[3];
+  if (count && tid == 0) count[b] = kp;
+  const double a = (double)alpha, inv = (double)kp;
+  const size_t step = (size_t)N * B * cd;                // the floats of one step slice of cand
+  for (int e = tid; e < T * cd; e += 256) {
+    const int t = e / cd, d = e % cd;
+    const size_t o = ((size_t)b * T + t) * cd + d;
+    const float m_in = mean_in[o], s_in = std_in[o];
+    if (kp == 0) {
+      mean_out[o] = m_in;
+      std_out[o] = s_in;
+      continue;
+    }
+    const float* src = cand + (size_t)t * step + (size_t)b * cd + d;    // + n * B * cd per candidate
+    double sum = 0.0;
+    for (int n = 0; n < N; ++n)
+      if (flag_s[n]) sum += (double)src[(size_t)n * B * cd];
+    const double m = sum / inv;
+    double acc = 0.0;
+    for (int n = 0; n < N; ++n)
+      if (flag_s[n]) acc = add_square(acc, (double)src[(size_t)n * B * cd], m);
+    const double s = sqrt(acc / inv);
+    mean_out[o] = (float)blend(a, (double)m_in, m);
+    std_out[o] = fmaxf((float)blend(a, (double)s_in, s), std_min);
+  }
+}
+
 bool ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
   return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
@@ -723,5 +859,51 @@ extern "C" int mmdyn_gather_best_steps(const mmdyn_gather_groups* groups, int G,
   }
   const int blocks = split_blocks(work, G, a.first_block);
   hipLaunchKernelGGL(gather_best_steps_kernel, dim3(blocks), dim3(256), 0, ST, a, best, G, N, T);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_plan_sample(const float* mean, const float* std, const float* eps, const float* keep, const float* lo,
+                                 const float* hi, float* cand, int N, int B, int T, int cd, void* stream) {
+  if (!mean || !std || !eps || !cand || (lo == nullptr) != (hi == nullptr)) return MMDYN_ERR_NULL;
+  if (N < 1 || B < 1 || T < 1 || cd < 1) return MMDYN_ERR_SHAPE;
+  const int64_t n = (int64_t)N * B * T * cd, row = (int64_t)B * T * cd;
+  if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  // the candidates are written while other threads read every input: no aliasing
+  const struct { const void* p; int64_t bytes; } in[6] = {{mean, row * 4}, {std, row * 4}, {eps, n * 4}, {keep, row * 4},
+                                                          {lo, (int64_t)cd * 4}, {hi, (int64_t)cd * 4}};
+  for (int i = 0; i < 6; ++i)
+    if (in[i].p && ranges_overlap(cand, n * 4, in[i].p, in[i].bytes)) return MMDYN_ERR_SHAPE;
+  const uintptr_t ptrs = (uintptr_t)mean | (uintptr_t)std | (uintptr_t)eps | (uintptr_t)keep | (uintptr_t)lo | (uintptr_t)hi |
+                         (uintptr_t)cand;
+  if ((ptrs & 15) == 0 && cd % 4 == 0)
+    hipLaunchKernelGGL(plan_sample_kernel<4>, dim3(ew_grid(n / 4)), dim3(256), 0, ST, mean, std, eps, keep, lo, hi, cand, N, B, T, cd,
+                       n / 4);
+  else
+    hipLaunchKernelGGL(plan_sample_kernel<1>, dim3(ew_grid(n)), dim3(256), 0, ST, mean, std, eps, keep, lo, hi, cand, N, B, T, cd, n);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_plan_refit(const float* cost, const float* cand, const float* mean_in, const float* std_in, float* mean_out,
+                                float* std_out, uint8_t* elite, int* count, int K, int N, int B, int T, int cd, float alpha,
+                                float std_min, void* stream) {
+  if (!cost || !cand || !mean_in || !std_in || !mean_out || !std_out) return MMDYN_ERR_NULL;
+  if (B < 1 || T < 1 || cd < 1 || N < 1 || N > MMDYN_REFIT_N_MAX || K < 1 || K > N) return MMDYN_ERR_SHAPE;
+  if (!(alpha >= 0.f && alpha < 1.f) || !(std_min >= 0.f)) return MMDYN_ERR_SHAPE;
+  const int64_t n = (int64_t)N * B * T * cd, row = (int64_t)B * T * cd, nb = (int64_t)N * B;
+  if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  // an output may be exactly its own input (an element is read and written by one thread); every other overlap is refused
+  struct Range { const void* p; int64_t bytes; };
+  const Range in[4] = {{cost, nb * 4}, {cand, n * 4}, {mean_in, row * 4}, {std_in, row * 4}};
+  const Range outs[4] = {{mean_out, row * 4}, {std_out, row * 4}, {elite, nb}, {count, (int64_t)B * 4}};
+  for (int i = 0; i < 4; ++i) {
+    if (!outs[i].p) continue;
+    for (int j = 0; j < 4; ++j)
+      if (!(i < 2 && j == i + 2 && outs[i].p == in[j].p) && ranges_overlap(outs[i].p, outs[i].bytes, in[j].p, in[j].bytes))
+        return MMDYN_ERR_SHAPE;
+    for (int j = i + 1; j < 4; ++j)
+      if (outs[j].p && ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return MMDYN_ERR_SHAPE;
+  }
+  hipLaunchKernelGGL(plan_refit_kernel, dim3(B), dim3(256), 0, ST, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, K, N,
+                     B, T, cd, alpha, std_min);
   MMDYN_LAUNCH_CHECK();
 }

@@ -161,6 +161,8 @@ _SIGNATURES = {
     "mmdyn_ensemble_feed": "p" + "i" + "p" + "ii" + "p",
     "mmdyn_plan_select_steps": "ppppppp" + "i" + "pppppppp" + "iiiii" + "ff" + "pp",
     "mmdyn_gather_best_steps": "p" + "i" + "p" + "iii" + "p",
+    "mmdyn_plan_sample": "ppppppp" + "iiii" + "p",
+    "mmdyn_plan_refit": "pppppppp" + "iiiii" + "ff" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

@@ -1344,7 +1344,9 @@ class MVAEInference:
     class indices; its one-hot rows are written by the join kernel.  :meth:`bad_condition` reports an index out of range.
     :meth:`plan` asks the inverse question: N candidate conditions per row are scored against a goal state and the best one is
     picked on the device, in one graph whose launch count does not grow with N (up to 8 candidates); :meth:`plan_rollout` asks it
-    over a horizon: N candidate condition sequences are rolled out T steps, and the best one comes back with its trajectory."""
+    over a horizon: N candidate condition sequences are rolled out T steps, and the best one comes back with its trajectory;
+    :meth:`plan_refine` makes and refines those sequences itself: the cross-entropy method, I iterations of draw / roll out / refit in
+    one graph (real-valued conditions)."""
 
     def __init__(self, model, precision="fp32x3", use_graph=True, seed=0):
         from .models.vae import NoiseSource
@@ -1453,10 +1455,49 @@ class MVAEInference:
         synchronisation, which :meth:`forward` / :meth:`score` / :meth:`inference` do not make on their own."""
         return bool(self._bad is not None and int(self._bad.item()))
 
-    def _encode(self, key, x, cond=None, x_rows=None):
-        h, _ = layers.run(layers.encoder_trunk_forward_steps(self.P[key], self.buf[key], x, packed=self.pk[key],
-                                                             training=False))
+    def _trunk(self, key, x):
+        """The image encoder's trunk: x -> the 512 features in front of its heads."""
+        return layers.run(layers.encoder_trunk_forward_steps(self.P[key], self.buf[key], x, packed=self.pk[key], training=False))[0]
+
+    def _image_heads(self, key, h, cond=None, x_rows=None):
+        """The image encoder's fused heads on the trunk's features (joined to the condition in front of them)."""
         return layers.heads_forward(self.P[key], h, self.pk[key[0] + "h"], cond=cond, x_rows=x_rows)[0]
+
+    def _encode(self, key, x, cond=None, x_rows=None):
+        return self._image_heads(key, self._trunk(key, x), cond, x_rows)
+
+    def _trunks(self, visual, tactile, pose):
+        """The part of :meth:`_heads` that does not see the condition, for a request that runs the heads more than once: [visual
+        features | None, tactile features | None, pose heads [B][2L] | None]."""
+        LN = self.lanes
+        out = [None, None, None]
+        LN.fork()
+        if visual is not None:
+            with LN.lane(0):
+                out[0] = self._trunk("ve", visual)
+        if tactile is not None:
+            with LN.lane(1):
+                out[1] = self._trunk("te", tactile)
+        if pose is not None and self.use_pose:
+            hp, _ = layers.pose_encoder_trunk_forward(self.P["pe"], pose)
+            out[2] = layers.heads_forward(self.P["pe"], hp, self.pk["ph"])[0]
+        LN.join()
+        return out
+
+    def _heads_of(self, trunks, cond, x_rows=None):
+        """The image heads on stored trunk outputs (:meth:`_trunks`): the heads of :meth:`_heads`, launch for launch from the
+        join on; the pose entry is handed through."""
+        LN = self.lanes
+        heads = [None, None, trunks[2]]
+        LN.fork()
+        if trunks[0] is not None:
+            with LN.lane(0):
+                heads[0] = self._image_heads("ve", trunks[0], cond, x_rows)
+        if trunks[1] is not None:
+            with LN.lane(1):
+                heads[1] = self._image_heads("te", trunks[1], cond, x_rows)
+        LN.join()
+        return heads
 
     @staticmethod
     def _rows_of(visual, tactile, pose, avail):
@@ -2000,6 +2041,34 @@ class MVAEInference:
             raise ValueError("plan_rollout needs at least one candidate condition sequence (N >= 1)")
         return rows.contiguous(), N, per_row
 
+    def _candidate_steps_forward(self, N, T, Tg, sample, B, dev, step0_heads, cand, avail_rows, gv, gt, gp, traj, means, log_var, tab):
+        """The step loop of the horizon planner on the N * B (candidate, row) rows, shared by :meth:`_plan_rollout` and
+        :meth:`_plan_refine`: step 0's heads come from ``step0_heads(cand[0])`` (the trunks on the B rows, the image heads through the
+        tiled join), every later step is the joint forward of the N * B state rows with the step's slice of ``cand``; PoE writes
+        slot t of ``means`` / ``log_var``, ONE rollout_feed slot t of the ``traj`` tensors, a scored step adds the row kernels and
+        kl_rows into ``tab`` (fp64 [4][Tg][N][B], cleared by the caller).  ``avail_rows``: the request's table on the N * B rows."""
+        feed = ops.backend_op("rollout_feed")
+        NB, L, kl = N * B, self.L, tab[3]
+        step_of = lambda t, i: None if t is None else t[i]
+        state = None
+        for i in range(T):
+            c_i = cand[i]
+            heads = step0_heads(c_i) if i == 0 else self._heads(state[0], state[1], state[2], c_i)
+            # one draw per row and step, shared by the row's candidates
+            eps = (self._draw_latent(B) if sample else self._zero_latent(B)).repeat(N, 1)
+            mu, lv, z = self._poe(heads, avail_rows if i == 0 else None, eps, NB, dev, out=(means[i], log_var[i]))
+            v, t, pr = self._decode(z, c_i)
+            if Tg == T or i == T - 1:
+                s = i if Tg == T else 0
+                self._row_terms(N, B, v, t, pr, step_of(gv, s), step_of(gt, s), step_of(gp, s), None, (tab[0, s], tab[1, s], tab[2, s]))
+                ops.B.kl_rows(mu, lv, kl[s].view(1, NB), 1, NB, L)
+            groups = [{"recon": v, "obs": None, "out": traj[0][i], "logits": True, "column": 0},
+                      {"recon": t, "obs": None, "out": traj[1][i], "logits": True, "column": 1}]
+            if self.use_pose:
+                groups.append({"recon": pr, "obs": None, "out": traj[2][i], "logits": False, "column": 2})
+            feed(groups, None, NB)
+            state = [traj[0][i], traj[1][i], traj[2][i] if self.use_pose else None]
+
     def _plan_rollout(self, N, T, Tg, sample, top, visual, tactile, pose, gv, gt, gp, cand, avail, tavail, weight):
         """N candidate condition sequences per row rolled out open loop over T steps on the N * B (candidate, row) rows.  Step 0 is
         the front half of :meth:`_plan_candidates` (the trunks and the pose heads ONCE on the B rows, the image heads through the
@@ -2008,7 +2077,8 @@ class MVAEInference:
         next step reads.  A scored step (the last one for a final goal, Tg = 1; every one for Tg = T) adds the row kernels with G = N
         passes against its one goal and kl_rows; tables fp64 [4][Tg][N][B] = (visual, tactile, pose, KL), cleared by one fill.  One
         plan_select_steps and one gather_best_steps launch close the request."""
-        select, gather, feed = (ops.backend_op(k) for k in ("plan_select_steps", "gather_best_steps", "rollout_feed"))
+        select, gather = ops.backend_op("plan_select_steps"), ops.backend_op("gather_best_steps")
+        ops.backend_op("rollout_feed")
         ops.backend_op("concat_condition_tiled")        # (a backend without the join: an error before anything is launched)
         (B, dev), L, S = self._rows_of(visual, tactile, pose, avail), self.L, self.model.visual_decoder.image_size
         NB = N * B
@@ -2017,32 +2087,15 @@ class MVAEInference:
         means, log_var = torch.empty(T, NB, L, device=dev), torch.empty(T, NB, L, device=dev)
         tab = torch.zeros(4, Tg, N, B, dtype=torch.float64, device=dev)
         kl = tab[3]
-        step_of = lambda t, i: None if t is None else t[i]
-        state = [visual, tactile, pose]
+
+        def step0(c_0):
+            heads = self._heads(visual, tactile, pose, c_0, x_rows=B)
+            if heads[2] is not None:
+                heads[2] = heads[2].repeat(N, 1)
+            return heads
         with self._index_scope():
-            for i in range(T):
-                c_i = cand[i]
-                if i == 0:
-                    heads = self._heads(state[0], state[1], state[2], c_i, x_rows=B)
-                    if heads[2] is not None:
-                        heads[2] = heads[2].repeat(N, 1)
-                else:
-                    heads = self._heads(state[0], state[1], state[2], c_i)
-                # one draw per row and step, shared by the row's candidates
-                eps = (self._draw_latent(B) if sample else self._zero_latent(B)).repeat(N, 1)
-                mu, lv, z = self._poe(heads, avail.repeat(N, 1) if i == 0 and avail is not None else None, eps, NB, dev,
-                                      out=(means[i], log_var[i]))
-                v, t, pr = self._decode(z, c_i)
-                if Tg == T or i == T - 1:
-                    s = i if Tg == T else 0
-                    self._row_terms(N, B, v, t, pr, step_of(gv, s), step_of(gt, s), step_of(gp, s), None, (tab[0, s], tab[1, s], tab[2, s]))
-                    ops.B.kl_rows(mu, lv, kl[s].view(1, NB), 1, NB, L)
-                groups = [{"recon": v, "obs": None, "out": traj[0][i], "logits": True, "column": 0},
-                          {"recon": t, "obs": None, "out": traj[1][i], "logits": True, "column": 1}]
-                if self.use_pose:
-                    groups.append({"recon": pr, "obs": None, "out": traj[2][i], "logits": False, "column": 2})
-                feed(groups, None, NB)
-                state = [traj[0][i], traj[1][i], traj[2][i] if self.use_pose else None]
+            self._candidate_steps_forward(N, T, Tg, sample, B, dev, step0, cand, None if avail is None else avail.repeat(N, 1),
+                                          gv, gt, gp, traj, means, log_var, tab)
         cost, step_cost = torch.empty(N, B, device=dev), torch.empty(Tg, N, B, device=dev)
         best, best_cost = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev)
         best_cond = torch.empty((B, T) + tuple(cand.shape[2:]), dtype=cand.dtype, device=dev)
@@ -2061,6 +2114,42 @@ class MVAEInference:
         if top is not None:
             res.update(top=top_idx, top_cost=top_cost)
         return res
+
+    def _horizon_goal(self, who, goal, goal_available, step_weight, T, B):
+        """The goal of a horizon request: (the three goal tensors as fp32 [Tg, B, ...] / None, the goal-availability tables uint8
+        [Tg][B][4] / None, the step weights fp32 [Tg] on the device / None, Tg); ValueError for what :meth:`plan_rollout` refuses."""
+        if not isinstance(goal, (list, tuple)) or len(goal) > 3:
+            raise ValueError("goal must be a list [visual | None, tactile | None, pose | None]")
+        goal = (list(goal) + [None] * 3)[:3]
+        if not self.use_pose:
+            goal[2] = None
+        given = [(i, t) for i, t in enumerate(goal) if t is not None]
+        if not given:
+            raise ValueError(f"{who} needs a goal: at least one of [visual, tactile, pose]")
+        if not all(torch.is_tensor(t) for _, t in given):
+            raise ValueError("goal must hold tensors")
+        # an image [B, 3, S, S] / a pose [B, 7] is a final goal, one more leading dimension a goal per step
+        forms = {t.dim() - (4 if i < 2 else 2) for i, t in given}
+        if not forms <= {0, 1}:
+            raise ValueError("goal tensors are [B, ...] (a final goal) or [T, B, ...] (one per step)")
+        if len(forms) > 1:
+            raise ValueError("goal mixes the two forms: every tensor is [B, ...] (a final goal) or every one [T, B, ...] (one per step)")
+        Tg = 1 if forms == {0} else T
+        if forms == {0}:
+            tg = [None if t is None else t.to(device=self.dev, dtype=torch.float32).unsqueeze(0)
+                  for t in self._targets("goal", goal, B)]
+            tavail = self._availability(goal_available, B)
+            tavail = None if tavail is None else tavail.view(1, B, -1)
+        else:
+            tg = self._step_tensors("goal", goal, T, B)
+            tavail = self._step_availability("goal_available", goal_available, T, B)
+        weight = None
+        if step_weight is not None:
+            if not torch.is_tensor(step_weight) or not step_weight.dtype.is_floating_point or tuple(step_weight.shape) != (Tg,):
+                raise ValueError(f"step_weight must be a floating-point tensor [Tg={Tg}] (one weight per scored step), got "
+                                 f"{tuple(step_weight.shape) if torch.is_tensor(step_weight) else type(step_weight).__name__}")
+            weight = step_weight.detach().to(device=self.dev, dtype=torch.float32).contiguous()
+        return tg, tavail, weight, Tg
 
     @torch.no_grad()
     def plan_rollout(self, x, pose=None, steps=1, goal=None, candidates=None, step_weight=None, top=None, kl_weight=0.0,
@@ -2111,37 +2200,7 @@ class MVAEInference:
             if isinstance(top, bool) or not isinstance(top, numbers.Integral) or not 1 <= top <= ops.PLAN_TOP_MAX:
                 raise ValueError(f"top must be an integer in [1, {ops.PLAN_TOP_MAX}] (the best candidates listed per row), got {top!r}")
             top = int(top)
-        if not isinstance(goal, (list, tuple)) or len(goal) > 3:
-            raise ValueError("goal must be a list [visual | None, tactile | None, pose | None]")
-        goal = (list(goal) + [None] * 3)[:3]
-        if not self.use_pose:
-            goal[2] = None
-        given = [(i, t) for i, t in enumerate(goal) if t is not None]
-        if not given:
-            raise ValueError("plan_rollout needs a goal: at least one of [visual, tactile, pose]")
-        if not all(torch.is_tensor(t) for _, t in given):
-            raise ValueError("goal must hold tensors")
-        # an image [B, 3, S, S] / a pose [B, 7] is a final goal, one more leading dimension a goal per step
-        forms = {t.dim() - (4 if i < 2 else 2) for i, t in given}
-        if not forms <= {0, 1}:
-            raise ValueError("goal tensors are [B, ...] (a final goal) or [T, B, ...] (one per step)")
-        if len(forms) > 1:
-            raise ValueError("goal mixes the two forms: every tensor is [B, ...] (a final goal) or every one [T, B, ...] (one per step)")
-        Tg = 1 if forms == {0} else T
-        if forms == {0}:
-            tg = [None if t is None else t.to(device=self.dev, dtype=torch.float32).unsqueeze(0)
-                  for t in self._targets("goal", goal, B)]
-            tavail = self._availability(goal_available, B)
-            tavail = None if tavail is None else tavail.view(1, B, -1)
-        else:
-            tg = self._step_tensors("goal", goal, T, B)
-            tavail = self._step_availability("goal_available", goal_available, T, B)
-        weight = None
-        if step_weight is not None:
-            if not torch.is_tensor(step_weight) or not step_weight.dtype.is_floating_point or tuple(step_weight.shape) != (Tg,):
-                raise ValueError(f"step_weight must be a floating-point tensor [Tg={Tg}] (one weight per scored step), got "
-                                 f"{tuple(step_weight.shape) if torch.is_tensor(step_weight) else type(step_weight).__name__}")
-            weight = step_weight.detach().to(device=self.dev, dtype=torch.float32).contiguous()
+        tg, tavail, weight, Tg = self._horizon_goal("plan_rollout", goal, goal_available, step_weight, T, B)
         self._set_weights(kl_weight, pose_multiplier)
         sample = bool(sample)
         avail = self._availability(available, B)
@@ -2149,6 +2208,134 @@ class MVAEInference:
         key = ("plan_rollout", T, Tg, top, sample, self._pose_multiplier, "index" if self.categorical else "real",
                ("candidates", N, per_row)) + self._shapes(ins + tg + [weight]) + self._shapes((avail, tavail), "avail")
         return self._run(key, lambda *a: self._plan_rollout(N, T, Tg, sample, top, *a), args)
+
+    def _plan_refine(self, N, K, I, T, Tg, sample, alpha, std_min, visual, tactile, pose, gv, gt, gp, init_mean, init_std, lo, hi,
+                     avail, tavail, weight):
+        """The cross-entropy method on the horizon planner, I iterations in one captured region.  Once per request: the trunks and
+        the pose heads on the B rows (:meth:`_trunks`).  Per iteration: one [N][B][T][cd] draw and its commit, one plan_sample (slot
+        0 = the previous iteration's winner), one fill of the tables, the steps of :meth:`_plan_rollout` from the image heads on,
+        one plan_select_steps and one plan_refit (in place from the second iteration on).  Every buffer is allocated once; the
+        winner's cost and the elite count of iteration i are written straight into row i of ``history`` / ``elite_count``.  One
+        gather_best_steps on the last iteration's trajectories closes the request."""
+        select, gather, sample_op, refit = (ops.backend_op(k) for k in ("plan_select_steps", "gather_best_steps", "plan_sample", "plan_refit"))
+        ops.backend_op("rollout_feed")
+        ops.backend_op("concat_condition_tiled")        # (a backend without the join: an error before anything is launched)
+        (B, dev), L, S, cd = self._rows_of(visual, tactile, pose, avail), self.L, self.model.visual_decoder.image_size, self.condition_dim
+        NB = N * B
+        traj = [torch.empty(T, NB, 3, S, S, device=dev), torch.empty(T, NB, 3, S, S, device=dev),
+                torch.empty(T, NB, 7, device=dev) if self.use_pose else None]
+        means, log_var = torch.empty(T, NB, L, device=dev), torch.empty(T, NB, L, device=dev)
+        tab = torch.empty(4, Tg, N, B, dtype=torch.float64, device=dev)
+        kl = tab[3]
+        cand = torch.empty(T, NB, cd, device=dev)
+        mean, std = torch.empty(B, T, cd, device=dev), torch.empty(B, T, cd, device=dev)
+        cost, step_cost = torch.empty(N, B, device=dev), torch.empty(Tg, N, B, device=dev)
+        best, best_cond = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, T, cd, device=dev)
+        history, count = torch.empty(I, B, device=dev), torch.empty(I, B, dtype=torch.int32, device=dev)
+        avail_rows = None if avail is None else avail.repeat(N, 1)
+        with self._index_scope():
+            trunks = self._trunks(visual, tactile, pose)
+            if trunks[2] is not None:
+                trunks[2] = trunks[2].repeat(N, 1)                    # the pose heads see no condition: their N * B rows once
+            step0 = lambda c_0: self._heads_of(trunks, c_0, x_rows=B)
+            for i in range(I):
+                eps = self.noise.eps((N, B, T, cd), dev)
+                self.noise.commit()
+                m_in, s_in = (init_mean, init_std) if i == 0 else (mean, std)
+                sample_op(m_in, s_in, eps, None if i == 0 else best_cond, lo, hi, cand, N, B, T)
+                tab.zero_()
+                self._candidate_steps_forward(N, T, Tg, sample, B, dev, step0, cand, avail_rows, gv, gt, gp, traj, means, log_var, tab)
+                select(tab[:2] if gv is not None or gt is not None else None, tab[2] if gp is not None else None, kl, tavail, weight,
+                       cand, cost, step_cost, best, history[i], best_cond, None, None, N, B, T, Tg, self._pose_multiplier, 1.0, self._klw)
+                refit(cost, cand, m_in, s_in, mean, std, None, count[i], K, N, B, T, alpha, std_min)
+        outs = [{"src": x, "out": torch.empty((T, B) + tuple(x.shape[2:]), device=dev), "logits": False} for x in traj if x is not None]
+        gather(outs, best, N, B, T)
+        split = lambda x: None if x is None else x.view((T, N, B) + tuple(x.shape[2:]))
+        return {"cost": cost, "step_cost": step_cost, "best": best, "best_cost": history[I - 1], "best_condition": best_cond,
+                "trajectory": [g["out"] for g in outs] + ([] if self.use_pose else [None]),
+                "visual": split(traj[0]), "tactile": split(traj[1]), "pose": split(traj[2]),
+                **self._terms(tab[:3], (gv, gt, gp)), "kl": kl, "means": split(means), "log_var": split(log_var),
+                "mean": mean, "std": std, "candidates": split(cand), "history": history, "elite_count": count}
+
+    @torch.no_grad()
+    def plan_refine(self, x, pose=None, steps=1, goal=None, init_mean=None, init_std=None, candidates=64, elites=8, iterations=4,
+                    alpha=0.0, std_min=0.0, bounds=None, step_weight=None, kl_weight=0.0, pose_multiplier=1000.0, available=None,
+                    goal_available=None, sample=False):
+        """:meth:`plan_rollout` with the candidates made and refined on the device: the cross-entropy method (CEM) over a horizon,
+        for models with real-valued conditions.  A distribution N(mean, std^2) over condition sequences [T, condition_dim] per row
+        starts at ``init_mean`` / ``init_std``; each of ``iterations`` = I rounds draws ``candidates`` = N sequences per row from
+        it (slot 0 is the incumbent: the mean in round 0, the previous round's winner afterwards, so the best cost never gets worse
+        beyond rounding), rolls them out over ``steps`` = T applications of the model exactly as :meth:`plan_rollout` does, scores
+        them against the goal, and refits mean and std to the ``elites`` = K cheapest of each row:
+        mean <- alpha * mean + (1 - alpha) * elite mean, std <- max(alpha * std + (1 - alpha) * elite std, std_min), the population
+        standard deviation, in fp64.  ONE captured graph for all I rounds: the encoder trunks and the pose heads run once per
+        request, nothing synchronises, and N may reach MMDYN_REFIT_N_MAX = 4096 with any K <= N.
+
+        ``init_mean`` / ``init_std`` (required): floating point, [T, condition_dim] (shared by every row) or [B, T,
+        condition_dim].  ``bounds`` = (lo, hi), floating point [condition_dim] each, or None: every candidate is clamped to them.
+        ``goal`` / ``goal_available`` / ``step_weight`` / ``available`` / ``sample`` / the weights: as in :meth:`plan_rollout`
+        (``sample=True``: one [B, L] draw per step and round, shared by a row's candidates).  All tensors are static inputs of the
+        graph: its key carries I, N, K, T, the goal's form, ``sample``, ``alpha``, ``std_min``, the pose multiplier, whether
+        bounds are given and the shapes -- never values.
+
+        The Philox stream: round i draws its [N, B, T, cd] candidate block first, then (``sample=True``) the T latent blocks of its
+        steps.  With n_c = ceil(N B T cd / 4), n_l = ceil(B L / 4) and per = n_c + (T n_l if sample else 0), round i of eager call c
+        (on an engine that served nothing else) draws its candidates at counter (c I + i) per and the latent block of step t at
+        (c I + i) per + n_c + t n_l.  The draw of slot 0 is taken and not used.
+
+        Returns a dict of the graph's static outputs (copy what must survive the next call of the same shapes): everything
+        :meth:`plan_rollout` returns (without ``top``), for the LAST round; ``mean`` / ``std`` fp32 [B, T, condition_dim], after the
+        last refit; ``candidates`` fp32 [T, N, B, condition_dim], the last round's candidates; ``history`` fp32 [I, B], each round's
+        best cost; ``elite_count`` int32 [I, B], the elites each refit found (< K when fewer costs were no NaN; 0 leaves the
+        distribution as it was).  ValueError: what :meth:`plan_rollout` refuses, a categorical or unconditional model, N outside
+        [1, 4096], K outside [1, N], I < 1, ``alpha`` outside [0, 1), ``std_min`` < 0, wrong shapes or dtypes of ``init_mean`` /
+        ``init_std`` / ``bounds``.  Out of scope: MPPI weights, categorical distributions, a receding-horizon shift helper,
+        observations inside a plan, ``loss_mask``."""
+        if not self.conditional:
+            raise ValueError("plan_refine refits a distribution over conditions: it was asked of an unconditional model")
+        if self.categorical:
+            raise ValueError("plan_refine serves real-valued conditions; a distribution over the classes of a categorical model is out of scope")
+        T = self._count("steps", steps, "model applications")
+        N = self._count("candidates", candidates, "condition sequences drawn per row and iteration")
+        K = self._count("elites", elites, "candidates each refit keeps")
+        I = self._count("iterations", iterations, "refinement rounds")
+        if N > ops.REFIT_N_MAX:
+            raise ValueError(f"candidates = {N} is more than the refit ranks per row (MMDYN_REFIT_N_MAX = {ops.REFIT_N_MAX})")
+        if K > N:
+            raise ValueError(f"elites = {K} must lie in [1, candidates = {N}]")
+        for name, v, ok in (("alpha", alpha, lambda a: 0.0 <= a < 1.0), ("std_min", std_min, lambda a: a >= 0.0)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not ok(float(v)):
+                raise ValueError(f"{name} must be a number in {'[0, 1)' if name == 'alpha' else '[0, inf)'}, got {v!r}")
+        # (as the kernel sees them: fp32)
+        alpha, std_min = float(torch.tensor(float(alpha), dtype=torch.float32)), float(torch.tensor(float(std_min), dtype=torch.float32))
+        if not alpha < 1.0:
+            raise ValueError("alpha rounds to 1.0 in fp32: it must lie in [0, 1)")
+        ins, B = self._request("plan_refine", x, pose, available, cast=True)
+        S, cd = self.model.visual_decoder.image_size, self.condition_dim
+        most = min(((1 << 31) - 1) // (T * B * 3 * S * S), ((1 << 31) - 1) // (B * self._decoder_row()))
+        if N > most:
+            raise ValueError(f"candidates = {N} condition sequences of B = {B} rows over steps = {T} make a trajectory tensor or a "
+                             f"decoder activation of 2^31 elements or more; the largest N for B = {B} and steps = {T} is {most}")
+        dist = []
+        for name, t in (("init_mean", init_mean), ("init_std", init_std)):
+            if not torch.is_tensor(t) or not t.dtype.is_floating_point or tuple(t.shape) not in ((T, cd), (B, T, cd)):
+                raise ValueError(f"{name} must be a floating-point tensor [T={T}, {cd}] (shared) or [B={B}, T={T}, {cd}] (per row), got "
+                                 f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+            dist.append(t.detach().to(device=self.dev, dtype=torch.float32).expand(B, T, cd).contiguous())
+        lo = hi = None
+        if bounds is not None:
+            if not isinstance(bounds, (list, tuple)) or len(bounds) != 2 or not all(
+                    torch.is_tensor(t) and t.dtype.is_floating_point and tuple(t.shape) == (cd,) for t in bounds):
+                raise ValueError(f"bounds must be a pair (lo, hi) of floating-point tensors [{cd}] or None")
+            lo, hi = (t.detach().to(device=self.dev, dtype=torch.float32).contiguous() for t in bounds)
+        tg, tavail, weight, Tg = self._horizon_goal("plan_refine", goal, goal_available, step_weight, T, B)
+        self._set_weights(kl_weight, pose_multiplier)
+        sample = bool(sample)
+        avail = self._availability(available, B)
+        args = ins + tg + dist + [lo, hi, avail, tavail, weight]
+        key = ("plan_refine", I, N, K, T, Tg, sample, alpha, std_min, self._pose_multiplier, bounds is not None) + \
+            self._shapes(ins + tg + dist + [weight]) + self._shapes((avail, tavail), "avail")
+        return self._run(key, lambda *a: self._plan_refine(N, K, I, T, Tg, sample, alpha, std_min, *a), args)
 
     def _rollout(self, T, sample, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
         """T forwards in a row, each followed by ONE feed launch that writes the next state into its trajectory slot, where the

@@ -21,6 +21,7 @@ ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
 DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0 = 0, 1, 2, 3, 4
 ROW_GROUPS_MAX = 8         # MMDYN_BCE_GROUPS_MAX: the passes one launch of a *_groups kernel walks over its target
 PLAN_TOP_MAX = 8           # MMDYN_PLAN_TOP_MAX: the longest list of best candidates mmdyn_plan_select_steps keeps per row
+REFIT_N_MAX = 4096         # MMDYN_REFIT_N_MAX: the candidates per row whose cost column mmdyn_plan_refit ranks in LDS
 
 
 def _ptr(t, dtype=torch.float32):
@@ -1181,6 +1182,82 @@ class HipBackend:
         check(self.lib.mmdyn_gather_best_steps(ctypes.addressof(arg), len(groups), _ptr(best, torch.int32), N, B, T, _stream()),
               "mmdyn_gather_best_steps")
 
+    # ---- iterative refinement (CEM): the candidates of an iteration, the elites and the refitted distribution ----
+    @staticmethod
+    def _touch(a, b):
+        """Whether the storage ranges of two tensors (None: no) intersect."""
+        if a is None or b is None:
+            return False
+        pa, pb = a.data_ptr(), b.data_ptr()
+        return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+    def plan_sample(self, mean, std, eps, keep, lo, hi, cand, N, B, T):
+        """cand [T][N * B][cd] fp32 = the candidates of one refinement iteration: row n * B + b of step t is mean[b][t] + std[b][t] *
+        eps[n][b][t] (product and sum each rounded to fp32), slot n = 0 the incumbent -- keep[b][t] where it is given and no NaN,
+        mean[b][t] otherwise; its eps is not read --, everything clamped to [lo, hi] per dimension where the bounds are given (a NaN
+        stays a NaN).  mean / std / keep: fp32 [B][T][cd]; eps: fp32 [N][B][T][cd]; lo / hi: fp32 [cd], both or neither.  cand
+        overlaps no input."""
+        name, N, B, T = "plan_sample", int(N), int(B), int(T)
+        if N < 1 or B < 1 or T < 1:
+            raise ValueError(f"mmdyn_plan_sample: N = {N}, B = {B} and T = {T} must be positive")
+        if any(t is None for t in (mean, std, eps, cand)):
+            raise ValueError("mmdyn_plan_sample: mean, std, eps and cand are required")
+        if (lo is None) != (hi is None):
+            raise ValueError("mmdyn_plan_sample: lo and hi come together")
+        if not torch.is_tensor(mean) or mean.dim() != 3 or mean.shape[2] < 1:
+            raise ValueError(f"mmdyn_plan_sample: mean must be fp32 [B = {B}][T = {T}][cd], got "
+                             f"{tuple(mean.shape) if torch.is_tensor(mean) else type(mean).__name__}")
+        cd = mean.shape[2]
+        if N * B * T * cd >= 1 << 31:
+            raise ValueError(f"mmdyn_plan_sample: N * B * T * cd = {N * B * T * cd} elements reach 2^31")
+        f32 = torch.float32
+        specs = ((mean, (B, T, cd), "mean", f32), (std, (B, T, cd), "std", f32), (eps, (N, B, T, cd), "eps", f32),
+                 (keep, (B, T, cd), "keep", f32), (lo, (cd,), "lo", f32), (hi, (cd,), "hi", f32), (cand, (T, N * B, cd), "cand", f32))
+        self._check_tables(name, *specs)
+        for t, _, what, _ in specs[:-1]:
+            if self._touch(cand, t):
+                raise ValueError(f"mmdyn_plan_sample: cand overlaps {what}")
+        ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
+        check(self.lib.mmdyn_plan_sample(*ptrs, N, B, T, cd, _stream()), "mmdyn_plan_sample")
+
+    def plan_refit(self, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, K, N, B, T, alpha=0.0, std_min=0.0):
+        """The elites of every row and the distribution refitted to them.  cost: fp32 [N][B] (plan_select_steps); cand: fp32
+        [T][N * B][cd]; candidate n is an elite of row b iff cost[n][b] is no NaN and fewer than K candidates come in front of it (a
+        smaller cost, or an equal one with a lower n).  Over the K' elites in ascending n, in fp64, each operation rounded on its
+        own: m = sum c / K', s = sqrt(sum (c - m)^2 / K'); mean_out = fp32(alpha * mean_in + (1 - alpha) * m), std_out =
+        fmax(fp32(alpha * std_in + (1 - alpha) * s), std_min); K' = 0: the inputs, bit for bit.  mean_* / std_*: fp32 [B][T][cd],
+        an output may be exactly its input and overlaps nothing else; elite: uint8 [N][B] or None; count: int32 [B] or None."""
+        name, K, N, B, T = "plan_refit", int(K), int(N), int(B), int(T)
+        alpha, std_min = float(alpha), float(std_min)
+        if B < 1 or T < 1 or not 1 <= N <= REFIT_N_MAX or not 1 <= K <= N:
+            raise ValueError(f"mmdyn_plan_refit: B = {B} and T = {T} must be positive, N = {N} lie in [1, {REFIT_N_MAX}] and K = {K} in [1, N]")
+        if not 0.0 <= alpha < 1.0 or not std_min >= 0.0:
+            raise ValueError(f"mmdyn_plan_refit: alpha = {alpha} must lie in [0, 1) and std_min = {std_min} be >= 0")
+        if any(t is None for t in (cost, cand, mean_in, std_in, mean_out, std_out)):
+            raise ValueError("mmdyn_plan_refit: cost, cand, mean_in, std_in, mean_out and std_out are required")
+        if not torch.is_tensor(cand) or cand.dim() != 3 or cand.shape[2] < 1:
+            raise ValueError(f"mmdyn_plan_refit: cand must be fp32 [T = {T}][N * B = {N * B}][cd], got "
+                             f"{tuple(cand.shape) if torch.is_tensor(cand) else type(cand).__name__}")
+        cd = cand.shape[2]
+        if N * B * T * cd >= 1 << 31:
+            raise ValueError(f"mmdyn_plan_refit: N * B * T * cd = {N * B * T * cd} elements reach 2^31")
+        f32 = torch.float32
+        specs = ((cost, (N, B), "cost", f32), (cand, (T, N * B, cd), "cand", f32), (mean_in, (B, T, cd), "mean_in", f32),
+                 (std_in, (B, T, cd), "std_in", f32), (mean_out, (B, T, cd), "mean_out", f32), (std_out, (B, T, cd), "std_out", f32),
+                 (elite, (N, B), "elite", torch.uint8), (count, (B,), "count", torch.int32))
+        self._check_tables(name, *specs)
+        ins, outs = specs[:4], specs[4:]
+        for i, (o, _, what, _) in enumerate(outs):
+            for j, (t, _, other, _) in enumerate(ins):
+                own = i < 2 and j == i + 2 and o.data_ptr() == t.data_ptr()
+                if not own and self._touch(o, t):
+                    raise ValueError(f"mmdyn_plan_refit: {what} overlaps {other} (an output may only be exactly its own input)")
+            for p, _, other, _ in outs[i + 1:]:
+                if self._touch(o, p):
+                    raise ValueError(f"mmdyn_plan_refit: {what} overlaps {other}")
+        ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
+        check(self.lib.mmdyn_plan_refit(*ptrs, K, N, B, T, cd, alpha, std_min, _stream()), "mmdyn_plan_refit")
+
     # ---- ensemble rollout: the N * B decoder rows of a step -> the N * B next states + the ensemble's statistics ----
     def ensemble_feed(self, groups, obs_avail, N, B):
         """One launch for up to FEED_GROUPS tensors: ``groups`` is a list of dicts {recon, obs | None, out, mean, var | None,
@@ -1231,11 +1308,16 @@ class HipBackend:
     def _iw_tables(name, *specs):
         """Pointers of contiguous GPU tables, each given as (tensor | None, shape, what, dtype): every shape and dtype is checked
         (ValueError) before the first pointer is taken (a CPU tensor: RuntimeError); None stays None."""
-        for t, shape, what, dtype in specs:
-            if t is not None and (t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
-                raise ValueError(f"mmdyn_hip: {name}: {what} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got "
-                                 f"{t.dtype} {tuple(t.shape)}")
+        HipBackend._check_tables(name, *specs)
         return [_ptr(t, dtype) for t, _, _, dtype in specs]
+
+    @staticmethod
+    def _check_tables(name, *specs):
+        """The shape / dtype / contiguity half of :meth:`_iw_tables`: ValueError, no pointer is taken."""
+        for t, shape, what, dtype in specs:
+            if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+                raise ValueError(f"mmdyn_hip: {name}: {what} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got "
+                                 f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
 
     def iw_latent(self, mu, lv, eps_noise, z, ratio, K, B, L):
         """mu / lv: fp32 [B, L] rows (may be column views of a fused heads output: unit inner stride, one row stride for both);

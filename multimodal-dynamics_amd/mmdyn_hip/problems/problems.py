@@ -866,21 +866,16 @@ class DynModeling(SeqModeling):
             out["recorded"] = inputs['shock']
             return out
 
-    def plan_rollout(self, data_input, data_target, candidates=None, steps=None, step_weight=None, top=None):
-        """Which of N candidate shock SEQUENCES takes frame 0 of each of the n sequences of one loader batch along its recorded
-        continuation (cnn-mvae, ``--conditional``): :meth:`mmdyn_hip.engine.MVAEInference.plan_rollout` with the batch built as
-        :meth:`rollout` builds it -- start = frame 0 of every sequence with its ``data[3]`` availability, goal = frames 1 .. T with
-        their availability (the dataset's final target for t + 1 = l; the pose goal always counts), every step scored --, the
-        problem's KL weight and pose multiplier, posterior-mean latents.  ``candidates``: as the engine takes them; None: the
-        batch's own n recorded shock sequences (``data[4]``, [n, T, ...]), shared by every row, so the row's own sequence is
-        candidate b.  ``steps`` <= l (default l), ``step_weight`` [T], ``top``: as the engine takes them.  Eval-mode arithmetic as
-        in :meth:`plan`.  Returns clones of the engine's dict plus ``recorded``: the [n, T, ...] shocks."""
+    def _horizon_batch(self, who, data_input, data_target, steps):
+        """The request :meth:`plan_rollout` and :meth:`plan_refine` build from one loader batch: (T, the start = frame 0 of each of
+        the n sequences as ``x`` / ``pose`` / ``available`` keywords, the goal frames 1 .. T [T, n, ...] with their availability,
+        the recorded shock sequences [n, T, ...]); ValueError for a batch or a model the planners do not serve."""
         if 'mvae' not in str(self.parameters.get('model_name')):
-            raise ValueError(f"plan_rollout() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
+            raise ValueError(f"{who}() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
         if not isinstance(data_input, (list, tuple)) or len(data_input) < 4 or self.parameters.get('input_type') != 'visuotactile':
-            raise ValueError("plan_rollout() takes a visuotactile batch in the loader's format (a list of tensors)")
+            raise ValueError(f"{who}() takes a visuotactile batch in the loader's format (a list of tensors)")
         if not self._conditional:
-            raise ValueError("plan_rollout() was called on an unconditional model: candidate conditions need --conditional")
+            raise ValueError(f"{who}() was called on an unconditional model: candidate conditions need --conditional")
         if len(data_input) < 5:
             raise ValueError("a conditional model needs the shock force of every frame (data[4])")
         l = int(self._seq_length)
@@ -895,13 +890,57 @@ class DynModeling(SeqModeling):
         recorded = data[4].reshape((n, l) + tuple(data[4].shape[1:]))[:, :T].to(dev)
         if recorded.dim() == 3 and self._model.categorical_conditions and recorded.shape[2] == 1:
             recorded = recorded[:, :, 0]
+        start = dict(x=[data[0][::l].to(dev), data[1][::l].to(dev)], pose=data[2][::l].to(dev) if self._model._use_pose else None,
+                     available=data[3][::l].to(dev))
+        return T, start, goal, goal_has, recorded
+
+    def plan_rollout(self, data_input, data_target, candidates=None, steps=None, step_weight=None, top=None):
+        """Which of N candidate shock SEQUENCES takes frame 0 of each of the n sequences of one loader batch along its recorded
+        continuation (cnn-mvae, ``--conditional``): :meth:`mmdyn_hip.engine.MVAEInference.plan_rollout` with the batch built as
+        :meth:`rollout` builds it -- start = frame 0 of every sequence with its ``data[3]`` availability, goal = frames 1 .. T with
+        their availability (the dataset's final target for t + 1 = l; the pose goal always counts), every step scored --, the
+        problem's KL weight and pose multiplier, posterior-mean latents.  ``candidates``: as the engine takes them; None: the
+        batch's own n recorded shock sequences (``data[4]``, [n, T, ...]), shared by every row, so the row's own sequence is
+        candidate b.  ``steps`` <= l (default l), ``step_weight`` [T], ``top``: as the engine takes them.  Eval-mode arithmetic as
+        in :meth:`plan`.  Returns clones of the engine's dict plus ``recorded``: the [n, T, ...] shocks."""
+        T, start, goal, goal_has, recorded = self._horizon_batch('plan_rollout', data_input, data_target, steps)
         with self._serving('_horizon_planner') as eng:
-            res = eng.plan_rollout([data[0][::l].to(dev), data[1][::l].to(dev)],
-                                   pose=data[2][::l].to(dev) if self._model._use_pose else None, steps=T, goal=goal,
-                                   candidates=recorded if candidates is None else candidates, step_weight=step_weight, top=top,
-                                   kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier, available=data[3][::l].to(dev),
-                                   goal_available=goal_has)
-            clone = lambda v: None if v is None else ([clone(t) for t in v] if isinstance(v, (list, tuple)) else v.clone())
-            out = {k: clone(v) for k, v in res.items()}
-            out["recorded"] = recorded
-            return out
+            res = eng.plan_rollout(steps=T, goal=goal, candidates=recorded if candidates is None else candidates,
+                                   step_weight=step_weight, top=top, kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier,
+                                   goal_available=goal_has, **start)
+            return self._cloned(res, recorded)
+
+    @staticmethod
+    def _cloned(res, recorded):
+        """Clones of an engine's result dict (its tensors are a graph's static outputs) plus ``recorded``."""
+        clone = lambda v: None if v is None else ([clone(t) for t in v] if isinstance(v, (list, tuple)) else v.clone())
+        out = {k: clone(v) for k, v in res.items()}
+        out["recorded"] = recorded
+        return out
+
+    def plan_refine(self, data_input, data_target, steps=None, candidates=64, elites=8, iterations=4, init_mean=None, init_std=None,
+                    bounds=None, alpha=0.0, std_min=0.0, step_weight=None, sample=False):
+        """The shock sequence that takes frame 0 of each of the n sequences of one loader batch along its recorded continuation,
+        searched by the cross-entropy method (cnn-mvae, ``--conditional`` with real-valued shocks):
+        :meth:`mmdyn_hip.engine.MVAEInference.plan_refine` on the request :meth:`plan_rollout` builds, every step scored, the
+        problem's KL weight and pose multiplier.  ``init_mean`` / ``init_std`` default to the per-(step, dimension) mean and
+        population standard deviation of the batch's n recorded shock sequences, ``bounds`` to their per-dimension minimum and
+        maximum; ``candidates`` / ``elites`` / ``iterations`` / ``alpha`` / ``std_min`` / ``step_weight`` / ``sample``: as the
+        engine takes them.  Eval-mode arithmetic as in :meth:`plan`.  Returns clones of the engine's dict plus ``recorded``."""
+        T, start, goal, goal_has, recorded = self._horizon_batch('plan_refine', data_input, data_target, steps)
+        if self._model.categorical_conditions:
+            raise ValueError("plan_refine() refits a distribution over real-valued shocks; a categorical model is out of scope")
+        shocks = recorded.to(torch.float32)
+        if init_mean is None:
+            init_mean = shocks.mean(0)
+        if init_std is None:
+            init_std = shocks.std(0, unbiased=False)
+        if bounds is None:
+            flat = shocks.reshape(-1, shocks.shape[-1])
+            bounds = (flat.min(0).values, flat.max(0).values)
+        with self._serving('_refiner') as eng:
+            res = eng.plan_refine(steps=T, goal=goal, init_mean=init_mean, init_std=init_std, candidates=candidates, elites=elites,
+                                  iterations=iterations, alpha=alpha, std_min=std_min, bounds=bounds, step_weight=step_weight,
+                                  kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier, goal_available=goal_has,
+                                  sample=sample, **start)
+            return self._cloned(res, recorded)
