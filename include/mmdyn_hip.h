@@ -921,6 +921,30 @@ int mmdyn_bn_swish_fwd_planes(const float* y, const float* mean, const float* rs
 int mmdyn_bn_swish_bwd_apply_planes(const float* da, const float* y, const float* mean, const float* rstd, const float* gamma,
                                     const float* beta, const float* sums, float* dy, void* dy_planes, int G, int rows_per_group,
                                     int C, int da_is_du, void* stream);
+/* The 3-channel layers' direct kernel (csrc/conv3.hip) with plane-row outputs, for the fp32x3 arithmetic on fp32 storage: the
+ * 32-channel tensor the kernel produces goes to HBM as the plane tensor its consumer GEMMs take ([rows][3][32] bf16, the exact
+ * three-term split as mmdyn_split_planes writes it, bit for bit), so no fp32 copy of it and no stand-alone split pass exist.
+ * Images are [G * Bg][3][H][H] fp32 NCHW with H = 64 (any other H: MMDYN_ERR_SHAPE), Wp the packed [32][64] fp32 weight of
+ * mmdyn_igemm_nt's MMDYN_IM2COL3 mode, rows = G * Bg * (H/2)^2.  Null pointer: MMDYN_ERR_NULL; rows * 32 >= 2^31: MMDYN_ERR_RANGE;
+ * both before anything is launched.
+ *   mmdyn_conv3_fwd_planes: Conv2d(3, 32, 4, 2, 1) forward (vae.py:198).  C [rows][32] fp32 = the pre-activation, exactly
+ *     mmdyn_igemm_nt(MMDYN_IM2COL3)'s C; act_planes = the split of act(C), exactly mmdyn_split_planes of that launch's C_act
+ *     (act: MMDYN_ACT_NONE / SWISH / RELU, anything else MMDYN_ERR_SHAPE).
+ *   Input gradient of ConvTranspose2d(32, 3, 4, 2, 1) (vae.py:277) through the train-mode BatchNorm + Swish below it, in two
+ *   passes of one main loop instead of mmdyn_igemm_nt_dgrad_bn + mmdyn_bn_swish_bwd_apply_planes(da_is_du = 1) -- du, which
+ *   existed only to cross the finalize between them, is recomputed by the second pass and never stored:
+ *   mmdyn_conv3_dgrad_bn_stats: stats [G][T][2][32], T = mmdyn_igemm_stat_tiles(MMDYN_IM2COL3, ...): the per-tile sums of du and
+ *     du * xhat, the table mmdyn_igemm_nt_dgrad_bn writes for the same inputs, bit for bit;
+ *   mmdyn_conv3_dgrad_bn_apply_planes: sums [G][2][32] = the finalized sums (mmdyn_bn_bwd_finalize / _finalize_sums);
+ *     dy_planes = dL/dy as plane rows, the bits mmdyn_bn_swish_bwd_apply_planes(da_is_du = 1) writes from the stored du.
+ * Added without touching an existing signature or workspace: the revision stays 6. */
+int mmdyn_conv3_fwd_planes(const float* x, const float* Wp, float* C, void* act_planes, int G, int Bg, int H, int act,
+                           void* stream);
+int mmdyn_conv3_dgrad_bn_stats(const float* dlogits, const float* Wp, float* stats, const float* y, const float* mean,
+                               const float* rstd, const float* gamma, const float* beta, int G, int Bg, int H, void* stream);
+int mmdyn_conv3_dgrad_bn_apply_planes(const float* dlogits, const float* Wp, const float* y, const float* mean,
+                                      const float* rstd, const float* gamma, const float* beta, const float* sums,
+                                      void* dy_planes, int G, int Bg, int H, void* stream);
 /* Backward of EVAL-mode nn.BatchNorm2d + Swish (vae.py:200-208, 268-276 under module.eval(): F.batch_norm(training=False), whose
  * autograd the reference gets for free) in ONE pass over [G * rows_per_group][C], fp32, shapes as the kernels above.  The forward
  * is u = gamma * (y - mean) * rstd + beta, a = swish(u), with mean / rstd [G][C] the running estimates (mmdyn_bn_eval_stats):

@@ -405,7 +405,7 @@ __global__ void bn_swish_bwd_apply_planes_kernel(const float* __restrict__ da, c
         float xh = (v[q][k] - m[k]) * r[k];
         float u = ga[k] * xh + be[k];
         float du = da_is_du ? d[q][k] : d[q][k] * swish_gradf_(u);
-        o[q][k] = ga[k] * r[k] * (du - s0[k] * inv_n - xh * (s1[k] * inv_n));
+        o[q][k] = bn_swish_bwd_dy(du, xh, ga[k], r[k], s0[k], s1[k], inv_n, q == 1 && k == 3);
       }
     }
     if (dy) {

@@ -317,6 +317,22 @@ __device__ __forceinline__ float swish_gradf_(float x) {
   float s = sigmoidf_(x);
   return s * (1.0f + x * (1.0f - s));
 }
+// One element of the apply pass of the train-mode BatchNorm + Swish backward, from du = dL/da * swish'(gamma * xh + beta):
+//   dy = gamma * rstd * (du - s0 / n - xh * (s1 / n)),   s0 = sum du, s1 = sum du * xh over the group, inv_n = 1 / n.
+// Shared by bn_swish_bwd_apply_planes_kernel (bn.hip) and the last decoder layer's two-pass input gradient (conv3.hip, the apply
+// pass), which must give the same bits.  The operation tree is therefore spelled out and contraction is off inside: the first
+// subtraction is one fma; the second is a product and a subtraction -- except for `tail_fused`, where it is one fma as well.
+// That exception is channel 7 of every 8-channel granule: it is the tree bn_swish_bwd_apply_planes_kernel has evaluated since
+// it was written (the vectoriser paired seven of a thread's eight elements and the contraction took the eighth), kept so that
+// results do not move.
+__device__ __forceinline__ float bn_swish_bwd_dy(float du, float xh, float ga, float r, float s0, float s1, float inv_n,
+                                                 bool tail_fused) {
+#pragma clang fp contract(off)
+  const float t0 = __builtin_fmaf(-inv_n, s0, du);
+  const float s1n = inv_n * s1;
+  const float t = tail_fused ? __builtin_fmaf(-s1n, xh, t0) : t0 - s1n * xh;
+  return (ga * r) * t;
+}
 __device__ __forceinline__ float apply_act(float x, int act) {
   if (act == MMDYN_ACT_SWISH) return swishf_(x);
   if (act == MMDYN_ACT_RELU) return x > 0.f ? x : 0.f;

@@ -10,6 +10,9 @@
 //     = the 32 rows of one 32x32 MFMA tile) and reads its A fragments STRAIGHT from the image -- with the K order
 //     permuted so that lane half h takes kw = h, h+2, the 64 lanes of one load cover 64 consecutive floats of one
 //     image row.  The weights live in 24 VGPRs for the life of the (persistent) block.  No LDS on the operand path.
+//     Where the consumer of the 32-channel tensor takes plane operands (fp32x3), the epilogue writes plane rows itself
+//     (template parameter OUT): the forward's activated output, and dL/dy of the last decoder BatchNorm from a second pass
+//     of the same main loop that recomputes du instead of reading it back (mmdyn_conv3_* entry points at the end).
 //   * conv3_wgrad (weight gradient of both layers): the reduction runs over pixels, so the window is the MFMA B
 //     operand and is gathered per lane.  Each wave stages the 12 image rows its output row touches in a private,
 //     zero-padded LDS patch (coalesced 16-byte loads, double buffered, no block barrier in the loop) and gathers
@@ -29,6 +32,10 @@ struct Conv3Geom {
   const float* bn_rstd;
   const float* bn_gamma;
   const float* bn_beta;
+  // the plane-row forms (C3_ACT_PLANES / C3_DY_PLANES below)
+  bf16_t* planes;        // [rows][3][32] bf16: hi | mid | lo of the activated output / of dL/dy
+  const float* bn_sums;  // C3_DY_PLANES: the finalized sums [G][2][32] (sum du, sum du * xhat)
+  float inv_n;           // C3_DY_PLANES: 1 / (Bg * Ho * Ho)
 };
 
 // A wave-uniform pointer, pinned into a scalar register pair (and kept in the GLOBAL address space): the compiler then
@@ -57,8 +64,27 @@ template <> struct store16<half_t> { typedef half_t type; };
 // of an output image row (SEGS segments per row); units are numbered (sample, row, segment), which is also their order
 // in the channels-last output, so unit u owns the 32 x 32 output block at byte offset u * OROW_B.
 // BN: BatchNorm+Swish backward epilogue; ACT: -1 = no second output, else the activation of the second output
+// OUT (fp32 storage only): what the epilogue stores
+//   C3_ROWS        C (and C_act) as channels-last rows of T, the BatchNorm partial sums when asked for
+//   C3_ACT_PLANES  !BN: C as fp32 rows, the ACTIVATED output as plane rows ([plane][32] bf16 per pixel, hi | mid | lo: the exact
+//                  three-term split, common.h) -- the operand format of the plane launches that consume it; no fp32 C_act
+//   C3_STATS       BN: the partial sums alone -- du = acc * swish'(.) is not stored
+//   C3_DY_PLANES   BN: the same du, recomputed, goes straight through the apply pass of the BatchNorm backward
+//                  (bn_swish_bwd_dy, common.h, with the finalized sums) and dL/dy is stored as plane rows; nothing else is written
+// A plane row is 192 bytes; a lane owns one channel, so adjacent lanes exchange one value per pair of pixels (the even lane
+// sends its second pixel, the odd lane its first) and every lane stores one dword per plane: channels (x, x + 1) of the
+// first pixel from the even lane, channels (x - 1, x) of the second from the odd one -- 4 x 64 contiguous bytes per store.
+// C3_STATS: one element into the running sums with the operation tree of the instance that also stores du (a product rounded on
+// its own, then cs + du and fma(du, xh, cq)).  Spelled out with contraction off: once du has no store, the contraction would
+// otherwise fold acc * swish' into the sum cs and the table would differ in its last bits.
+__device__ __forceinline__ void stat_acc_as_stored(float du, float xh, float& cs, float& cq) {
+#pragma clang fp contract(off)
+  cs = cs + du;
+  cq = __builtin_fmaf(du, xh, cq);
+}
 constexpr int C3_N = 32;
-template <typename T, bool BN, int ACT, int SEGS>
+constexpr int C3_ROWS = 0, C3_ACT_PLANES = 1, C3_STATS = 2, C3_DY_PLANES = 3;
+template <typename T, bool BN, int ACT, int SEGS, int OUT = C3_ROWS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv3_nt_kernel(
     const float* __restrict__ img, const float* __restrict__ Wp, T* __restrict__ C, T* __restrict__ C_act,
     float* __restrict__ stats, const Conv3Geom g) {
@@ -100,6 +126,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const unsigned voffB = (4 * h * C3_N + x) * sizeof(T);              // pixel +4h of the unit, channel x
   constexpr unsigned IMG_B = 3 * C3_HI * C3_HI * sizeof(float);       // bytes per sample of the image
   constexpr unsigned OROW_B = 32 * C3_N * sizeof(T);                  // bytes per unit of output (32 px x 32 ch)
+  constexpr bool PLANES = OUT == C3_ACT_PLANES || OUT == C3_DY_PLANES;
+  static_assert(OUT == C3_ROWS || sizeof(T) == 4, "the plane-row and statistics-only forms are fp32 storage only");
+  static_assert(BN == (OUT == C3_STATS || OUT == C3_DY_PLANES) || OUT == C3_ROWS, "C3_STATS / C3_DY_PLANES belong to the BN epilogue");
+  constexpr unsigned PROW_B = 3 * C3_N * sizeof(bf16_t);              // bytes per plane row (one pixel)
+  // plane stores: the even lane writes channels (x, x + 1) of pixel +4h, the odd lane channels (x - 1, x) of pixel +4h + 1
+  const unsigned voffP = (4 * h + (x & 1)) * PROW_B + (x & ~1) * sizeof(bf16_t);
 
   // tile t = 128 GEMM rows = units 4t .. 4t+3 (wave w takes unit 4t + w); UNITS / 4 tiles per sample
   struct TileAt {
@@ -133,6 +165,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     return gld1<float>(rowp + p.xoB[j & 1]);
   };
   auto erow = [](int e) { return (unsigned)(((e & 3) + 8 * (e >> 2)) * C3_N * sizeof(T)); };   // immediate offsets
+  auto prow = [](int e) { return (unsigned)(((e & 3) + 8 * (e >> 2)) * PROW_B); };
 
   // Software pipeline over the block's tiles: the loads of tile t+1 are issued behind the MFMA / epilogue step
   // that consumed the same register of tile t, so they fly during the rest of tile t (no second register set).
@@ -171,21 +204,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const gchar_p cb = sgpr_ptr(reinterpret_cast<const char*>(C) + cur.orow) + voffB;
     const gchar_p ab = sgpr_ptr(reinterpret_cast<const char*>(C_act) + cur.orow) + voffB;
     const gchar_p yb = sgpr_ptr(reinterpret_cast<const char*>(g.bn_y) + nxt.orow) + voffB;
-    float cs = 0.f, cq = 0.f;
+    // (a unit's plane rows: 32 x 192 bytes against the 32 x 128 of its fp32 rows)
+    const gchar_p pb = sgpr_ptr(reinterpret_cast<const char*>(g.planes) + (PLANES ? cur.orow / 2 * 3 : 0)) + voffP;
+    float ap_s0 = 0.f, ap_s1 = 0.f;
+    if (OUT == C3_DY_PLANES) {
+      ap_s0 = g.bn_sums[(grp * 2 + 0) * 32 + x];
+      ap_s1 = g.bn_sums[(grp * 2 + 1) * 32 + x];
+    }
+    float cs = 0.f, cq = 0.f, pv = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       float v = acc[e];
+      float o = 0.f;                   // PLANES: the value that goes into the plane rows
       if (BN) {
         const float xh = (yv[e] - bn_m) * bn_r;
         yv[e] = gld1<T>(yb + erow(e));
         v *= swish_gradf_(bn_g * xh + bn_b);
-        cs += v;
-        cq += v * xh;
+        if (OUT == C3_DY_PLANES) {
+          o = bn_swish_bwd_dy(v, xh, bn_g, bn_r, ap_s0, ap_s1, g.inv_n, (x & 7) == 7);
+        } else if (OUT == C3_STATS) {
+          stat_acc_as_stored(v, xh, cs, cq);
+        } else {
+          cs += v;
+          cq += v * xh;
+        }
       } else {
         cs += v;
         cq += v * v;
+        if (OUT == C3_ACT_PLANES) o = apply_act(v, ACT);
       }
-      if (sizeof(T) == 2) {
+      if (PLANES) {
+        if (OUT == C3_ACT_PLANES) *(GLOBAL_AS float*)(cb + erow(e)) = v;
+        if (!(e & 1)) {
+          pv = o;
+        } else {
+          // pixels e - 1 and e of this lane's channel: the even lane keeps e - 1 and sends e, the odd lane the reverse
+          const float got = __shfl_xor((x & 1) ? pv : o, 1, 64);
+          uint32_t p_hi, p_mid, p_lo;
+          split3_bf16((x & 1) ? got : pv, (x & 1) ? o : got, p_hi, p_mid, p_lo);
+          *(GLOBAL_AS uint32_t*)(pb + prow(e - 1)) = p_hi;
+          *(GLOBAL_AS uint32_t*)(pb + prow(e - 1) + 64) = p_mid;
+          *(GLOBAL_AS uint32_t*)(pb + prow(e - 1) + 128) = p_lo;
+        }
+      } else if (OUT == C3_STATS) {
+        // (the partial sums below are this pass's only output)
+      } else if (sizeof(T) == 2) {
         // adjacent channels sit in adjacent lanes: the even lane stores both as one dword
         const float vn = __shfl_down(v, 1, 64);
         if (!(x & 1)) {
@@ -436,6 +499,73 @@ int mmdyn_conv3_nt_try(const float* A, const float* Bp, const float* bias, void*
 #undef CONV3_LAUNCH
 #undef CONV3_CASE
   MMDYN_LAUNCH_CHECK();
+}
+
+// ---- plane-row forms of conv3_nt (fp32 storage, 64 x 64 images) ----------------------------------------------------------
+namespace {
+// out: C3_ACT_PLANES (with `act`), C3_STATS or C3_DY_PLANES.  One image size only: 64 x 64, the reference's -- the extended
+// stacks (128 / 256) keep the launches they have
+int conv3_planes_launch(int out, const float* img, const float* Wp, float* C, float* stats, void* planes, const float* y,
+                        const float* mean, const float* rstd, const float* gamma, const float* beta, const float* sums, int G,
+                        int Bg, int H, int act, hipStream_t st) {
+  if (G <= 0 || Bg <= 0 || H != 64) return MMDYN_ERR_SHAPE;
+  const int Ho = H / 2;
+  if ((int64_t)G * Bg * Ho * Ho * C3_N >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  Conv3Geom g{};
+  g.G = G;
+  g.Bg = Bg;
+  g.Hi = H;
+  g.Wi = H;
+  g.Ho = Ho;
+  g.ldc = C3_N;
+  g.act = act;
+  g.want_stats = stats != nullptr;
+  g.tiles_per_group = Bg * Ho * Ho / 128;
+  g.bn_y = y;
+  g.bn_mean = mean;
+  g.bn_rstd = rstd;
+  g.bn_gamma = gamma;
+  g.bn_beta = beta;
+  g.planes = reinterpret_cast<bf16_t*>(planes);
+  g.bn_sums = sums;
+  g.inv_n = 1.f / (float)(Bg * Ho * Ho);      // (as bn_swish_bwd_apply_planes_kernel forms it from rows_per_group)
+  const int ntiles = G * g.tiles_per_group;
+  const dim3 grid(ntiles < CONV3_GRID ? ntiles : CONV3_GRID);
+  float* none = nullptr;
+#define CONV3_PLANES(BN_, ACT_, OUT_) \
+  hipLaunchKernelGGL((conv3_nt_kernel<float, BN_, ACT_, 1, OUT_>), grid, dim3(256), 0, st, img, Wp, C, none, stats, g)
+  if (out == C3_STATS) CONV3_PLANES(true, -1, C3_STATS);
+  else if (out == C3_DY_PLANES) CONV3_PLANES(true, -1, C3_DY_PLANES);
+  else if (act == MMDYN_ACT_SWISH) CONV3_PLANES(false, MMDYN_ACT_SWISH, C3_ACT_PLANES);
+  else if (act == MMDYN_ACT_RELU) CONV3_PLANES(false, MMDYN_ACT_RELU, C3_ACT_PLANES);
+  else if (act == MMDYN_ACT_NONE) CONV3_PLANES(false, MMDYN_ACT_NONE, C3_ACT_PLANES);
+  else return MMDYN_ERR_SHAPE;
+#undef CONV3_PLANES
+  MMDYN_LAUNCH_CHECK();
+}
+}  // namespace
+
+extern "C" int mmdyn_conv3_fwd_planes(const float* x, const float* Wp, float* C, void* act_planes, int G, int Bg, int H, int act,
+                                      void* stream) {
+  if (!x || !Wp || !C || !act_planes) return MMDYN_ERR_NULL;
+  return conv3_planes_launch(C3_ACT_PLANES, x, Wp, C, nullptr, act_planes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, G,
+                             Bg, H, act, (hipStream_t)stream);
+}
+
+extern "C" int mmdyn_conv3_dgrad_bn_stats(const float* dlogits, const float* Wp, float* stats, const float* y, const float* mean,
+                                          const float* rstd, const float* gamma, const float* beta, int G, int Bg, int H,
+                                          void* stream) {
+  if (!dlogits || !Wp || !stats || !y || !mean || !rstd || !gamma || !beta) return MMDYN_ERR_NULL;
+  return conv3_planes_launch(C3_STATS, dlogits, Wp, nullptr, stats, nullptr, y, mean, rstd, gamma, beta, nullptr, G, Bg, H,
+                             MMDYN_ACT_NONE, (hipStream_t)stream);
+}
+
+extern "C" int mmdyn_conv3_dgrad_bn_apply_planes(const float* dlogits, const float* Wp, const float* y, const float* mean,
+                                                 const float* rstd, const float* gamma, const float* beta, const float* sums,
+                                                 void* dy_planes, int G, int Bg, int H, void* stream) {
+  if (!dlogits || !Wp || !y || !mean || !rstd || !gamma || !beta || !sums || !dy_planes) return MMDYN_ERR_NULL;
+  return conv3_planes_launch(C3_DY_PLANES, dlogits, Wp, nullptr, nullptr, dy_planes, y, mean, rstd, gamma, beta, sums, G, Bg, H,
+                             MMDYN_ACT_NONE, (hipStream_t)stream);
 }
 
 // chunks = partial slabs = blocks; 1 when the shape is not this file's

@@ -125,6 +125,9 @@ _SIGNATURES = {
     "mmdyn_igemm_planes_served": "iiiiiiiii",
     "mmdyn_bn_swish_fwd_planes": "ppppppp" + "iii" + "p",
     "mmdyn_bn_swish_bwd_apply_planes": "ppppppppp" + "iiii" + "p",
+    "mmdyn_conv3_fwd_planes": "pppp" + "iiii" + "p",
+    "mmdyn_conv3_dgrad_bn_stats": "pppppppp" + "iii" + "p",
+    "mmdyn_conv3_dgrad_bn_apply_planes": "ppppppppp" + "iii" + "p",
     "mmdyn_bn_eval_swish_bwd": "ppppppppp" + "iiii" + "p",
     "mmdyn_bn_swish_fwd_b16": "pppppp" + "iiii" + "p",
     "mmdyn_bn_swish_bwd_reduce_b16": "ppppppp" + "iiii" + "p",

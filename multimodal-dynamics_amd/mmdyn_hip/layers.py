@@ -129,6 +129,18 @@ def _plane_twin(Wp):
 
 
 PATCH_PLANES = True      # (False: the 32-channel up-sampling layers keep fp32 operands -- A/B measurements only)
+# The 3-channel layers next to a plane consumer (64 x 64 images, fp32 storage; False: A/B measurements only -- the same bits either way)
+CONV1_PLANES = True      # encoder conv 0 writes its activated output as plane rows: no fp32 a1, no stand-alone split launch
+OUT3_RECOMPUTE = True    # last decoder layer's input gradient in two passes of one main loop: du is recomputed, never stored
+
+
+def _conv3_plane_op(name, switch, S, *tensors):
+    """The backend's plane-row form ``name`` of the 3-channel layers' kernel when this launch may take it, else None (the caller
+    then issues the launches it always did): the switch is on, the image is the 64 x 64 one, everything is fp32 and the backend
+    has the op (the emulation backend of the CPU tests does not)."""
+    if not switch or S != 64 or ACT_DTYPE != torch.float32 or any(t.dtype != torch.float32 for t in tensors):
+        return None
+    return getattr(ops.B, name, None)
 
 
 def planes_served(mode, G, Bg, Hi, Cin, Ho, N):
@@ -402,8 +414,19 @@ def dgrad_bn_swish_backward(x, Wp, mode, G, Bg, Hi, Cin, Ho, N, stride, offset, 
     if y.dtype == torch.float32 and mode != IM2COL3:
         x, Wp = split_operands(x, Wp, mode, G, Bg, Hi, Cin, Ho, N)
     T = _stat_tiles(x, Wp, mode, G, Bg, Hi, Cin, Ho, N)
-    du = torch.empty_like(y)
     partial = _new(y, G, T, 2, N)
+    if mode == IM2COL3 and not eval_mode and planes_out:
+        # the last decoder layer (OUT3_RECOMPUTE): the statistics pass writes the partial sums alone, the apply pass runs the same
+        # main loop again and turns the recomputed du into dL/dy plane rows -- no du tensor crosses the finalize
+        stats_op = _conv3_plane_op("conv3_dgrad_bn_stats", OUT3_RECOMPUTE, Hi, x, Wp, y)
+        apply_op = _conv3_plane_op("conv3_dgrad_bn_apply_planes", OUT3_RECOMPUTE, Hi, x, Wp, y)
+        if stats_op is not None and apply_op is not None:
+            stats_op(x, Wp, partial, y, mean, rstd, bn.gamma, bn.beta, G, Bg, Hi)
+            sums = _bn_backward_sums(y, partial, T, dgamma, dbeta, G, N)
+            dyp = ops.Planes(y.shape[0], y.shape[1], y.device)
+            apply_op(x, Wp, y, mean, rstd, bn.gamma, bn.beta, sums, dyp, G, Bg, Hi)
+            return dyp
+    du = torch.empty_like(y)
     ops.B.igemm_nt_dgrad_bn(x, Wp, du, partial, y, mean, rstd, bn.gamma, bn.beta, mode, G, Bg, Hi, Hi, Cin, Ho, Ho, N,
                             stride, offset)
     if eval_mode:
@@ -864,17 +887,26 @@ def encoder_trunk_forward_steps(P, buf, x, G=1, repeat=1, packed=None, training=
     c = {"Bt": Bt, "G": G, "Bg": Bg, "pk": pk, "S": S, "training": bool(training)}
     H = S // 2
     W1p = pk["W1p"]                                                          # [32][64], cols 48.. zero
-    u1, a1 = _act(x, Bt * H * H, 32), _act(x, Bt * H * H, 32)
-    # first layer: the k4 s2 p1 window of the NCHW image is gathered on the fly (no im2col matrix in HBM)
-    ops.B.igemm_nt(x, W1p, None, u1, a1, None, None, IM2COL3, 1, Bt, S, S, 64, H, H, 32, 32, 1, 0,
-                   ACT_SWISH, 1)
-    yield
-    stages, a, cin = [], a1, 32
     # fp32x3: an activation whose consumer GEMM takes plane operands exists ONLY as ops.Planes from here on (the convolution
-    # that reads it and the weight gradient that reads it as `a_in` both take it so); conv_net.0's output comes out of its kernel
-    # as fp32 and is split by its own launch
+    # that reads it and the weight gradient that reads it as `a_in` both take it so); conv_net.0's kernel writes its activated
+    # output so itself on 64 x 64 images (CONV1_PLANES: no fp32 a1 then -- the backward reads u1 and the planes), else the
+    # activation comes out as fp32 and is split by its own launch
     # (eval mode too since round 6: the inference engine's launches take the same plane operands as the train step's)
-    if len(convs) and planes_served(CONV, G, Bg, H, 32, H // 2, P[f"conv_net.{convs[0]}.weight"].shape[0]):
+    a_planes = bool(len(convs)) and planes_served(CONV, G, Bg, H, 32, H // 2, P[f"conv_net.{convs[0]}.weight"].shape[0])
+    u1 = _act(x, Bt * H * H, 32)
+    fwd_planes = _conv3_plane_op("conv3_fwd_planes", CONV1_PLANES and a_planes, S, x, W1p, u1)
+    # first layer: the k4 s2 p1 window of the NCHW image is gathered on the fly (no im2col matrix in HBM)
+    if fwd_planes is not None:
+        a1, a = None, ops.Planes(Bt * H * H, 32, x.device)
+        fwd_planes(x, W1p, u1, a, 1, Bt, S, ACT_SWISH)
+    else:
+        a1 = _act(x, Bt * H * H, 32)
+        ops.B.igemm_nt(x, W1p, None, u1, a1, None, None, IM2COL3, 1, Bt, S, S, 64, H, H, 32, 32, 1, 0,
+                       ACT_SWISH, 1)
+        a = a1
+    yield
+    stages, cin = [], 32
+    if a_planes and fwd_planes is None:
         a = as_planes(a1, 32)
     for j, i in enumerate(convs):
         cout = P[f"conv_net.{i}.weight"].shape[0]

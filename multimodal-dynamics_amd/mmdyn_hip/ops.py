@@ -678,6 +678,44 @@ class HipBackend:
         check(self.lib.mmdyn_bn_swish_bwd_apply(pd, py, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(sums), po, G,
                                                 rows_per_group, C, int(da_is_du), _stream()), "mmdyn_bn_swish_bwd_apply")
 
+    # ---- the 3-channel layers' direct kernel with plane-row outputs (fp32x3 on fp32 storage, 64 x 64 images) ----
+    @staticmethod
+    def _conv3_shapes(name, img, Wp, G, Bg, H, **rows32):
+        """The sizes the kernel cannot check: the NCHW image, the packed [32][64] weight, every [rows][32] tensor / plane tensor."""
+        rows = G * Bg * (H // 2) ** 2
+        if img.numel() != G * Bg * 3 * H * H or Wp.numel() != 32 * 64:
+            raise ValueError(f"mmdyn_hip: {name}: image / packed weight of the wrong shape")
+        for k, t in rows32.items():
+            if isinstance(t, Planes):
+                if t.rows != rows or t.C != 32 or not t.t.is_cuda or not t.t.is_contiguous():
+                    raise ValueError(f"mmdyn_hip: {name}: {k} must be a contiguous GPU plane tensor of [{rows}][3][32]")
+            elif t.numel() != rows * 32:
+                raise ValueError(f"mmdyn_hip: {name}: {k} must hold [{rows}][32] elements")
+
+    def conv3_fwd_planes(self, x, Wp, C, act_planes, G, Bg, H, act):
+        """Conv2d(3, 32, 4, 2, 1) forward: C = the fp32 pre-activation, ``act_planes`` (a Planes) = act(C) already split."""
+        self._conv3_shapes("conv3_fwd_planes", x, Wp, G, Bg, H, C=C, act_planes=act_planes)
+        check(self.lib.mmdyn_conv3_fwd_planes(_ptr(x), _ptr(Wp), _ptr(C), act_planes.t.data_ptr(), G, Bg, H, int(act), _stream()),
+              "mmdyn_conv3_fwd_planes")
+
+    def conv3_dgrad_bn_stats(self, dlogits, Wp, stats, y, mean, rstd, gamma, beta, G, Bg, H):
+        """Statistics pass of the last decoder layer's input gradient: the partial-sum table of igemm_nt_dgrad_bn, no du."""
+        self._conv3_shapes("conv3_dgrad_bn_stats", dlogits, Wp, G, Bg, H, y=y)
+        self._check_stat_tiles(stats, False, IM2COL3, G, Bg, H, H, 64, H // 2, H // 2, 32)
+        if mean.numel() != G * 32 or rstd.numel() != G * 32 or gamma.numel() != 32 or beta.numel() != 32:
+            raise ValueError("mmdyn_hip: conv3_dgrad_bn_stats: BatchNorm vectors of the wrong shape")
+        check(self.lib.mmdyn_conv3_dgrad_bn_stats(_ptr(dlogits), _ptr(Wp), _ptr(stats), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                                  _ptr(beta), G, Bg, H, _stream()), "mmdyn_conv3_dgrad_bn_stats")
+
+    def conv3_dgrad_bn_apply_planes(self, dlogits, Wp, y, mean, rstd, gamma, beta, sums, dy_planes, G, Bg, H):
+        """Apply pass: du recomputed, dL/dy written as ``dy_planes`` (a Planes) from the finalized ``sums`` [G][2][32]."""
+        self._conv3_shapes("conv3_dgrad_bn_apply_planes", dlogits, Wp, G, Bg, H, y=y, dy_planes=dy_planes)
+        if mean.numel() != G * 32 or rstd.numel() != G * 32 or gamma.numel() != 32 or beta.numel() != 32 or sums.numel() != G * 64:
+            raise ValueError("mmdyn_hip: conv3_dgrad_bn_apply_planes: BatchNorm vectors / sums of the wrong shape")
+        check(self.lib.mmdyn_conv3_dgrad_bn_apply_planes(_ptr(dlogits), _ptr(Wp), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                                         _ptr(beta), _ptr(sums), dy_planes.t.data_ptr(), G, Bg, H, _stream()),
+              "mmdyn_conv3_dgrad_bn_apply_planes")
+
     def bn_eval_swish_bwd(self, da, y, mean, rstd, gamma, beta, dy, partial, G, rows_per_group, C, da_is_du=False, planes=None):
         """Backward of eval-mode BatchNorm + Swish in one pass: dy = du * gamma * rstd -> ``dy`` (fp32) and / or ``planes`` (a
         Planes); ``partial`` (nullable) [G][colstats_tiles][2][C]: the tile sums bn_bwd_finalize turns into dgamma / dbeta.  With

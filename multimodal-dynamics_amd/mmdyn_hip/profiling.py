@@ -33,6 +33,16 @@ def _canon(name, a):
         return "conv3_wgrad", (y, Gt, partial, ops.IM2COL3, G * Bg, Hr, Hr, 32, 2 * Hr, 2 * Hr, 64, 1, 0, chunks)
     if name == "tconv_out3_bn_fwd":
         return "tconv_out3_fwd", a
+    # the plane-row forms of conv3_nt_kernel: the same main loop (and FLOPs) as the launches they stand in for
+    if name == "conv3_fwd_planes":
+        x, Wp, C, planes, G, Bg, H, act = a
+        return "conv3_nt", (x, Wp, None, C, planes, None, None, ops.IM2COL3, G, Bg, H, H, 64, H // 2, H // 2, 32, 32, 1, 0, act, 1)
+    if name == "conv3_dgrad_bn_stats":
+        x, Wp, stats, y, mean, rstd, gamma, beta, G, Bg, H = a
+        return "conv3_nt", (x, Wp, y, None, None, stats, None, ops.IM2COL3, G, Bg, H, H, 64, H // 2, H // 2, 32, 32, 1, 0, 0, 1)
+    if name == "conv3_dgrad_bn_apply_planes":
+        x, Wp, y, mean, rstd, gamma, beta, sums, planes, G, Bg, H = a
+        return "conv3_nt", (x, Wp, y, planes, None, None, None, ops.IM2COL3, G, Bg, H, H, 64, H // 2, H // 2, 32, 32, 1, 0, 0, 1)
     # the 3-channel layers run their own kernels (csrc/conv3.hip), not igemm_nt_kernel / wgrad_tn_kernel: booked apart so
     # that the launch counts and average durations of the MFMA families match what rocprofv3 reports per kernel name
     if name == "igemm_nt" and a[7] == ops.IM2COL3 and a[10] in (64, 128, 256) and \
