@@ -591,6 +591,38 @@ int mmdyn_elbo_assemble_weighted(const double* bce_rows, const double* mse_rows,
                                  const float* w, float* loss, float* wpartials, float* out, float* partials, float* w_sum_out, int P,
                                  int B, float kl_weight, float pose_multiplier, const float* kl_weight_dev, int kl_mode, void* stream);
 
+/* ---- the training step on a mixed-modality batch: per-row INPUT availability in the PoE, per-row TARGET availability in the loss ---
+ * L = (1/B) sum_p sum_b w_b * [ sum_{m in pass p, target m present in row b} rec_m(p, b) + kl_weight * KL(p, b) ]; the division stays
+ * by B.  Every row passes through every encoder and decoder (BatchNorm statistics are those of the whole batch); only the PoE leaves
+ * an absent (row, expert) unread, and only the loss leaves an absent (row, target) out.
+ *
+ * mmdyn_poe_bwd with BOTH the tables of mmdyn_poe_bwd_avail and the row weights of mmdyn_poe_bwd_weighted (the arguments are the
+ * union of the two; w_kl is required).  With avail null (or every entry null) the results are mmdyn_poe_bwd_weighted's bit for bit,
+ * with w_kl = 1 they are mmdyn_poe_bwd_avail's.  Any L: with L % 64 != 0 a wavefront spans rows and the per-expert branch diverges,
+ * each lane follows its own row's word. */
+int mmdyn_poe_bwd_avail_weighted(const mmdyn_pass_experts* passes, const uint8_t* const* avail, const float* eps_noise, const float* mu,
+                                 const float* logvar, const float* dz, const float* g_mu, const float* g_lv, float kl_scale,
+                                 const float* w_kl, int with_prior, int P, int B, int L, const float* kl_weight_dev, void* stream);
+/* The weight vectors of the three gradient seeds (visual BCE, tactile BCE, pose MSE) in one launch:
+ *   w_term[m][b] = tavail[b][m] != 0 ? (w ? w[b] : 1.f) : 0.f,  m = 0, 1, 2;   w_term: [3][B] float, OUTPUT.
+ * tavail: a TARGET-availability table (null = every target present); w: [B] float or null.  A select, never a product: the weight of
+ * a row whose target is absent (it may be NaN) reaches nothing.  One 32-bit word per row; a misaligned table or B <= 0:
+ * MMDYN_ERR_SHAPE; w_term null: MMDYN_ERR_NULL. */
+int mmdyn_term_weights(const uint8_t* tavail, const float* w, float* w_term, int B, void* stream);
+/* mmdyn_elbo_assemble_weighted with one [P][B] double table per TERM -- bce_v_rows (visual BCE), bce_t_rows (tactile BCE), mse_rows
+ * (pose MSE); any may be null = 0 -- and the target-availability table tavail (null = every target present).  A (row, term) whose
+ * target is absent is left out of loss / wpartials / out / partials by selection and its table entries are overwritten with 0
+ * (the tables are OUTPUTS for those entries), as in mmdyn_elbo_assemble_rows_avail.  The KL counts for every row.  w null = 1.
+ * Also written (either may be null): present [3] double, the number of rows that hold target m; term_sums [3][P] double, the
+ * UNWEIGHTED sum of term m's table over the rows that hold its target.  Everything else -- kl_mode, w_sum_out, kl_weight_dev, the
+ * fixed-order fp64 accumulation by one block without atomics -- as mmdyn_elbo_assemble_weighted: with tavail null and w given the
+ * results are its bits on the table bce_v_rows + bce_t_rows.  loss null: MMDYN_ERR_NULL; P > MMDYN_MAX_PASSES, a misaligned table,
+ * or bce_v_rows == bce_t_rows (non-null): MMDYN_ERR_SHAPE. */
+int mmdyn_elbo_assemble_avail_weighted(double* bce_v_rows, double* bce_t_rows, double* mse_rows, const double* kl_rows,
+                                       const double* kl_sum, const float* w, const uint8_t* tavail, float* loss, float* wpartials,
+                                       float* out, float* partials, float* w_sum_out, double* present, double* term_sums, int P, int B,
+                                       float kl_weight, float pose_multiplier, const float* kl_weight_dev, int kl_mode, void* stream);
+
 /* ---- importance-weighted K-sample bound (evaluation only; no reference op: the reference scores a sample with one draw and the
  * analytic KL, problems.py:401-458) -------------------------------------------------------------------------------------------------
  * L_K(x) = log (1/K) sum_k p(x|z_k) p(z_k) / q(z_k|x), z_k ~ q(z|x) (Burda et al., "Importance Weighted Autoencoders"), per request

@@ -14,7 +14,9 @@
 //   - assemblies of the [B] result from the row tables: elbo_assemble_rows with the reference's KL (the batch total in every row,
 //     problems.py:429, 456) or the per-sample one -- flag AVAIL: a target-availability word per row, a (row, term) whose target
 //     is absent is written as 0 into its table and left out of the row sum; elbo_assemble_weighted: the weighted scalar, its
-//     per-pass partials and the [B] vector of sum_b w_b that the reference's KL mode hands to the latent backward;
+//     per-pass partials and the [B] vector of sum_b w_b that the reference's KL mode hands to the latent backward -- flag AVAIL (the
+//     training step on a mixed batch): one table per term and a target-availability word per row, counts and per-term sums beside
+//     the loss; term_weights: the three gradient seeds' weight vectors of such a step, present ? w_b : 0 by selection;
 //     iw_assemble_rows: the importance-weighted K-sample bound L_K(x) = log (1/K) sum_k p(x|z_k) p(z_k) / q(z_k|x) from the
 //     [K][B] row tables and the density ratios of latent.hip's iw_latent: log_w_k = -rec_k - kl_weight * ratio_k,
 //     out[b] = -(logsumexp_k log_w_k - log K) and the effective sample size of the weights, max-subtracted, fp64.
@@ -300,29 +302,67 @@ __global__ void elbo_assemble_rows_kernel(std::conditional_t<AVAIL, double, cons
 // shuffle tree of wave_sum_d and the four wave totals in wave order -- no atomics, the same order in every run.
 //   S[p]  = sum_b w_b * (bce[p][b] + pose_multiplier * mse[p][b]),  K[p] = sum_b w_b * kl_rows[p][b],  W = sum_b w_b
 //   wpartials[p] = (S[p] + kl_weight * (kl_mode ? K[p] : W * kl_sum[p])) / B,  loss = sum_p wpartials[p]
-__global__ __launch_bounds__(256) void elbo_assemble_weighted_kernel(const double* __restrict__ bce, const double* __restrict__ mse,
-                                                                     const double* __restrict__ kl_rows,
-                                                                     const double* __restrict__ kl_sum, const float* __restrict__ w,
-                                                                     float* __restrict__ loss, float* __restrict__ wpartials,
-                                                                     float* __restrict__ out, float* __restrict__ partials,
-                                                                     float* __restrict__ w_sum_out, int P, int B, float kl_weight_arg,
-                                                                     float pose_multiplier, const float* __restrict__ kl_weight_dev,
-                                                                     int kl_mode) {
+// AVAIL (the training step on a mixed batch): one table per TERM -- bce is the visual term's, bce_t the tactile term's, mse the pose
+// term's -- and a target-availability word per row (null table: all present); a (row, term) whose target is absent is selected out
+// of every sum and its table entries are written back as 0.  w may then be null (= 1).  Beside the loss: present[m] = the number of
+// rows that hold target m, term_sums[m][p] = the unweighted sum of term m's table over those rows.  The flag only adds statements:
+// all present, the tactile table null, gives the bits of the plain instance.
+template <bool AVAIL>
+__global__ __launch_bounds__(256) void elbo_assemble_weighted_kernel(
+    std::conditional_t<AVAIL, double, const double>* __restrict__ bce, std::conditional_t<AVAIL, double, const double>* __restrict__ mse,
+    const double* __restrict__ kl_rows, const double* __restrict__ kl_sum, const float* __restrict__ w, float* __restrict__ loss,
+    float* __restrict__ wpartials, float* __restrict__ out, float* __restrict__ partials, float* __restrict__ w_sum_out,
+    double* __restrict__ bce_t, const uint32_t* __restrict__ tavail, double* __restrict__ present, double* __restrict__ term_sums, int P,
+    int B, float kl_weight_arg, float pose_multiplier, const float* __restrict__ kl_weight_dev, int kl_mode) {
   constexpr int PM = MMDYN_MAX_PASSES;
+  constexpr int NT = 3;                  // terms with a target of their own: visual BCE, tactile BCE, pose MSE
   const float kl_weight = kl_weight_dev ? kl_weight_arg * kl_weight_dev[0] : kl_weight_arg;
   const int tid = threadIdx.x;
   double S[PM], K[PM], W = 0.0;
+  double T[AVAIL ? NT * PM : 1], C[AVAIL ? NT : 1];
 #pragma unroll
   for (int p = 0; p < PM; ++p) S[p] = K[p] = 0.0;
+  if constexpr (AVAIL) {
+#pragma unroll
+    for (int i = 0; i < NT * PM; ++i) T[i] = 0.0;
+#pragma unroll
+    for (int m = 0; m < NT; ++m) C[m] = 0.0;
+  }
   for (int b = tid; b < B; b += 256) {
-    const double wb = (double)w[b];
+    const double wb = (!AVAIL || w) ? (double)w[b] : 1.0;
+    uint32_t word = ALL_PRESENT;
+    if constexpr (AVAIL) {
+      if (tavail) word = tavail[b];
+#pragma unroll
+      for (int m = 0; m < NT; ++m) C[m] += has(word, m) ? 1.0 : 0.0;
+    }
     W += wb;
     double tot = 0.0;
 #pragma unroll
     for (int p = 0; p < PM; ++p) {
       if (p < P) {
         const size_t o = (size_t)p * B + b;
-        const double rec = (bce ? bce[o] : 0.0) + (double)pose_multiplier * (mse ? mse[o] : 0.0);
+        double bs = bce ? bce[o] : 0.0, ms = mse ? mse[o] : 0.0;
+        if constexpr (AVAIL) {
+          double bt = bce_t ? bce_t[o] : 0.0;
+          if (!has(word, 0)) {           // (selections: what the entry of an absent target held reaches nothing)
+            bs = 0.0;
+            if (bce) bce[o] = 0.0;
+          }
+          if (!has(word, 1)) {
+            bt = 0.0;
+            if (bce_t) bce_t[o] = 0.0;
+          }
+          if (!has(word, 2)) {
+            ms = 0.0;
+            if (mse) mse[o] = 0.0;
+          }
+          T[0 * PM + p] += bs;
+          T[1 * PM + p] += bt;
+          T[2 * PM + p] += ms;
+          bs = bs + bt;
+        }
+        const double rec = bs + (double)pose_multiplier * ms;
         const double klr = kl_rows ? kl_rows[o] : 0.0;
         const double kl = kl_mode ? klr : (kl_sum ? kl_sum[p] : 0.0);
         const double v = rec + (double)kl_weight * kl;
@@ -334,7 +374,7 @@ __global__ __launch_bounds__(256) void elbo_assemble_weighted_kernel(const doubl
     }
     if (out) out[b] = (float)tot;
   }
-  __shared__ double red[2 * PM + 1][4];
+  __shared__ double red[2 * PM + 1 + (AVAIL ? NT * PM + NT : 0)][4];
   const int wv = tid >> 6;
 #pragma unroll
   for (int p = 0; p < PM; ++p) {
@@ -346,6 +386,18 @@ __global__ __launch_bounds__(256) void elbo_assemble_weighted_kernel(const doubl
   }
   W = wave_sum_d(W);
   if ((tid & 63) == 0) red[2 * PM][wv] = W;
+  if constexpr (AVAIL) {
+#pragma unroll
+    for (int i = 0; i < NT * PM; ++i) {
+      const double t = wave_sum_d(T[i]);
+      if ((tid & 63) == 0) red[2 * PM + 1 + i][wv] = t;
+    }
+#pragma unroll
+    for (int m = 0; m < NT; ++m) {
+      const double c = wave_sum_d(C[m]);
+      if ((tid & 63) == 0) red[2 * PM + 1 + NT * PM + m][wv] = c;
+    }
+  }
   __syncthreads();
   const double Wt = red[2 * PM][0] + red[2 * PM][1] + red[2 * PM][2] + red[2 * PM][3];
   if (tid == 0) {
@@ -360,8 +412,32 @@ __global__ __launch_bounds__(256) void elbo_assemble_weighted_kernel(const doubl
     }
     loss[0] = (float)tot;
   }
+  if constexpr (AVAIL) {
+    if (tid < NT * PM && term_sums) {                      // term_sums [NT][P]
+      const int m = tid / PM, p = tid - m * PM;
+      const double* r = red[2 * PM + 1 + tid];
+      if (p < P) term_sums[m * P + p] = r[0] + r[1] + r[2] + r[3];
+    }
+    if (tid >= 64 && tid < 64 + NT && present) {
+      const double* r = red[2 * PM + 1 + NT * PM + (tid - 64)];
+      present[tid - 64] = r[0] + r[1] + r[2] + r[3];
+    }
+  }
   if (w_sum_out)
     for (int b = tid; b < B; b += 256) w_sum_out[b] = (float)Wt;
+}
+
+// w_term[m][b] = present(b, m) ? (w ? w[b] : 1) : 0 for the three target modalities (visual, tactile, pose): the weight vectors of
+// the three gradient seeds of a mixed batch.  A select, never a product: the weight of an absent row (it may be NaN) reaches nothing.
+// One 32-bit word per row, coalesced.
+__global__ __launch_bounds__(256) void term_weights_kernel(const uint32_t* __restrict__ tavail, const float* __restrict__ w,
+                                                           float* __restrict__ w_term, int B) {
+  for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
+    const uint32_t word = tavail ? tavail[b] : ALL_PRESENT;
+    const float wb = w ? w[b] : 1.f;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) w_term[(size_t)m * B + b] = has(word, m) ? wb : 0.f;
+  }
 }
 
 // log_w[k][b] = -(bce[0][k][b] + bce[1][k][b] + pose_multiplier * mse[k][b]) - kl_weight * ratio[k][b] over the terms whose target the
@@ -622,8 +698,30 @@ extern "C" int mmdyn_elbo_assemble_weighted(const double* bce_rows, const double
                                             const float* kl_weight_dev, int kl_mode, void* stream) {
   if (!w || !loss) return MMDYN_ERR_NULL;
   if (P <= 0 || P > MMDYN_MAX_PASSES || B <= 0 || (kl_mode != 0 && kl_mode != 1)) return MMDYN_ERR_SHAPE;
-  hipLaunchKernelGGL(elbo_assemble_weighted_kernel, dim3(1), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows, kl_sum, w, loss, wpartials,
-                     out, partials, w_sum_out, P, B, kl_weight, pose_multiplier, kl_weight_dev, kl_mode);
+  hipLaunchKernelGGL(elbo_assemble_weighted_kernel<false>, dim3(1), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows, kl_sum, w, loss,
+                     wpartials, out, partials, w_sum_out, (double*)nullptr, (const uint32_t*)nullptr, (double*)nullptr,
+                     (double*)nullptr, P, B, kl_weight, pose_multiplier, kl_weight_dev, kl_mode);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_elbo_assemble_avail_weighted(double* bce_v_rows, double* bce_t_rows, double* mse_rows, const double* kl_rows,
+                                                  const double* kl_sum, const float* w, const uint8_t* tavail, float* loss,
+                                                  float* wpartials, float* out, float* partials, float* w_sum_out, double* present,
+                                                  double* term_sums, int P, int B, float kl_weight, float pose_multiplier,
+                                                  const float* kl_weight_dev, int kl_mode, void* stream) {
+  if (!loss) return MMDYN_ERR_NULL;
+  if (P <= 0 || P > MMDYN_MAX_PASSES || B <= 0 || (kl_mode != 0 && kl_mode != 1) || ((uintptr_t)tavail & 3)) return MMDYN_ERR_SHAPE;
+  if (bce_v_rows && bce_v_rows == bce_t_rows) return MMDYN_ERR_SHAPE;      // (one table per term: a shared one would count twice)
+  hipLaunchKernelGGL(elbo_assemble_weighted_kernel<true>, dim3(1), dim3(256), 0, ST, bce_v_rows, mse_rows, kl_rows, kl_sum, w, loss,
+                     wpartials, out, partials, w_sum_out, bce_t_rows, reinterpret_cast<const uint32_t*>(tavail), present, term_sums, P,
+                     B, kl_weight, pose_multiplier, kl_weight_dev, kl_mode);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_term_weights(const uint8_t* tavail, const float* w, float* w_term, int B, void* stream) {
+  if (!w_term) return MMDYN_ERR_NULL;
+  if (B <= 0 || ((uintptr_t)tavail & 3)) return MMDYN_ERR_SHAPE;
+  hipLaunchKernelGGL(term_weights_kernel, dim3(ew_grid(B)), dim3(256), 0, ST, reinterpret_cast<const uint32_t*>(tavail), w, w_term, B);
   MMDYN_LAUNCH_CHECK();
 }
 

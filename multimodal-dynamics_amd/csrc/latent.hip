@@ -7,7 +7,9 @@
 //     wave-uniform.  WEIGHTED (backward) -- the KL scale of row b is kl_scale * w_kl[b] (the gradient of the weighted per-sample
 //     ELBO, (1/B) sum_b w_b * row_b); dz arrives already weighted through the decoders and is not scaled again.  The flags only
 //     add statements, so every instance evaluates the same expressions in the same order: all rows present, or w = 1
-//     (x * 1.f == x), give the bits of the plain instance;
+//     (x * 1.f == x), give the bits of the plain instance.  Both flags together are the backward of the training step on a mixed
+//     batch (mmdyn_poe_bwd_avail_weighted).  With L % 64 != 0 a wavefront spans rows and the per-expert branches diverge: every
+//     statement inside them is per-lane (no cross-lane operation sits in the row loop), so each lane follows its own row's word;
 //   - reparametrisation alone (z = eps * exp(lv/2) + mu and/or KL), forward and backward (WEIGHTED as above);
 //   - kl_rows: one KL value per SAMPLE (the reduce=False branch of problems.py:401-458), one wavefront per row;
 //   - iw_latent: the K draws of the importance-weighted bound (Burda et al., "Importance Weighted Autoencoders") from ONE encoder
@@ -354,6 +356,19 @@ extern "C" int mmdyn_poe_bwd_weighted(const mmdyn_pass_experts* passes, const fl
   PoeArgs<false> a{};
   if (int e = copy_passes(passes, nullptr, with_prior, P, B > 0 && L > 0, true, eps_noise, &a)) return e;
   hipLaunchKernelGGL((poe_bwd_kernel<false, true>), dim3(latent_gx(B, L), P), dim3(256), 0, ST, a, eps_noise, mu, logvar, dz, g_mu,
+                     g_lv, kl_scale, kl_weight_dev, w_kl, with_prior, B, L);
+  MMDYN_LAUNCH_CHECK();
+}
+
+/* both flags: the tables of mmdyn_poe_bwd_avail and the row weights of mmdyn_poe_bwd_weighted (the training step on a mixed batch) */
+extern "C" int mmdyn_poe_bwd_avail_weighted(const mmdyn_pass_experts* passes, const uint8_t* const* avail, const float* eps_noise,
+                                            const float* mu, const float* logvar, const float* dz, const float* g_mu,
+                                            const float* g_lv, float kl_scale, const float* w_kl, int with_prior, int P, int B, int L,
+                                            const float* kl_weight_dev, void* stream) {
+  if (!mu || !logvar || !w_kl || (dz && !eps_noise)) return MMDYN_ERR_NULL;
+  PoeArgs<true> a{};
+  if (int e = copy_passes(passes, avail, with_prior, P, B > 0 && L > 0, true, eps_noise, &a)) return e;
+  hipLaunchKernelGGL((poe_bwd_kernel<true, true>), dim3(latent_gx(B, L), P), dim3(256), 0, ST, a, eps_noise, mu, logvar, dz, g_mu,
                      g_lv, kl_scale, kl_weight_dev, w_kl, with_prior, B, L);
   MMDYN_LAUNCH_CHECK();
 }

@@ -155,6 +155,9 @@ _SIGNATURES = {
     "mmdyn_poe_bwd_weighted": "ppppppp" + "f" + "p" + "iiii" + "pp",
     "mmdyn_reparam_bwd_weighted": "pppp" + "f" + "ppp" + "iii" + "p",
     "mmdyn_elbo_assemble_weighted": "pppppppppp" + "ii" + "ff" + "p" + "i" + "p",
+    "mmdyn_poe_bwd_avail_weighted": "pppppppp" + "f" + "p" + "iiii" + "pp",
+    "mmdyn_term_weights": "ppp" + "i" + "p",
+    "mmdyn_elbo_assemble_avail_weighted": "pppppppppppppp" + "ii" + "ff" + "p" + "i" + "p",
     "mmdyn_iw_latent": "pp" + "i" + "ppp" + "iii" + "p",
     "mmdyn_iw_assemble_rows": "ppppppp" + "iii" + "ff" + "pp",
     "mmdyn_rollout_feed": "p" + "i" + "p" + "i" + "p",

@@ -233,6 +233,25 @@ def _with_precision(fn):
     return wrapped
 
 
+class _AvailTables:
+    """The two availability tables of a mixed-modality step as the kernels take them (uint8 [B][4], models.functional.
+    availability_table): ``inp`` -- which experts a row's posterior holds; ``tgt`` -- which reconstruction terms of a row count
+    (the same tensor as ``inp`` when no target table was given).  Either may be None: every row holds everything."""
+    __slots__ = ("inp", "tgt")
+
+    def __init__(self, inp, tgt):
+        self.inp, self.tgt = inp, tgt
+
+    def clone(self):
+        inp = None if self.inp is None else self.inp.clone()
+        return _AvailTables(inp, inp if self.tgt is self.inp else self.tgt.clone())
+
+    def pairs(self, src):
+        """(dst, src) copies that move the contents of ``src`` (tables of the same presence) into these."""
+        out = [] if self.inp is None else [(self.inp, src.inp)]
+        return out + ([(self.tgt, src.tgt)] if (self.tgt is not None and self.tgt is not self.inp) else [])
+
+
 class MVAEStep:
     """Fused train / eval step for an :class:`mmdyn_hip.models.MVAE` on one GPU (one rank)."""
 
@@ -461,8 +480,28 @@ class MVAEStep:
             ops.backend_op(name)         # a backend without the weighted ops: an error before anything is launched
         return sample_weight.detach().reshape(B).to(device=self.params.flat.device, dtype=torch.float32).contiguous()
 
-    def _begin(self, inputs, targets, kl_weight, train, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
+    def _check_avail(self, available, target_available, B):
+        """The availability tables of a mixed-modality step in the form the kernels take (:class:`_AvailTables` of uint8 [B][4] tables
+        on the step's device), or None when neither is given.  Shapes and dtypes are checked, contents never looked at."""
+        if isinstance(available, _AvailTables):
+            return available                     # (the captured step's static tables, checked when they were made)
+        if available is None and target_available is None:
+            return None
+        if self.pg is not None:
+            raise ValueError("available / target_available with a process group is not built: data-parallel training on "
+                             "mixed-modality batches is out of scope")
+        from .models.functional import availability_table
+        dev = self.params.flat.device
+        inp = None if available is None else availability_table(available, B, dev)
+        tgt = inp if target_available is None else availability_table(target_available, B, dev)
+        for name in ("bce_logits_rows_groups_grad", "mse_rows_groups_grad", "poe_fwd_avail", "poe_bwd_avail_weighted", "term_weights",
+                     "elbo_assemble_avail_weighted"):
+            ops.backend_op(name)         # a backend without these ops: an error before anything is launched
+        return _AvailTables(inp, tgt)
+
+    def _begin(self, inputs, targets, kl_weight, train, loss_mask=None, condition=None, sample_weight=None, kl="batch", avail=None):
         sample_weight = self._check_weights(sample_weight, kl, inputs[0].shape[0])
+        avail = self._check_avail(avail, None, inputs[0].shape[0])
         self._set_kl_weight(kl_weight)
         if self.conditional:
             from .models.vae import _condition
@@ -499,7 +538,11 @@ class MVAEStep:
                     "rows": None,                 # score_step: fp64 [4][P][B] per-sample bce / mse / kl / unmasked-bce tables
                     # per-sample weights (fp32 [B]) of the training loss and the KL mode: the row tables are then allocated by the
                     # pre-phase, the three gradient seeds take weight vectors, the assembly is the weighted one
-                    "w": sample_weight, "kl_mode": 1 if kl == "sample" else 0, "w_kl": None}
+                    "w": sample_weight, "kl_mode": 1 if kl == "sample" else 0, "w_kl": None,
+                    # a mixed-modality step (_AvailTables or None): it takes the row-table path too, with one table and one seed
+                    # weight vector per TERM -- "wt" (visual, tactile, pose), written by the pre-phase's term-weight launch
+                    "avail": avail, "row_path": sample_weight is not None or avail is not None,
+                    "wt": {"v": sample_weight, "t": sample_weight, "p": sample_weight}}
 
     def _passes_of(self, m):
         return self.pass_v if m == "v" else self.pass_t
@@ -520,7 +563,15 @@ class MVAEStep:
         c["mask"] = {"v": mv, "t": mt}
         LN.join()
         self.acc.zero_()
-        if c["w"] is not None:                    # (inside the captured region: a replay starts from cleared tables)
+        if c["avail"] is not None:
+            # bce (visual) / mse / kl / unmasked bce (visual) as below, then the tactile term's bce and unmasked bce: the two image
+            # decoders do not add into one table, the assembly selects per (row, term)
+            c["rows"] = torch.zeros(6, self.P, c["B"], dtype=torch.float64, device=c["dev"])
+            if c["train"]:
+                wt = torch.empty(3, c["B"], device=c["dev"])
+                ops.B.term_weights(c["avail"].tgt, c["w"], wt, c["B"])
+                c["wt"] = {"v": wt[0], "t": wt[1], "p": wt[2]}
+        elif c["w"] is not None:                  # (inside the captured region: a replay starts from cleared tables)
             c["rows"] = torch.zeros(4, self.P, c["B"], dtype=torch.float64, device=c["dev"])
         if self._bad_index is not None:
             self._bad_index.zero_()
@@ -615,7 +666,10 @@ class MVAEStep:
             d["zdst"] = [c["zz" + m][pl.index(p) * B:(pl.index(p) + 1) * B] if p in pl else None for m, pl in lists.items()]
             d["zpl"] = [zpl[m].t.data_ptr() + lists[m].index(p) * B * 3 * L * 2 if (zpl.get(m) is not None and p in lists[m]) else None
                         for m in ("v", "t")]
-        ops.B.poe_fwd(passes, c["eps"], c["mu"], c["lv"], c["z"], self.acc[2], True, P, B, L)
+        if c["avail"] is not None:     # the SAME input table for every pass: the pass's subset is in its null pointers, as always
+            ops.B.poe_fwd_avail(passes, [c["avail"].inp] * P, c["eps"], c["mu"], c["lv"], c["z"], self.acc[2], True, P, B, L)
+        else:
+            ops.B.poe_fwd(passes, c["eps"], c["mu"], c["lv"], c["z"], self.acc[2], True, P, B, L)
         if c["rows"] is not None:
             ops.B.kl_rows(c["mu"], c["lv"], c["rows"][2], P, B, L)
 
@@ -636,8 +690,11 @@ class MVAEStep:
                     keep=None if self.keep_logits else plist.index(joint), mask=mk,
                     mask_channels=1 if mk is None else mk.shape[1], acc_u=None if mk is None else self.acc[3])
         rows = c["rows"]
+        # (a mixed-modality step: the tactile term has tables of its own, and each term its own seed weights)
+        kb, ku = (4, 5) if (c["avail"] is not None and m == "t") else (0, 3)
+        wrec = c["wt"][m]
         if rows is not None:
-            spec.update(rows=rows[0], rows_u=None if mk is None else rows[3], weights=c["w"])
+            spec.update(rows=rows[kb], rows_u=None if mk is None else rows[ku], weights=wrec)
         lg, c["d" + m] = yield from layers.decoder_forward_steps(FP.sub(dec), self._buffers(dec), zz, len(plist),
                                                                  packed=c["pk"].get("d" + m), cond=cond, loss=spec if FUSED_BCE else None,
                                                                  z_planes=c.get("zzpl" + m))
@@ -646,17 +703,17 @@ class MVAEStep:
             c["lg_joint_only" + m] = not self.keep_logits
             return
         c["lg_joint_only" + m] = False
-        if rows is not None and c["w"] is not None and c["train"]:
+        if rows is not None and wrec is not None and c["train"]:
             dl = torch.empty_like(lg)
-            ops.B.bce_logits_rows_groups_grad(lg, tg, dl, c["w"], rows[0], slots, B, tg[0].numel(), self.loss_scale / B, mask=mk,
+            ops.B.bce_logits_rows_groups_grad(lg, tg, dl, wrec, rows[kb], slots, B, tg[0].numel(), self.loss_scale / B, mask=mk,
                                               hw=tg[0, 0].numel(), mask_channels=1 if mk is None else mk.shape[1],
-                                              unmasked_rows=None if mk is None else rows[3])
+                                              unmasked_rows=None if mk is None else rows[ku])
             c["lg" + m], c["dl" + m] = lg, dl
             return
         if rows is not None:
-            ops.B.bce_logits_rows_groups(lg, tg, rows[0], slots, B, tg[0].numel(), mask=mk, hw=tg[0, 0].numel(),
+            ops.B.bce_logits_rows_groups(lg, tg, rows[kb], slots, B, tg[0].numel(), mask=mk, hw=tg[0, 0].numel(),
                                          mask_channels=1 if mk is None else mk.shape[1],
-                                         unmasked_rows=None if mk is None else rows[3])
+                                         unmasked_rows=None if mk is None else rows[ku])
             c["lg" + m], c["dl" + m] = lg, None
             return
         dl = torch.empty_like(lg) if c["train"] else None
@@ -676,8 +733,8 @@ class MVAEStep:
             pr, c["dp"] = layers.pose_decoder_forward(FP.sub("pose_decoder"), zp)
             dpr = torch.empty_like(pr) if c["train"] else None
             # every pose-bearing pass against the same target: one launch, one loss slot per pass
-            if c["rows"] is not None and c["w"] is not None and c["train"]:
-                ops.B.mse_rows_groups_grad(pr, c["pose_tg"], dpr, c["w"], c["rows"][1], list(self.pass_p), B, 7,
+            if c["rows"] is not None and c["wt"]["p"] is not None and c["train"]:
+                ops.B.mse_rows_groups_grad(pr, c["pose_tg"], dpr, c["wt"]["p"], c["rows"][1], list(self.pass_p), B, 7,
                                            self.loss_scale * self.pose_multiplier / B)
             elif c["rows"] is not None:
                 ops.B.mse_rows_groups(pr, c["pose_tg"], c["rows"][1], list(self.pass_p), B, 7)
@@ -688,6 +745,8 @@ class MVAEStep:
 
     def _ph_assemble(self):
         c = self.ctx
+        if c["avail"] is not None:
+            return self._assemble_avail()
         if c["rows"] is not None:
             # the per-pass sums eval_step would have produced are the sums of the rows (no second run of the scalar kernels)
             for k, used in ((0, True), (1, self.use_pose), (3, c["lmask"] is not None)):
@@ -709,6 +768,38 @@ class MVAEStep:
             return
         ops.B.elbo_assemble(self.acc[0], self.acc[1], self.acc[2], self.loss, self.partials, self.P, c["B"],
                             1.0, self.pose_multiplier, self.klw)
+
+    def _assemble_avail(self):
+        """The loss of a mixed-modality step: a (row, term) whose target is absent is selected out of the per-term tables (and
+        written back as 0), the KL counts for every row, the division stays by B; ``self.acc`` is then formed from the filtered
+        tables, so the performance measures see present targets only."""
+        c, B, P, tab, dev = self.ctx, self.ctx["B"], self.P, self.ctx["rows"], self.ctx["dev"]
+        tgt, mk = c["avail"].tgt, c["lmask"]
+        out, partials = torch.empty(B, device=dev), torch.empty(P, B, device=dev)
+        present, sums = torch.empty(3, dtype=torch.float64, device=dev), torch.empty(3, P, dtype=torch.float64, device=dev)
+        # the KL seed's row weights: kl="sample" the weights themselves (ones without), kl="batch" sum_b w_b in every row
+        if c["kl_mode"]:
+            c["w_kl"] = c["w"] if c["w"] is not None else torch.ones(B, device=dev)
+        else:
+            c["w_kl"] = torch.empty(B, device=dev)
+        ops.B.elbo_assemble_avail_weighted(tab[0], tab[4], tab[1] if self.use_pose else None, tab[2], self.acc[2], c["w"], tgt,
+                                           self.loss, self.partials, out, partials, None if c["kl_mode"] else c["w_kl"], present,
+                                           sums, P, B, 1.0, self.pose_multiplier, self.klw, c["kl_mode"])
+        torch.add(sums[0], sums[1], out=self.acc[0][:P])
+        self.acc[1][:P].copy_(sums[2])
+        unmasked = None
+        if mk is not None:               # (--mask-loss: the plain sums beside the masked ones, selected the same way)
+            for k, col in ((3, 0), (5, 1)):
+                if tgt is not None:
+                    tab[k].copy_(torch.where(tgt[:, col] != 0, tab[k], torch.zeros_like(tab[k])))
+            unmasked = tab[3] + tab[5]
+            torch.sum(unmasked, 1, out=self.acc[3][:P])
+        self.last_rows = {"rows": out, "partials": partials, "bce_rows": tab[0] + tab[4], "mse_rows": tab[1], "kl_rows": tab[2],
+                          "unmasked_bce_rows": unmasked, "kl": "sample" if c["kl_mode"] else "batch",
+                          # per term (visual, tactile, pose): the tables, the number of rows that hold each target, and each
+                          # term's per-pass sum over those rows
+                          "bce_v_rows": tab[0], "bce_t_rows": tab[4], "present": present, "term_sums": sums,
+                          "unmasked_bce_v_rows": None if mk is None else tab[3], "unmasked_bce_t_rows": None if mk is None else tab[5]}
 
     def _ph_dec_bwd_steps(self, m):
         c, FP = self.ctx, self.params
@@ -766,6 +857,10 @@ class MVAEStep:
         else:
             c["dov"], c["dot"] = torch.empty_like(c["ov"]), torch.empty_like(c["ot"])
             c["dop"] = torch.empty_like(c["op"]) if self.use_pose else None
+        if c["avail"] is not None:
+            ops.B.poe_bwd_avail_weighted(self._passes(c, B, [c["dov"], c["dot"], c["dop"]], blocks), [c["avail"].inp] * P, c["eps"],
+                                         c["mu"], c["lv"], None, None, None, self.loss_scale / B, c["w_kl"], True, P, B, L, self.klw)
+            return
         if c["w"] is not None:
             ops.B.poe_bwd_weighted(self._passes(c, B, [c["dov"], c["dot"], c["dop"]], blocks), c["eps"], c["mu"], c["lv"], None,
                                    None, None, self.loss_scale / B, c["w_kl"], True, P, B, L, self.klw)
@@ -825,7 +920,7 @@ class MVAEStep:
     # ------------------------------------------------------------------------------------------
     @_with_precision
     def forward(self, inputs, targets, kl_weight, train=True, loss_mask=None, condition=None, rows=False, sample_weight=None,
-                kl="batch"):
+                kl="batch", available=None, target_available=None):
         """Runs the forward schedule and the loss; with train=True also fills the loss gradients needed by
         :meth:`backward`.  Returns the device scalar loss (fp32).  ``loss_mask`` ([B][1 or C][H][W], models without pose):
         the reference's --mask-loss, multiplying logits and targets of every image term.  ``condition``: the condition of the
@@ -839,15 +934,29 @@ class MVAEStep:
         gradient seeds of :meth:`backward` (BCE, MSE, KL) are scaled per sample.  ``self.partials`` holds the weighted per-pass
         parts, ``self.last_rows`` the unweighted per-sample tables (``rows``, ``partials``, ``bce_rows``, ``mse_rows``,
         ``kl_rows``) as a by-product.  BatchNorm statistics are those of the UNWEIGHTED batch, as in the reference's autograd: a
-        zero weight does not remove a sample from them.  Weights are not inspected (NaN / Inf propagate)."""
-        self._begin(inputs, targets, kl_weight, train, loss_mask, condition, sample_weight, kl)
+        zero weight does not remove a sample from them.  Weights are not inspected (NaN / Inf propagate).
+
+        ``available`` / ``target_available`` (None: every row holds everything, on exactly the launches above): a mixed-modality
+        batch.  Tables in the forms ``models.functional.availability_table`` takes -- [B, 2] (visual, tactile; the pose counts as
+        present) or [B, 3], any numeric dtype, non-zero = present, never inspected on the host.  ``available``: the posterior of
+        row b in every subset pass is the prior times the pass's experts that the row holds (none: the prior alone).
+        ``target_available`` (default: ``available``): the reconstruction term of modality m for row b counts iff the row holds
+        that target; the KL counts for every row, and the loss stays divided by B:
+        L = (1/B) sum_s sum_b w_b [ sum_{m in s, target present} rec_m(s, b) + kl_weight KL(s, b) ].  ``sample_weight`` composes
+        (an absent term's weight is 0, by selection).  All B rows pass through every encoder and decoder and take part in the
+        BatchNorm statistics, so the tensors of an absent (row, modality) must be FINITE in training (the dataset's constant image
+        is); only the product of experts never loads them.  An absent target sends no gradient into its decoder, an absent
+        (row, expert) gets exact-zero head-gradient rows.  ``self.last_rows`` then also holds ``bce_v_rows`` / ``bce_t_rows`` (the
+        per-term tables, absent entries 0), ``present`` (fp64 [3]: rows that hold each target) and ``term_sums`` (fp64 [3][P])."""
+        avail = self._check_avail(available, target_available, inputs[0].shape[0])
+        self._begin(inputs, targets, kl_weight, train, loss_mask, condition, sample_weight, kl, avail)
         with layers.bad_index_into(self._bad_index):
             return self._forward_schedule(rows, train)
 
     def _forward_schedule(self, rows, train):
         LN = self.lanes
         if rows:
-            if train or self.ctx["w"] is not None:
+            if train or self.ctx["row_path"]:
                 raise ValueError("rows=True is the evaluation schedule of score_step; a training step with per-sample rows takes "
                                  "sample_weight (its rows are in self.last_rows)")
             self.ctx["rows"] = torch.zeros(4, self.P, self.ctx["B"], dtype=torch.float64, device=self.ctx["dev"])
@@ -957,18 +1066,21 @@ class MVAEStep:
         return int(self.adam_state[4])
 
     @_with_precision
-    def train_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
+    def train_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch", available=None,
+                   target_available=None):
         """zero_grad -> forward -> backward -> (all-reduce) -> Adam, as problems.py:150-155.  Gradients are
-        overwritten, not accumulated, so no zero_grad pass is needed.  ``sample_weight`` / ``kl``: see :meth:`forward`."""
+        overwritten, not accumulated, so no zero_grad pass is needed.  ``sample_weight`` / ``kl`` / ``available`` /
+        ``target_available``: see :meth:`forward`."""
         loss = self.forward(inputs, targets, kl_weight, train=True, loss_mask=loss_mask, condition=condition,
-                            sample_weight=sample_weight, kl=kl)
+                            sample_weight=sample_weight, kl=kl, available=available, target_available=target_available)
         handles = self.backward()
         self.optimizer_step(handles)
         return loss
 
     # ------------------------------------------------------------------------------------------
     @_with_precision
-    def train_step_graphed(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
+    def train_step_graphed(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch",
+                           available=None, target_available=None):
         """Same as :meth:`train_step`, replayed from HIP graphs: the ~300 kernel launches of a step are captured
         once per batch shape (the KL weight is read from device memory).  Each phase is its OWN graph: the visual and the tactile phases are
         linear kernel chains that are launched concurrently on two streams (a single graph with parallel branches
@@ -977,13 +1089,18 @@ class MVAEStep:
         Inputs are copied into static buffers; random draws advance through a device-side counter and Adam's step
         count lives on the device, so every replay is a real optimiser step.  With more than one rank the gradient
         all-reduce and Adam run after the graphs.  ``sample_weight`` / ``kl`` (see :meth:`forward`): the weights are one more static
-        input; the capture key carries "weighted" and the KL mode, so one captured step serves every weight vector of a shape."""
+        input; the capture key carries "weighted" and the KL mode, so one captured step serves every weight vector of a shape.
+        ``available`` / ``target_available``: the two tables are static inputs as well; the key carries which of them were given
+        (and the KL mode), never their contents -- one capture serves every mixture of a batch shape, a replay copies the tables in."""
         sample_weight = self._check_weights(sample_weight, kl, inputs[0].shape[0])
+        avail = self._check_avail(available, target_available, inputs[0].shape[0])
         if self._sync is not None and not self._sync_graph_ok:
-            return self.train_step(inputs, targets, kl_weight, loss_mask, condition, sample_weight, kl)      # (gloo: collectives cannot be captured)
+            return self.train_step(inputs, targets, kl_weight, loss_mask, condition, sample_weight, kl, avail)      # (gloo: collectives cannot be captured)
         key = tuple(tuple(x.shape) for x in inputs) + ((tuple(loss_mask.shape),) if loss_mask is not None else ())
         if sample_weight is not None:
             key += (("weighted", kl),)
+        if avail is not None:
+            key += (("avail", kl, avail.inp is not None, avail.tgt is not avail.inp),)
         if condition is not None:
             from .models.vae import _condition
             condition = _condition(condition, True, self.categorical)
@@ -995,6 +1112,7 @@ class MVAEStep:
             self._static_mask = None if loss_mask is None else loss_mask.to(torch.float32).clone()
             self._static_cond = None if condition is None else condition.clone()
             self._static_w, self._static_kl = None if sample_weight is None else sample_weight.clone(), kl
+            self._static_avail = None if avail is None else avail.clone()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             if self._sync is not None:
@@ -1004,7 +1122,7 @@ class MVAEStep:
             try:
                 with torch.cuda.stream(side):                  # warm-up outside capture (allocator, lazy init)
                     self.train_step(self._static_in, self._static_tg, kl_weight, self._static_mask, self._static_cond,
-                                    self._static_w, kl)
+                                    self._static_w, kl, self._static_avail)
                 torch.cuda.current_stream().wait_stream(side)
                 if self.pg is not None:
                     self._drain_before_capture(key)
@@ -1017,7 +1135,7 @@ class MVAEStep:
             mark = getattr(ops.B, "ticket_mark", None)
             if mark is not None:
                 mark()
-            warm_rows = self.last_rows if sample_weight is not None else None
+            warm_rows = self.last_rows if (sample_weight is not None or avail is not None) else None
             try:
                 captured = self._capture(kl_weight)
             except BaseException:
@@ -1047,6 +1165,8 @@ class MVAEStep:
             moves.append((self._static_cond, condition))
         if sample_weight is not None:
             moves.append((self._static_w, sample_weight))
+        if avail is not None:
+            moves += self._static_avail.pairs(avail)
         if COPY_MANY and all(d.dtype == s_.dtype and s_.is_cuda and s_.is_contiguous() for d, s_ in moves):
             ops.B.copy_many(moves)
         else:                        # (a batch that arrives in another type / layout / on the host: the runtime's converting copy)
@@ -1192,7 +1312,7 @@ class MVAEStep:
         bad_scope.__enter__()
         try:
             self._begin(self._static_in, self._static_tg, kl_weight, True, self._static_mask, self._static_cond,
-                        getattr(self, "_static_w", None), getattr(self, "_static_kl", "batch"))
+                        getattr(self, "_static_w", None), getattr(self, "_static_kl", "batch"), getattr(self, "_static_avail", None))
             for stage in stages:
                 row = []
                 for lane, fn in stage:
@@ -1290,10 +1410,12 @@ class MVAEStep:
 
     @torch.no_grad()
     @_with_precision
-    def eval_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch"):
-        """``sample_weight`` / ``kl``: the weighted loss of :meth:`forward` without gradients (rows in ``self.last_rows``)."""
+    def eval_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch", available=None,
+                  target_available=None):
+        """``sample_weight`` / ``kl`` / ``available`` / ``target_available``: the loss of :meth:`forward` without gradients (rows in
+        ``self.last_rows``)."""
         loss = self.forward(inputs, targets, kl_weight, train=False, loss_mask=loss_mask, condition=condition,
-                            sample_weight=sample_weight, kl=kl)
+                            sample_weight=sample_weight, kl=kl, available=available, target_available=target_available)
         self.ctx = None
         return loss
 

@@ -49,6 +49,10 @@ _BUILD_FLAGS = (
     ("exact-running-stats", False, None, "fused step: also run the image decoders on the subset passes whose reconstruction the "
                                          "reference computes and discards, so that the decoders' BatchNorm running statistics "
                                          "get the reference's 7 (3) updates per step instead of 4 (2); ~1.4x the step time"),
+    ("use-availability", False, None, "seq / dyn modeling with cnn-mvae: train and validate on mixed-modality batches -- the dataset's "
+                                      "per-frame availability table selects each row's experts in the posterior and drops the "
+                                      "reconstruction terms of absent targets (default: every frame counts as complete)"),
+    ("synthetic-absent", 0.0, float, "with --synthetic-batches: share of (frame, image modality) pairs marked missing"),
 )
 
 
@@ -69,9 +73,9 @@ def main(argv=None):
     shock = 3 if args.conditional else 0
     if args.synthetic_batches > 0:
         loaders = dict(train_loader=SyntheticVisuoTactile(args.synthetic_batches, args.batchsize, L, seed=1234,
-                                                          shock_dim=shock, size=args.image_size),
+                                                          shock_dim=shock, size=args.image_size, absent=args.synthetic_absent),
                        test_loader=SyntheticVisuoTactile(max(1, args.synthetic_batches // 4), args.batchsize, L,
-                                                         seed=4321, shock_dim=shock, size=args.image_size),
+                                                         seed=4321, shock_dim=shock, size=args.image_size, absent=args.synthetic_absent),
                        seq_length=L, fused=not args.reference_schedule)
     else:
         loaders = dict(fused=not args.reference_schedule)      # Problem.set_dataset reads --dataset-path

@@ -1492,6 +1492,49 @@ class HipBackend:
                                                     float(pose_multiplier), _ptr(kl_weight_dev), int(kl_mode), _stream()),
               "mmdyn_elbo_assemble_weighted")
 
+    # ---- the training step on a mixed-modality batch: input availability in the PoE, target availability in the loss ----
+    def poe_bwd_avail_weighted(self, passes, avail, eps_noise, mu, logvar, dz, g_mu, g_lv, kl_scale, w_kl, with_prior, P, B, L,
+                               kl_weight_dev=None):
+        """poe_bwd with the tables of poe_bwd_avail AND the row weights of poe_bwd_weighted."""
+        name = "poe_bwd_avail_weighted"
+        arr = self._passes(passes)
+        tabs = self._avail_tables(avail, P, B, name, mu)
+        check(self.lib.mmdyn_poe_bwd_avail_weighted(ctypes.cast(arr, ctypes.c_void_p), None if tabs is None else ctypes.addressof(tabs),
+                                                    _ptr(eps_noise), _ptr(mu), _ptr(logvar), _ptr(dz), _ptr(g_mu), _ptr(g_lv),
+                                                    float(kl_scale), self._weights(w_kl, B, name), int(with_prior), P, B, L,
+                                                    _ptr(kl_weight_dev), _stream()), "mmdyn_" + name)
+
+    def term_weights(self, tavail, w, w_term, B):
+        """w_term [3][B] fp32: w_term[m][b] = tavail[b][m] != 0 ? (w[b], or 1 without w) : 0 -- the weight vectors of the visual,
+        tactile and pose gradient seeds.  tavail: uint8 [B][4] or None (every target present); w: fp32 [B] or None."""
+        name = "term_weights"
+        if w_term is None or w_term.dtype != torch.float32 or tuple(w_term.shape) != (3, B) or not w_term.is_contiguous():
+            raise ValueError(f"mmdyn_{name}: w_term must be a contiguous fp32 [3][B={B}] tensor")
+        check(self.lib.mmdyn_term_weights(self._avail(tavail, B, name, w_term), None if w is None else self._weights(w, B, name),
+                                          _ptr(w_term), B, _stream()), "mmdyn_" + name)
+
+    def elbo_assemble_avail_weighted(self, bce_v_rows, bce_t_rows, mse_rows, kl_rows, kl_sum, w, tavail, loss, wpartials, out, partials,
+                                     w_sum_out, present, term_sums, P, B, kl_weight, pose_multiplier, kl_weight_dev=None, kl_mode=0):
+        """elbo_assemble_weighted with one fp64 [P][B] table per term (visual BCE, tactile BCE, pose MSE; any None = 0) and the
+        target-availability table ``tavail`` (uint8 [B][4] or None): an absent (row, term) is selected out of every sum and its table
+        entries are overwritten with 0.  w None = 1.  present fp64 [3] / term_sums fp64 [3][P] (optional): the number of rows that
+        hold each target, and each term's unweighted per-pass sum over them.  Deterministic."""
+        name = "elbo_assemble_avail_weighted"
+        for t, n, what in ((bce_v_rows, P * B, "bce_v_rows"), (bce_t_rows, P * B, "bce_t_rows"), (mse_rows, P * B, "mse_rows"),
+                           (kl_rows, P * B, "kl_rows"), (kl_sum, P, "kl_sum"), (partials, P * B, "partials"), (out, B, "out"),
+                           (wpartials, P, "wpartials"), (w_sum_out, B, "w_sum_out"), (loss, 1, "loss"), (present, 3, "present"),
+                           (term_sums, 3 * P, "term_sums")):
+            if t is not None and t.numel() < n:
+                raise ValueError(f"mmdyn_{name}: {what} holds {t.numel()} elements, needs {n}")
+        f64 = torch.float64
+        check(self.lib.mmdyn_elbo_assemble_avail_weighted(_ptr(bce_v_rows, f64), _ptr(bce_t_rows, f64), _ptr(mse_rows, f64),
+                                                          _ptr(kl_rows, f64), _ptr(kl_sum, f64),
+                                                          None if w is None else self._weights(w, B, name),
+                                                          self._avail(tavail, B, name, loss), _ptr(loss), _ptr(wpartials), _ptr(out),
+                                                          _ptr(partials), _ptr(w_sum_out), _ptr(present, f64), _ptr(term_sums, f64),
+                                                          P, B, float(kl_weight), float(pose_multiplier), _ptr(kl_weight_dev),
+                                                          int(kl_mode), _stream()), "mmdyn_" + name)
+
     def adam_step(self, p, g, m, v, state, lr, beta1, beta2, eps, grad_scale, guarded=False):
         """guarded: ``state`` has six doubles and a gradient holding inf / NaN skips the step (counted in state[4])."""
         if guarded and state.numel() < 6:

@@ -84,22 +84,26 @@ class SyntheticVisuoTactile:
     frames of ``seq_length`` per sequence folded into the batch dimension.  Values are U[0,1) like
     ``ToTensor`` images and min-max normalised poses (datasets.py:23-31, 407-408)."""
 
-    def __init__(self, n_batches, batchsize, seq_length=1, device="cpu", seed=1234, size=64, shock_dim=0):
+    def __init__(self, n_batches, batchsize, seq_length=1, device="cpu", seed=1234, size=64, shock_dim=0, absent=0.0):
+        """``absent`` (default 0: every frame holds both images, the table is all ones): the share of (frame, image modality) pairs
+        marked missing in ``available_modals``, drawn from a generator of its own so that every other tensor stays what it was."""
         self.n_batches, self.batchsize, self.seq_length = n_batches, batchsize, seq_length
         self.device, self.seed, self.size, self.shock_dim = device, seed, size, shock_dim
+        self.absent = float(absent)
 
     def __len__(self):
         return self.n_batches
 
     def __iter__(self):
         g = torch.Generator().manual_seed(self.seed)
+        ga = torch.Generator().manual_seed(self.seed + 1)
         n = self.batchsize * self.seq_length
         for _ in range(self.n_batches):
             def draw():
                 return [torch.rand(n, 3, self.size, self.size, generator=g), torch.rand(n, 3, self.size, self.size, generator=g),
                         torch.rand(n, 7, generator=g)]
             d, t = draw(), draw()
-            d.append(torch.ones(n, 2))
+            d.append((torch.rand(n, 2, generator=ga) >= self.absent).to(torch.float32) if self.absent > 0 else torch.ones(n, 2))
             if self.shock_dim:
                 d.append(torch.rand(n, self.shock_dim, generator=g))      # the shock force (datasets.py:395-404)
             t.append(torch.ones(n, 1, self.size, self.size))
@@ -209,6 +213,7 @@ class Problem:
         perf = defaultdict(float)
         dev_loss = dev_acc = None        # fused path: loss and per-pass sums accumulate ON THE DEVICE, read once per epoch
         dev_n = dev_rows = 0             # (the reference's loss.item() per step, problems.py:156, would stall the replay)
+        dev_perf, dev_perf_n = None, 0   # --use-availability: the per-step means over PRESENT targets, summed on the device
         try:
             n_batches = len(self.train_loader)
         except TypeError:
@@ -229,17 +234,24 @@ class Problem:
                               self.parameters.get('exact_last_step', True))
                 if last_exact:
                     self._step.exact_running_stats, run = True, self._step.train_step
+                avail_kw = self._avail_kw(inputs)
                 try:
                     loss = run(*self._fused_io(inputs, targets), self._kl_weight, loss_mask=self._fused_mask(targets),
-                               condition=inputs.get('shock') if self._conditional else None)
+                               condition=inputs.get('shock') if self._conditional else None,
+                               **(dict(avail_kw, kl="sample") if avail_kw else {}))
                 finally:
                     if last_exact:
                         self._step.exact_running_stats = False
                 if dev_loss is None:
                     dev_loss, dev_acc = torch.zeros_like(loss, dtype=torch.float64), torch.zeros_like(self._step.acc)
                 dev_loss += loss.detach().to(torch.float64)
-                dev_acc += self._step.acc
                 dev_n += 1
+                if avail_kw:
+                    step_perf = self._fused_perf_present_dev()
+                    dev_perf = step_perf if dev_perf is None else dev_perf + step_perf
+                    dev_perf_n += 1
+                    continue
+                dev_acc += self._step.acc
                 dev_rows += self._step.last['means'].shape[0]
                 continue
             else:
@@ -253,8 +265,12 @@ class Problem:
                 perf[k] += v
         if dev_n:
             train_loss += float(dev_loss.sum())
-            for k, v in self._fused_perf(dev_acc.cpu(), dev_rows / dev_n).items():
-                perf[k] += v          # (sums over the epoch's steps / rows per step = the sum of the per-step means)
+            if dev_n > dev_perf_n:
+                for k, v in self._fused_perf(dev_acc.cpu(), dev_rows / (dev_n - dev_perf_n)).items():
+                    perf[k] += v          # (sums over the epoch's steps / rows per step = the sum of the per-step means)
+            if dev_perf is not None:
+                for k, v in self._perf_dict(dev_perf.cpu()).items():
+                    perf[k] += v
             n += dev_n
         self._logger_dict['Loss/train_epoch'].append(train_loss / max(n, 1))
         self._logger_dict['KL_annealing/train_epoch'].append(self._kl_weight)
@@ -270,10 +286,12 @@ class Problem:
             for batch_idx, (data_input, data_target) in enumerate(self.test_loader):
                 inputs, targets = self.parse_input(data_input, data_target)
                 if self._step is not None and self._fused_applicable(inputs):
+                    avail_kw = self._avail_kw(inputs)
                     loss = self._step.eval_step(*self._fused_io(inputs, targets), self._kl_weight,
                                                 loss_mask=self._fused_mask(targets),
-                                                condition=inputs.get('shock') if self._conditional else None)
-                    outputs = {'perf_measure': self._fused_perf()}
+                                                condition=inputs.get('shock') if self._conditional else None,
+                               **(dict(avail_kw, kl="sample") if avail_kw else {}))
+                    outputs = {'perf_measure': self._fused_perf_present() if avail_kw else self._fused_perf()}
                 else:
                     outputs, loss = self._evaluate_model(inputs, targets)
                 val_loss += float(loss)
@@ -390,6 +408,44 @@ class Problem:
         if st.use_pose:
             out['pose'] = float(acc[1, 6]) / (B * 7)
         return out
+
+    # ---- --use-availability: mixed-modality batches ------------------------------------------------------------------------------
+    def _avail_kw(self, inputs):
+        """``{available, target_available}`` of one parsed batch when --use-availability is on and the batch carries the dataset's
+        per-frame table (``input_available_modals``), else ``{}``: the keywords of the fused step and of the module path."""
+        if not self.parameters.get('use_availability') or not isinstance(inputs, dict) \
+                or inputs.get('input_available_modals') is None:
+            return {}
+        has = inputs['input_available_modals']
+        return {"available": has, "target_available": self._target_available(has)}
+
+    def _target_available(self, has):
+        """[B, 3] target availability of a parsed batch (overridden per problem)."""
+        raise NotImplementedError
+
+    def _perf_dict(self, means):
+        out = {'visual': float(means[0]), 'tactile': float(means[1])}
+        if self.parameters['use_pose']:
+            out['pose'] = float(means[2])
+        return out
+
+    def _fused_perf_present_dev(self):
+        """The performance measures of the latest fused step on a mixed batch as a device tensor (fp64 [3]: visual, tactile, pose):
+        the single-modality passes' term sums over the rows whose TARGET is present, divided by that many rows (and the elements of
+        one) -- from the sums and counts the step's loss assembly leaves in ``last_rows``; nothing is read back here."""
+        st = self._step
+        lr = st.last_rows
+        npx = st.last['recon_x'][0][0].numel()
+        if st.last.get('masked'):        # the perf measures are unmasked sums (problems.py:495-505)
+            sums = torch.stack([lr['unmasked_bce_v_rows'][1].sum(), lr['unmasked_bce_t_rows'][2].sum(), lr['term_sums'][2, 0] * 0])
+        else:
+            sums = torch.stack([lr['term_sums'][0, 1], lr['term_sums'][1, 2], lr['term_sums'][2, 6] if st.use_pose else
+                                lr['term_sums'][2, 0] * 0])
+        per = torch.tensor([npx, npx, 7], dtype=torch.float64, device=sums.device)
+        return sums / (lr['present'].clamp(min=1.0) * per)
+
+    def _fused_perf_present(self):
+        return self._perf_dict(self._fused_perf_present_dev().cpu())
 
     @property
     def log_dir(self):
@@ -557,10 +613,51 @@ class Reconstruction(Problem):
         loss = self._criterion(recon_x, x, means, log_var, reduce=reduce, reduction=reduction)
         return {'recon_x': recon_x, 'means': means, 'log_var': log_var}, loss
 
-    def _evaluate_mvae(self, x, targets, loss_mask=None, reduce=None, reduction='sum', condition=None):
+    def _evaluate_mvae_avail(self, x, targets, loss_mask, condition, available, target_available):
+        """The subset schedule on a mixed-modality batch, the semantics of ``MVAEStep.forward(available=, target_available=)``:
+        ``MVAE.forward(available=)`` per subset, the differentiable row functions, and a ``torch.where`` on the target table --
+        L = (1/B) sum_s [ sum_b sum_{m in s, target present} rec_m(s, b) + kl_weight KL(s) ].  The performance measures are means
+        over present targets."""
+        m, dev = self._model, x[0].device
+        B = x[0].shape[0]
+        tgt = Fn.availability_table(available if target_available is None else target_available, B, dev) != 0
+        use_pose = bool(self.parameters['use_pose'])
+        zero = torch.zeros(B, dtype=torch.float64, device=dev)
+        order = [(1, 1, 0), (1, 0, 0), (0, 1, 0)] + ([(1, 1, 1), (1, 0, 1), (0, 1, 1), (0, 0, 1)] if use_pose else [])
+        loss, perf, joint = 0, {}, None
+        for a, b, c in order:
+            out = m([x[0] if a else None, x[1] if b else None], pose=x[2] if c else None, condition=condition, available=available)
+            means, log_var = out[3], out[4]
+            rec = 0
+            for on, r, col, key in ((a, out[0], 0, 'visual'), (b, out[1], 1, 'tactile')):
+                if on:
+                    rows = Fn.BCERowsFn.apply(r.view(targets[col].size()), targets[col], loss_mask)
+                    rec = rec + torch.where(tgt[:, col], rows, zero).sum()
+                    if a + b + c == 1:
+                        with torch.no_grad():
+                            plain = Fn.BCERowsFn.apply(r.view(targets[col].size()), targets[col], None)
+                            perf[key] = float(torch.where(tgt[:, col], plain, zero).sum()) / \
+                                (max(int(tgt[:, col].sum()), 1) * targets[col][0].numel())
+            if c:
+                if loss_mask is not None:
+                    raise ValueError("loss_mask is image-shaped and cannot multiply the (B, 7) pose term "
+                                     "(the reference raises here too: problems.py:445-447)")
+                rows = Fn.MSERowsFn.apply(out[2], targets[2])
+                rec = rec + self._pose_multiplier * torch.where(tgt[:, 2], rows, zero).sum()
+                if a + b == 0:
+                    perf['pose'] = float(torch.where(tgt[:, 2], rows.detach(), zero).sum()) / (max(int(tgt[:, 2].sum()), 1) * 7)
+            loss = loss + (rec.to(torch.float32) + self._kl_weight * Fn.KLFn.apply(means, log_var)) / B
+            if (a, b, c) == ((1, 1, 1) if use_pose else (1, 1, 0)):
+                joint = [out[0], out[1]] + ([out[2]] if use_pose else [])
+        return {'recon_x': joint, 'means': means, 'log_var': log_var, 'perf_measure': perf}, loss
+
+    def _evaluate_mvae(self, x, targets, loss_mask=None, reduce=None, reduction='sum', condition=None, available=None,
+                       target_available=None):
         """The reference's 3- or 7-subset schedule, one full model call per subset (problems.py:473-546)."""
         assert isinstance(x, list) and isinstance(targets, list)
         self._check_reduce(reduce, reduction)          # (before the first model call draws noise and moves running statistics)
+        if reduce is None and (available is not None or target_available is not None):
+            return self._evaluate_mvae_avail(x, targets, loss_mask, condition, available, target_available)
         kw = dict(loss_mask=loss_mask, reduce=reduce, reduction=reduction)
         m = self._model
         v_joint, t_joint, _, means, log_var = m([x[0], x[1]], condition=condition)
@@ -703,6 +800,10 @@ class SeqModeling(Reconstruction):
         return ({'model_input': mi, 'input_object_pose': pose_in, 'input_available_modals': avail, 'shock': shock},
                 {'target_output': to, 'target_object_pose': pose_t, 'loss_mask': mask})
 
+    def _target_available(self, has):
+        """Every target is the dataset's final frame of its sequence, which counts as present; so does the pose target."""
+        return torch.ones(has.shape[0], 3, device=has.device)
+
     def _evaluate_model(self, x, targets, reduction='sum', reduce=None, **kwargs):
         self._check_reduce(reduce, reduction)
         loss_mask = targets['loss_mask'] if self.parameters['mask_loss'] else None
@@ -717,7 +818,7 @@ class SeqModeling(Reconstruction):
                 return {'recon_x': last['recon_x'], 'means': last['means'], 'log_var': last['log_var'],
                         'perf_measure': self._fused_perf()}, res['rows']
             return self._evaluate_mvae(x=xs, targets=ts, loss_mask=loss_mask, reduce=reduce, reduction=reduction,
-                                       condition=x.get('shock'))
+                                       condition=x.get('shock'), **(self._avail_kw(x) if reduce is None else {}))
         if self._conditional:
             recon_x, means, log_var = self._model(x['model_input'], x['shock'])
         else:
@@ -761,6 +862,14 @@ class DynModeling(SeqModeling):
                  'shock': shock},
                 {'target_output': to, 'target_object_pose': [torch.roll(data[2], -1, dims=0).to(dev)],
                  'loss_mask': target[3].to(dev)})
+
+    def _target_available(self, has):
+        """The target of frame b is frame b + 1 (the roll of :meth:`parse_input`): so is its availability; the last frame of a
+        sequence takes the dataset's final target, which counts as present, and the pose target always counts."""
+        l = int(self._seq_length)
+        tgt = torch.roll(has.to(torch.float32), -1, dims=0)
+        tgt[l - 1::l] = 1.0
+        return torch.cat((tgt[:, :2], torch.ones(tgt.shape[0], 1, device=tgt.device)), 1)
 
     def _recorded_steps(self, data, target, T, n):
         """The recorded continuation of the n sequences of a loader batch over T steps: (``steps_of``, targets [visual, tactile,
