@@ -236,6 +236,17 @@ int mmdyn_wgrad_chunks_mx(int mode, int rows, int Cd, int Cg, int flags);
  * ACCUMULATOR with beta != 0.  The gathered columns cg_canon..Cg are dropped, written nowhere. */
 int mmdyn_wgrad_reduce(const float* partial, float* canon, int chunks, int taps, int Cd, int Cg,
                        int cg_canon, int perm, float beta, void* stream);
+/* The dense weight gradient written ONCE: mmdyn_wgrad_tn_grouped + mmdyn_wgrad_reduce(taps = 1, Cd' = G*Cd) in one launch without
+ * the slabs -- one block per (channel tile, group) sums its `chunks` row pieces itself, in the slab reduction's order, so canon
+ * [G*Cd][cg_canon] holds the same bits as after the two launches.  chunks as mmdyn_wgrad_chunks_mx(DENSE, rows, Cd, Cg, flags);
+ * perm / cg_canon / beta as mmdyn_wgrad_reduce (perm 1 / 2: G = 1; perm 1: cg_canon = Cg).  Serves what mmdyn_wgrad_canon_served accepts, else
+ * MMDYN_ERR_SHAPE (added without touching an existing signature: revision 6). */
+int mmdyn_wgrad_tn_canon(const void* D, const void* Gt, float* canon, int G, int rows, int Cd, int Cg, int cg_canon, int perm,
+                         float beta, int chunks, int flags, void* stream);
+/* Host only: 1 when mmdyn_wgrad_tn_canon serves (rows, Cd, Cg, groups) under `flags`, 0 otherwise -- plane operands, 16-bit
+ * storage, channel tiles whose waves split the rows, more than 64 chunks or fewer than 65536 elements (the slab reduction sums
+ * those in another order). */
+int mmdyn_wgrad_canon_served(int rows, int Cd, int Cg, int groups, int flags);
 
 /* ---- weight packing (canonical reference layout -> GEMM operand layout) --------------------- */
 /* Wc[d0][d1][16] -> P[tap][d0][d1] (swap=0) or P[tap][d1][d0] (swap=1) */

@@ -18,6 +18,10 @@ struct WgradGeom {
   int groups;
   int x3;      // fp32 launch on the bf16 matrix cores through the exact three-term operand split (wgrad_tn_kernel X3)
   int pre;     // x3: bit 0 = D, bit 1 = Gt arrives already split (rows of [plane][C] bf16) -- wgrad_tn_kernel / wgrad_tn4_kernel PRE
+  // "once" form of wgrad_tn_kernel (mmdyn_wgrad_tn_canon): the block sums its chunks itself and writes the reference layout
+  int cg_canon, perm;   // as mmdyn_wgrad_reduce
+  float beta;
+  int xcd_order;        // block ids that are equal modulo 8 (one XCD) walk neighbouring tiles
 };
 
 // wgrad_ws.hip (LAB build only: measured no faster than wgrad_tn.hip, see wgrad_entry): fp32 weight-gradient GEMM with loader

@@ -15,6 +15,7 @@
 // conflict-free ds_read_b32.  The row reduction is split over `chunks` blocks (deterministic partial
 // slabs, no atomics); a second kernel sums the slabs and scatters into the canonical layout.
 #include <stdlib.h>
+#include <string.h>
 #include "common.h"
 #include "wgrad_geom.h"
 
@@ -22,6 +23,22 @@ namespace {
 
 
 constexpr int RK = 32;  // rows per K-step
+
+// The reference ("canon") layout of a weight gradient: where element (tap, cd, cg) of the [taps][Cd][Cg] sum goes, and how it
+// is stored.  ONE definition for the two slab-reduction kernels and for the epilogue of the "once" form of wgrad_tn_kernel.
+//   perm 0: canon[cd][cg][tap];  perm 1: cg = hw*256 + ch -> canon[cd][ch*25 + hw];  perm 2: cd = hw*256 + ch -> canon[ch*25 + hw][cg]
+__device__ __forceinline__ int64_t canon_index(int tap, int cd, int cg, int taps, int cg_canon, int perm) {
+  if (perm == 0) return ((int64_t)cd * cg_canon + cg) * taps + tap;
+  if (perm == 1) {
+    const int hw = cg / 256, ch = cg - hw * 256;
+    return (int64_t)cd * cg_canon + ch * 25 + hw;
+  }
+  const int hw = cd / 256, ch = cd - hw * 256;
+  return (int64_t)(ch * 25 + hw) * cg_canon + cg;
+}
+__device__ __forceinline__ void canon_store(float* __restrict__ canon, int64_t o, float s, float beta) {
+  canon[o] = (beta != 0.f) ? (beta * canon[o] + s) : s;
+}
 
 // WK = number of waves that split the rows of one K-step between them (small channel tiles cannot
 // occupy four waves with distinct 32x32 outputs); each of them owns its own partial slab.
@@ -58,12 +75,20 @@ template <int BX> struct x3_ld { static constexpr int v = (BX == 32) ? 32 : BX +
 // PRE (X3 only; bit 0: D, bit 1: Gt): that operand ARRIVES split -- rows of [plane][C] bf16 written by its producer (the exact
 // three-term split, mmdyn_split_planes) -- and goes from HBM to the LDS planes as it is: three 8-byte loads per four channels, no
 // VALU work ("split once, not once per tile that reads the operand").
-template <int MODE, int BD, int BG, int WD, int WG, int WK, bool BF16, int ST, bool X3 = false, int PRE = 0>
+// ONCE (dense launches, WK = 1, fp32 operands in HBM): no slabs.  One block owns a (channel tile, group), walks ALL the rows
+// of its group and keeps two accumulator sets: `acc` for the current chunk and `tot` for the running total.  The chunks are
+// those of the slab form (g.chunks, g.rows_per_chunk), and at every chunk boundary tot += acc, acc = 0 -- so every element is
+// the sum wgrad_reduce_vec_kernel forms from the slabs, s = 0; for c: s += partial[c], in the same order and to the same bits
+// (a chunk past the end of the rows is a zero slab there and nothing here: s + 0 == s, and s is never -0).  rows_per_chunk is
+// a multiple of RK, so a K-step never straddles a chunk and the row loop runs through the boundaries without draining its
+// prefetch.  The epilogue writes `partial` = canon through canon_index / canon_store.
+template <int MODE, int BD, int BG, int WD, int WG, int WK, bool BF16, int ST, bool X3 = false, int PRE = 0, bool ONCE = false>
 __global__ __launch_bounds__(256) void wgrad_tn_kernel(const float* __restrict__ D,
                                                        const float* __restrict__ Gt,
                                                        float* __restrict__ partial, const WgradGeom g) {
   static_assert(!X3 || (!BF16 && ST == 0 && WK == 1 && MODE != MMDYN_IM2COL3), "the three-term split is a variant of the fp32 kernel");
   static_assert(PRE == 0 || X3, "operands that arrive split belong to the three-term split arithmetic");
+  static_assert(!ONCE || (MODE == MMDYN_DENSE && WK == 1 && PRE == 0 && (ST == 0 || ST == 4)), "the once form: dense, fp32 operands in HBM");
   constexpr bool PD = (PRE & 1) != 0, PG = (PRE & 2) != 0;
   constexpr int DT = WD / 32, GT = WG / 32;
   constexpr int WAVES_G = BG / WG;
@@ -85,19 +110,47 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(const float* __restrict__
   const int wk = wave / WAVES_DG, wdg = wave % WAVES_DG;
   const int wd = wdg / WAVES_G, wg = wdg % WAVES_G;
   const int tiles_g = g.Cg / BG;
-  const int td = blockIdx.x / tiles_g, tg = blockIdx.x - td * tiles_g;
-  const int cd0 = td * BD, cg0 = tg * BG;
-  const int tap = blockIdx.y;
-  // grouped launch: blockIdx.z = group * zblocks + chunk (plain launch: one group)
   const int ngrp = g.groups > 1 ? g.groups : 1;
-  const int zb = gridDim.z / ngrp;
-  const int grp = blockIdx.z / zb, chunk = blockIdx.z - grp * zb;
+  int td, tg, tap, grp, chunk;
+  if constexpr (ONCE) {
+    // one-dimensional grid over (group, channel tile).  xcd_order: workgroups are dealt round-robin over the 8 XCDs, so the
+    // ids that are equal modulo 8 take a contiguous run of tiles -- neighbours share the D tile in that XCD's L2, and with
+    // perm 1 (hw fastest below) the 25 tiles that fill the same 128-byte lines of canon write them into ONE L2
+    const int tiles = (g.Cd / BD) * tiles_g, n = tiles * ngrp;
+    int v = blockIdx.x;
+    if (g.xcd_order) {
+      const int per = (n + 7) >> 3;
+      v = (v & 7) * per + (v >> 3);
+      if (v >= n) return;                 // (uniform per block: before any barrier)
+    }
+    grp = v / tiles;
+    const int t = v - grp * tiles;
+    if (g.perm == 1) {                    // Cg = 25 * 256: tile tg = hw * (256 / BG) + channel tile
+      constexpr int TPH = 256 / BG;
+      const int hw = t % 25, rest = t / 25;
+      td = rest / TPH;
+      tg = hw * TPH + (rest - td * TPH);
+    } else {
+      td = t / tiles_g;
+      tg = t - td * tiles_g;
+    }
+    tap = 0;
+    chunk = 0;
+  } else {
+    td = blockIdx.x / tiles_g, tg = blockIdx.x - td * tiles_g;
+    tap = blockIdx.y;
+    // grouped launch: blockIdx.z = group * zblocks + chunk (plain launch: one group)
+    const int zb = gridDim.z / ngrp;
+    grp = blockIdx.z / zb, chunk = blockIdx.z - grp * zb;
+  }
+  const int cd0 = td * BD, cg0 = tg * BG;
   const int dh = (MODE == MMDYN_CONV) ? (tap >> 2) : 0;
   const int dw = (MODE == MMDYN_CONV) ? (tap & 3) : 0;
   const int HWr = g.Hr * g.Wr;
 
+  // (ONCE: all the rows of the group; rows_per_chunk then only places the chunk boundaries)
   const int row_begin = grp * g.rows + chunk * g.rows_per_chunk;
-  const int row_end = min((grp + 1) * g.rows, row_begin + g.rows_per_chunk);
+  const int row_end = ONCE ? (grp + 1) * g.rows : min((grp + 1) * g.rows, row_begin + g.rows_per_chunk);
 
   // Branch-free fetch (same idea as igemm_nt): rows past the chunk or outside the image read a valid dummy
   // address and are zeroed when the tile is written to LDS; pixel decode uses a float reciprocal (rows < 2^23).
@@ -287,6 +340,16 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(const float* __restrict__
     for (int b = 0; b < GT; ++b)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+  f32x16 tot[ONCE ? DT : 1][ONCE ? GT : 1];      // ONCE: the sum of the chunks that are complete
+  if constexpr (ONCE) {
+#pragma unroll
+    for (int a = 0; a < DT; ++a)
+#pragma unroll
+      for (int b = 0; b < GT; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) tot[a][b][e] = 0.f;
+  }
+  int fold_at = row_begin + g.rows_per_chunk;     // ONCE: the first row of the next chunk
 
   const int h = lane >> 5, cl = lane & 31;
   if (row_begin < row_end) {
@@ -382,11 +445,43 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(const float* __restrict__
           for (int b = 0; b < GT; ++b)
             acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a], bf[b], acc[a][b], 0, 0, 0);
       }
+      if constexpr (ONCE) {
+        if (r0 + RK == fold_at) {          // a chunk is complete (uniform per block)
+          fold_at += g.rows_per_chunk;
+#pragma unroll
+          for (int a = 0; a < DT; ++a)
+#pragma unroll
+            for (int b = 0; b < GT; ++b)
+#pragma unroll
+              for (int e = 0; e < 16; ++e) {
+                tot[a][b][e] += acc[a][b][e];
+                acc[a][b][e] = 0.f;
+              }
+        }
+      }
       __builtin_amdgcn_sched_barrier(0);   // the masking selects of lds_store (which wait for the loads) stay behind the MFMAs
       __syncthreads();
       lds_store();
       __syncthreads();
     }
+  }
+
+  if constexpr (ONCE) {
+    // the last chunk (ragged, or none: acc is zero then); then canon, rows [groups * Cd] -- no block but this one writes them
+    const int cgc = g.cg_canon, perm = g.perm;
+    const float beta = g.beta;
+#pragma unroll
+    for (int a = 0; a < DT; ++a)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int cd = grp * g.Cd + cd0 + wd * WD + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+#pragma unroll
+        for (int b = 0; b < GT; ++b) {
+          const int cg = cg0 + wg * WG + b * 32 + cl;
+          if (cg < cgc) canon_store(partial, canon_index(0, cd, cg, 1, cgc, perm), tot[a][b][e] + acc[a][b][e], beta);
+        }
+      }
+    return;
   }
 
   float* out = partial + ((size_t)(((chunk * WK + wk) * ngrp + grp) * g.ntaps + tap) * g.Cd) * g.Cg;
@@ -1095,19 +1190,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
       int64_t t = i / Cg;
       int cd = (int)(t % Cd);
       int tap = (int)(t / Cd);
-      if (cg < cg_canon) {
-        int64_t o;
-        if (perm == 0) {
-          o = ((int64_t)cd * cg_canon + cg) * taps + tap;
-        } else if (perm == 1) {  // cg = hw*256 + ch  -> column ch*25 + hw
-          int hw = cg / 256, ch = cg - hw * 256;
-          o = (int64_t)cd * cg_canon + ch * 25 + hw;
-        } else {                 // cd = hw*256 + ch  -> row ch*25 + hw
-          int hw = cd / 256, ch = cd - hw * 256;
-          o = (int64_t)(ch * 25 + hw) * cg_canon + cg;
-        }
-        canon[o] = (beta != 0.f) ? (beta * canon[o] + s) : s;
-      }
+      if (cg < cg_canon) canon_store(canon, canon_index(tap, cd, cg, taps, cg_canon, perm), s, beta);
     }
     __syncthreads();
   }
@@ -1131,17 +1214,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_vec_kernel(const float* __re
     for (int k = 0; k < 4; ++k) {
       const int cg = cg0 + k;
       if (cg >= cg_canon) continue;
-      int64_t o;
-      if (perm == 0) {
-        o = ((int64_t)cd * cg_canon + cg) * taps + tap;
-      } else if (perm == 1) {
-        int hw = cg / 256, ch = cg - hw * 256;
-        o = (int64_t)cd * cg_canon + ch * 25 + hw;
-      } else {
-        int hw = cd / 256, ch = cd - hw * 256;
-        o = (int64_t)(ch * 25 + hw) * cg_canon + cg;
-      }
-      canon[o] = (beta != 0.f) ? (beta * canon[o] + s[k]) : s[k];
+      canon_store(canon, canon_index(tap, cd, cg, taps, cg_canon, perm), s[k], beta);
     }
   }
 }
@@ -1219,6 +1292,30 @@ static int launch(const float* D, const float* Gt, float* partial, WgradGeom g, 
   else return MMDYN_ERR_SHAPE;
 #undef WGRAD_MODE
 #undef WGRAD_LAUNCH
+  MMDYN_LAUNCH_CHECK();
+}
+
+// The once form (wgrad_tn_kernel ONCE): tiles x groups blocks, the chunk cut of launch<.., 1>.  g.chunks / cg_canon / perm / beta
+// / xcd_order are set by the caller.
+template <int BD, int BG, int WD, int WG>
+static int launch_once(const float* D, const float* Gt, float* canon, WgradGeom g, hipStream_t st, bool bf16) {
+  const int rpc = ceil_div(g.rows, g.chunks);
+  g.rows_per_chunk = ceil_div(rpc, RK) * RK;
+  const int n = (g.Cd / BD) * (g.Cg / BG) * (g.groups > 1 ? g.groups : 1);
+  dim3 grid(g.xcd_order ? (n + 7) / 8 * 8 : n);
+  size_t smem = (size_t)RK * (BD + BG) * sizeof(float);
+#define WGRAD_ONCE(BF, ST_, X3_) \
+  hipLaunchKernelGGL((wgrad_tn_kernel<MMDYN_DENSE, BD, BG, WD, WG, 1, BF, ST_, X3_, 0, true>), grid, dim3(256), smem, st, D, Gt, canon, g)
+  if (g.x3 && !bf16) {
+    smem = (size_t)3 * RK * (x3_ld<BD>::v + x3_ld<BG>::v) * 2;
+    static LdsOptIn opt_in;
+    if (smem > 65536)
+      if (int e = opt_in.ensure((const void*)wgrad_tn_kernel<MMDYN_DENSE, BD, BG, WD, WG, 1, false, 0, true, 0, true>, (int)smem)) return e;
+    WGRAD_ONCE(false, 0, true);
+  } else if (bf16 && g.f16) WGRAD_ONCE(true, 4, false);
+  else if (bf16) WGRAD_ONCE(true, 0, false);
+  else WGRAD_ONCE(false, 0, false);
+#undef WGRAD_ONCE
   MMDYN_LAUNCH_CHECK();
 }
 
@@ -1454,4 +1551,75 @@ extern "C" int mmdyn_wgrad_reduce(const float* partial, float* canon, int chunks
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, partial, canon, chunks,
                      taps, Cd, Cg, cg_canon, perm, beta);
   MMDYN_LAUNCH_CHECK();
+}
+
+// ---- the once form: the gradient written in the reference layout by the GEMM itself (no slabs, no reduction launch) ----
+// Channel tile of the once form.  The grid is tiles x groups blocks and every block walks all the rows of its group, so what
+// pays is many short row loops: 64x64 tiles were the fastest instance on every FC-level shape of the bs-256 step, alone and in
+// the step (docs/LAB_NOTES.md AA: 33 / 35 / 38 us on the encoder layer for 64x64 / 128x64 / 128x128).  The larger instances are
+// built for the LAB knob only: MMDYN_WGRAD_ONCE_TILE=128x128 | 128x64 | 64x64 asks for one; a tile that does not divide the
+// channels gives way to the next smaller one.
+struct OnceTile {
+  int bd, bg;
+};
+static OnceTile once_tile(int Cd, int Cg) {
+  int want = 1;
+  if (const char* e = lab_env("MMDYN_WGRAD_ONCE_TILE")) want = !strcmp(e, "128x128") ? 3 : !strcmp(e, "128x64") ? 2 : 1;
+  const bool d128 = Cd % 128 == 0, g128 = Cg % 128 == 0;
+  if (want == 3 && d128 && g128) return {128, 128};
+  if (want >= 2 && d128) return {128, 64};
+  return {64, 64};
+}
+
+/* 1 when mmdyn_wgrad_tn_canon serves the launch with the bits of mmdyn_wgrad_tn_grouped + mmdyn_wgrad_reduce, else 0 (host only). */
+extern "C" int mmdyn_wgrad_canon_served(int rows, int Cd, int Cg, int groups, int flags) {
+  if (flags & ~(1 | 32 | 128)) return 0;                  // 16-bit storage (bits 1 / 2), plane operands (bits 8 / 9)
+  if ((flags & 128) && (flags & (1 | 32))) return 0;
+  if (rows <= 0 || groups < 1 || Cd <= 0 || Cg <= 0 || Cd % 32 || Cg % 32) return 0;
+  const WgradRoute r = wgrad_route(MMDYN_DENSE, Cd, Cg, false);
+  if (r.family != WGRAD_TN || r.wk != 1) return 0;        // (WK > 1: the waves of a block own slabs of their own)
+  // the slab reduction sums in wgrad_reduce_vec_kernel's order for <= 64 slabs of >= 65536 elements, else in wgrad_reduce_kernel's
+  const int chunks = mmdyn_wgrad_chunks_mx(MMDYN_DENSE, rows, Cd, Cg, flags);
+  if (chunks < 4 || chunks > 64 || (int64_t)groups * Cd * Cg < 65536) return 0;
+  if ((int64_t)groups * rows * Cd >= (1LL << 31) || (int64_t)groups * rows * Cg >= (1LL << 31) || (int64_t)groups * Cd * Cg >= (1LL << 31)) return 0;
+  return 1;
+}
+
+/* Weight gradient of G dense problems (operands as mmdyn_wgrad_tn_grouped), summed over the rows in `chunks` pieces inside the
+ * block and written once: canon [G*Cd][cg_canon] (+ beta * canon), perm / cg_canon as mmdyn_wgrad_reduce with taps = 1. */
+extern "C" int mmdyn_wgrad_tn_canon(const void* D, const void* Gt, float* canon, int G, int rows, int Cd, int Cg, int cg_canon,
+                                    int perm, float beta, int chunks, int flags, void* stream) {
+  if (!D || !Gt || !canon) return MMDYN_ERR_NULL;
+  if (G < 1 || rows <= 0 || cg_canon > Cg || cg_canon <= 0 || perm < 0 || perm > 2) return MMDYN_ERR_SHAPE;
+  if (perm == 1 && (Cg % 256 || Cg / 256 != 25 || cg_canon != Cg)) return MMDYN_ERR_SHAPE;      // (every column moves: none can be dropped)
+  if (perm == 2 && (Cd % 256 || Cd / 256 != 25)) return MMDYN_ERR_SHAPE;
+  if (perm != 0 && G > 1) return MMDYN_ERR_SHAPE;
+  if (chunks < 4 || chunks % 4 || chunks > 64) return MMDYN_ERR_SHAPE;
+  if (!mmdyn_wgrad_canon_served(rows, Cd, Cg, G, flags)) return MMDYN_ERR_SHAPE;
+  const bool bf16 = (flags & (1 | 32)) != 0;
+  bool x3 = (flags & 128) != 0;
+  if (const char* e = lab_env("MMDYN_X3_WGRAD")) x3 = e[0] == '1';      // (LAB: override, as wgrad_entry)
+  WgradGeom g{};
+  g.x3 = x3 && !bf16;
+  g.f16 = (flags & 32) != 0;
+  g.mode = MMDYN_DENSE;
+  g.groups = G;
+  g.rows = rows;
+  g.Hr = g.Wr = g.Hi = g.Wi = 1;
+  g.Cd = Cd;
+  g.Cg = Cg;
+  g.rs = 1;
+  g.ntaps = 1;
+  g.chunks = chunks;
+  g.cg_canon = cg_canon;
+  g.perm = perm;
+  g.beta = beta;
+  g.xcd_order = 1;
+  if (const char* e = lab_env("MMDYN_WGRAD_ONCE_XCD")) g.xcd_order = e[0] != '0';      // (LAB: block order A/B)
+  hipStream_t st = (hipStream_t)stream;
+  const float *d = (const float*)D, *gt = (const float*)Gt;
+  const OnceTile t = once_tile(Cd, Cg);
+  if (t.bd == 128 && t.bg == 128) return launch_once<128, 128, 64, 64>(d, gt, canon, g, st, bf16);
+  if (t.bd == 128) return launch_once<128, 64, 64, 32>(d, gt, canon, g, st, bf16);
+  return launch_once<64, 64, 32, 32>(d, gt, canon, g, st, bf16);
 }

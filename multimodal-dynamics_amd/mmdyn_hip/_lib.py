@@ -67,6 +67,8 @@ _SIGNATURES = {
     "mmdyn_wgrad_chunks": "iiii",
     "mmdyn_wgrad_chunks_mx": "iiiii",
     "mmdyn_wgrad_reduce": "pp" + "iiiiii" + "f" + "p",
+    "mmdyn_wgrad_tn_canon": "ppp" + "iiiiii" + "f" + "ii" + "p",
+    "mmdyn_wgrad_canon_served": "iiiii",
     "mmdyn_pack_conv_weight": "pp" + "iii" + "p",
     "mmdyn_repack2d": "pp" + "iiiii" + "p",
     "mmdyn_repack2d_ld": "pp" + "iiiiii" + "p",

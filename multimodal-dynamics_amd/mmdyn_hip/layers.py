@@ -132,6 +132,12 @@ PATCH_PLANES = True      # (False: the 32-channel up-sampling layers keep fp32 o
 # The 3-channel layers next to a plane consumer (64 x 64 images, fp32 storage; False: A/B measurements only -- the same bits either way)
 CONV1_PLANES = True      # encoder conv 0 writes its activated output as plane rows: no fp32 a1, no stand-alone split launch
 OUT3_RECOMPUTE = True    # last decoder layer's input gradient in two passes of one main loop: du is recomputed, never stored
+# Dense weight gradients the once-form kernel serves are written by the GEMM itself
+# (False: A/B measurements only -- wgrad_tn + wgrad_reduce through the slabs, the same bits)
+WGRAD_ONCE = True
+# which of them, by the permutation of the layer: encoder fc_net.0 (perm 1) -- 256 rows, 8 K-steps per block.  Decoder upsample.0
+# (perm 2: 1024 rows, 32 K-steps per block) and the 512-wide layers (perm 0) measured no faster than through the slabs and stay there
+WGRAD_ONCE_PERMS = (1,)
 
 
 def _conv3_plane_op(name, switch, S, *tensors):
@@ -457,6 +463,12 @@ def wgrad(D, Gt, canon, mode, Bt, Hr, Cd, Hi, Cg, stride=1, offset=0, cg_canon=N
         chunks = ops.B.wgrad_chunks(mode, rows, Cd, Cg, planes=(isinstance(D, ops.Planes), isinstance(Gt, ops.Planes)))
     else:
         chunks = ops.B.wgrad_chunks(mode, rows, Cd, Cg)
+    if WGRAD_ONCE and mode == DENSE and perm in WGRAD_ONCE_PERMS:
+        # the FC-level gradients: the GEMM sums its chunks itself and writes canon -- no slabs, no reduction launch, the same bits
+        once, served = getattr(ops.B, "wgrad_tn_canon", None), getattr(ops.B, "wgrad_canon_served", None)
+        if once is not None and served is not None and served(rows, Cd, Cg, 1, D, Gt):
+            once(D, Gt, canon, 1, rows, Cd, Cg, Cg if cg_canon is None else cg_canon, perm, 0.0, chunks)
+            return
     partial = _new(D, chunks, taps, Cd, Cg)
     ops.B.wgrad_tn(D, Gt, partial, mode, Bt, Hr, Hr, Cd, Hi, Hi, Cg, stride, offset, chunks)
     ops.B.wgrad_reduce(partial, canon, chunks, taps, Cd, Cg, Cg if cg_canon is None else cg_canon, perm, 0.0)

@@ -456,6 +456,26 @@ class HipBackend:
         check(self.lib.mmdyn_wgrad_reduce(_ptr(partial), _ptr(canon), chunks, taps, Cd, Cg, cg_canon, perm,
                                           float(beta), _stream()), "mmdyn_wgrad_reduce")
 
+    def _wgrad_canon_flags(self):
+        """Flag word of a dense weight gradient on fp32 operands in the current precision mode (as wgrad_tn_grouped)."""
+        return {"fp32": self._x3(), "fp16": 33, "fp16s": 33}.get(self.precision, 1)
+
+    def wgrad_canon_served(self, rows, Cd, Cg, groups=1, D=None, Gt=None):
+        """Whether wgrad_tn_canon writes this dense weight gradient (the bits of wgrad_tn / wgrad_tn_grouped + wgrad_reduce).
+        ``D`` / ``Gt``: the operands, if at hand -- plane operands and 16-bit tensors are not served."""
+        if self.precision in ("bf16s", "fp16s"):        # (the 16-bit storage modes cut their chunks for the all-16-bit kernels)
+            return False
+        for t in (D, Gt):
+            if isinstance(t, Planes) or (t is not None and t.dtype != torch.float32):
+                return False
+        return self.lib.mmdyn_wgrad_canon_served(rows, Cd, Cg, groups, self._wgrad_canon_flags()) == 1
+
+    def wgrad_tn_canon(self, D, Gt, canon, G, rows, Cd, Cg, cg_canon, perm, beta, chunks):
+        """canon [G*Cd][cg_canon] (+ beta * canon) of G dense weight-gradient problems whose rows follow one another in D / Gt:
+        one launch, no slabs; ``chunks`` as wgrad_chunks(DENSE, rows, Cd, Cg)."""
+        check(self.lib.mmdyn_wgrad_tn_canon(_ptr(D), _ptr(Gt), _ptr(canon), G, rows, Cd, Cg, cg_canon, perm, float(beta), chunks,
+                                            self._wgrad_canon_flags(), _stream()), "mmdyn_wgrad_tn_canon")
+
     # ---- packing / layout ----
     def pack_conv_weight(self, Wc, P, d0, d1, swap):
         pp, p16 = _aptr(P)                 # a 16-bit destination: the GEMM operand type of the 16-bit precision modes

@@ -10,7 +10,7 @@ import torch
 from . import ops
 
 PAD_CYCLES = 100000       # torch.cuda._sleep argument: ~43 us on an MI355X
-HOST_ONLY = {"igemm_stat_tiles", "colstats_tiles", "wgrad_chunks", "igemm_planes_served"}
+HOST_ONLY = {"igemm_stat_tiles", "colstats_tiles", "wgrad_chunks", "igemm_planes_served", "wgrad_canon_served"}
 
 
 def _canon(name, a):
@@ -28,7 +28,10 @@ def _canon(name, a):
     if name == "wgrad_tn_grouped":
         D, Gt, partial, G, rows, Cd, Cg, chunks = a
         name, a = "wgrad_tn", (D, Gt, partial, ops.DENSE, G * rows, 1, 1, Cd, 1, 1, Cg, 1, 0, chunks)
-    if name == "wgrad_out3_bn":           # the last decoder layer's weight gradient with the fused BatchNorm + Swish (conv3_wgrad_kernel)
+    if name == "wgrad_tn_canon":          # the once form of wgrad_tn_kernel: the same GEMM (and FLOPs), canon in place of the slabs
+        D, Gt, canon, G, rows, Cd, Cg, cg_canon, perm, beta, chunks = a
+        name, a = "wgrad_tn", (D, Gt, canon, ops.DENSE, G * rows, 1, 1, Cd, 1, 1, Cg, 1, 0, chunks)
+    if name == "wgrad_out3_bn":          # the last decoder layer's weight gradient with the fused BatchNorm + Swish (conv3_wgrad_kernel)
         y, mean, rstd, gamma, beta, Gt, partial, G, Bg, Hr, chunks = a
         return "conv3_wgrad", (y, Gt, partial, ops.IM2COL3, G * Bg, Hr, Hr, 32, 2 * Hr, 2 * Hr, 64, 1, 0, chunks)
     if name == "tconv_out3_bn_fwd":
