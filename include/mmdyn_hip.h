@@ -735,6 +735,42 @@ typedef struct {
 } mmdyn_ensemble_groups;
 int mmdyn_ensemble_feed(const mmdyn_ensemble_groups* groups, int G, const uint8_t* obs_avail, int N, int B, void* stream);
 
+/* mmdyn_ensemble_quantiles: Q order statistics per element of the ensemble's prediction, for up to MMDYN_FEED_GROUPS tensors in one
+ * launch (MVAEInference.rollout(samples=N, quantiles=...): the prediction band the mean and the variance do not give for a squashed
+ * pixel).  src[g] is fp32 [N][plane], plane = B * row_len[g], sample-major -- the layout of mmdyn_ensemble_groups.recon --, and
+ * p_n = logits[g] ? 1 / (1 + expf(-src)) : src, the bits mmdyn_ensemble_feed writes into out for the same element.  For element e
+ * let s_0 <= ... <= s_{N-1} be the N values p_n[e] in ascending order of the fp32 `<`, and hi = min(lo[j] + 1, N - 1).  Then
+ *   out[g][j][e] = s_lo[j]                                                      where frac[j] == 0: no arithmetic, so +-Inf samples
+ *                                                                               are ordinary values;
+ *   out[g][j][e] = (float)((double)s_lo + frac[j] * ((double)s_hi - (double)s_lo))   otherwise: the difference, the product and the
+ *                                                                               sum each rounded on their own in fp64, then ONE
+ *                                                                               rounding to fp32.
+ * With lo = floor(h), frac = h - lo, h = q * (N - 1) -- formed by the CALLER, the kernel never sees q -- this is the `linear`
+ * quantile of numpy / torch.quantile; a restatement made of a sort and single fp64 operations has the same bits.  Values that
+ * compare equal are interchangeable: only the SIGN OF A ZERO result is unspecified (-0.0 == +0.0).  A NaN among the N samples of an
+ * element makes all Q outputs of THAT element NaN and nothing else (the rule of mean / var).  No atomics: the same bits in every run.
+ * One wavefront per block works on chunks of 64 consecutive elements: the chunk's N x 64 values go through LDS once (N rounded up
+ * to four, times 256 bytes: 32 KB at MMDYN_QUANTILE_N_MAX), each lane then ranks the samples of its own element (sample n has rank
+ * #{m: p_m < p_n or (p_m == p_n and m < n)}) and keeps those of rank lo[j] and hi.  Every src element is loaded from global memory
+ * exactly once; 16-byte accesses where src[g] and out[g] are 16-byte aligned and plane % 4 == 0, element by element otherwise.  A
+ * block works on one group.  No workspace, no scratch; out is an OUTPUT: every element written, none read.
+ * Checked on the host before the launch: groups, or src / out of a group < G, null: MMDYN_ERR_NULL; G outside
+ * [1, MMDYN_FEED_GROUPS], Q outside [1, MMDYN_QUANTILES_MAX], N < 1, B < 1, a row_len < 1, a lo[j] outside [0, N), a frac[j] outside
+ * [0, 1) or NaN (j < Q), or an out[g] that overlaps the src of ANY group < G or the out of another: MMDYN_ERR_SHAPE;
+ * N > MMDYN_QUANTILE_N_MAX, N * plane >= 2^31 or Q * plane >= 2^31: MMDYN_ERR_RANGE.  The struct is read during the call only: lo and
+ * frac travel to the kernel by value.  Added without touching an existing signature or workspace: the revision stays 6. */
+#define MMDYN_QUANTILES_MAX 8
+#define MMDYN_QUANTILE_N_MAX 128
+typedef struct {
+  const float* src[MMDYN_FEED_GROUPS];    /* [N][B * row_len[g]], sample-major */
+  float* out[MMDYN_FEED_GROUPS];          /* [Q][B * row_len[g]] */
+  int row_len[MMDYN_FEED_GROUPS];
+  int logits[MMDYN_FEED_GROUPS];          /* != 0: src holds logits, the quantiles are those of their sigmoid */
+  int lo[MMDYN_QUANTILES_MAX];            /* index of the lower order statistic of quantile j */
+  double frac[MMDYN_QUANTILES_MAX];       /* weight of the upper one, in [0, 1) */
+} mmdyn_quantile_groups;
+int mmdyn_ensemble_quantiles(const mmdyn_quantile_groups* groups, int G, int Q, int N, int B, void* stream);
+
 /* ---- candidate conditions: N conditions scored per row, the best one picked on the device (the reference has no such operation:
  * with vae.py:126-165 a caller would run MVAE.forward once per candidate and take the argmin of the losses of problems.py:473-546
  * on the host) --------------------------------------------------------------------------------------------------------------

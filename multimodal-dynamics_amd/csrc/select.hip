@@ -25,11 +25,15 @@
 //     decoder rows of a step become the N * B next states under observations that exist once per request row, and the same read
 //     of the logits leaves the ensemble's per-element mean and variance and each row's summed variance.  An element scheme of
 //     its own (a thread walks the samples of one quad); its out has the bits of rollout_feed on the N * B rows.
+//   - ensemble_quantiles: Q order statistics per element over the N samples of the same decoder outputs
+//     (MVAEInference.rollout(samples=N, quantiles=...)): one launch after the step's ensemble_feed.  A wavefront ranks the samples
+//     of 64 elements in LDS; a selected image value has the bits ensemble_feed wrote (the same sigmoid_exact).
 //   - plan_sample / plan_refit: the two launches that turn the horizon planner into the cross-entropy method
 //     (MVAEInference.plan_refine).  plan_sample writes an iteration's candidates mean + std * eps (slot 0: the incumbent), clamped,
 //     straight into the [T][N * B][cd] layout the steps read; plan_refit ranks a row's [N] cost column in LDS, flags the K smallest
 //     and refits mean / std over them in fp64, one block per row.
-// Memory-bound, no LDS (plan_refit: 20 KB), no scratch; no atomics except ensemble_feed's spread accumulator.
+// Memory-bound, no LDS (plan_refit: 20 KB; ensemble_quantiles: 256 bytes per sample, 32 KB at most), no scratch; no atomics except
+// ensemble_feed's spread accumulator.
 #include "common.h"
 
 namespace {
@@ -257,6 +261,168 @@ __global__ __launch_bounds__(256) void ensemble_feed_kernel(const EnsembleArgs a
   else
     ensemble_rows<1>(a.recon[g], a.obs[g], avail, a.column[g], a.out[g], a.mean[g], a.var[g], a.spread[g], a.plane[g], a.row_len[g],
                      a.logits[g], N, wave0, nthreads);
+}
+
+// ---- ensemble rollout: order statistics of the N samples of every element ----
+
+struct QuantileArgs {
+  const float* src[MMDYN_FEED_GROUPS];
+  float* out[MMDYN_FEED_GROUPS];
+  int64_t plane[MMDYN_FEED_GROUPS];          // B * row_len: the floats of one sample, the stride between samples and between quantiles
+  int logits[MMDYN_FEED_GROUPS], vec[MMDYN_FEED_GROUPS];
+  int first_block[MMDYN_FEED_GROUPS + 1];
+  int lo[MMDYN_QUANTILES_MAX], hi[MMDYN_QUANTILES_MAX];     // hi = min(lo + 1, N - 1), formed on the host
+  double frac[MMDYN_QUANTILES_MAX];
+};
+
+constexpr int QUANTILE_CHUNK = 64;           // elements of one chunk: one per lane of the block's single wavefront
+constexpr int QUANTILE_UNROLL = 4;           // loads of one thread in flight while the chunk is brought in
+
+// s_lo + frac * (s_hi - s_lo) in fp64, the difference, the product and the sum rounded on their own (the pragma as in plan_cost),
+// then one rounding to fp32.
+__device__ __forceinline__ float quantile_lerp(float a, float b, double frac) {
+#pragma clang fp contract(off)
+  const double d = (double)b - (double)a;
+  const double p = frac * d;
+  return (float)((double)a + p);
+}
+
+// One block = one wavefront works on chunks of 64 consecutive elements of the plane.  A chunk's N x 64 values p go through LDS
+// once: column `lane` of col[N4 / 4][64][4] (sample n of element c at (n / 4, c, n % 4); N4 = N rounded up to four, the pad NaN) is
+// the sample vector of element c.  Bringing in: every src element is loaded once -- 16 bytes per lane where the group allows it
+// (16 lanes cover the chunk, so one wave instruction brings four samples), one float per lane otherwise.  Selecting: lane c owns
+// element c and walks its column four samples at a time; the rank of sample n is the number of samples in front of it -- a
+// smaller value, or an equal one with a smaller n --, so the ranks of an element without NaN are a permutation of 0 .. N-1 and
+// s_k is the sample of rank k.  The pad counts in front of nothing (every comparison with NaN is false) and is never selected
+// (n < N).  Every loop bound is block-uniform (the barriers) and every index into the Q-sized register arrays is a compile-time
+// constant (no scratch).  Writing: 4 bytes per lane, or through the first Q rows of LDS as 16-byte stores.
+__global__ __launch_bounds__(QUANTILE_CHUNK) void ensemble_quantiles_kernel(const QuantileArgs a, int G, int Q, int N) {
+  extern __shared__ __attribute__((aligned(16))) float col[];                 // max(N4, MMDYN_QUANTILES_MAX) * 64 floats
+  int g = 0;
+#pragma unroll
+  for (int k = 1; k < MMDYN_FEED_GROUPS; ++k)
+    if (k < G && (int)blockIdx.x >= a.first_block[k]) g = k;
+  const float* __restrict__ src = a.src[g];
+  float* __restrict__ out = a.out[g];
+  const int64_t plane = a.plane[g];
+  const int logits = a.logits[g], vec = a.vec[g];
+  const int lane = threadIdx.x;
+  const int N4 = (N + 3) & ~3;
+  const int64_t chunks = (plane + QUANTILE_CHUNK - 1) / QUANTILE_CHUNK;
+  const int nblocks = a.first_block[g + 1] - a.first_block[g];
+  for (int64_t chunk = (int)blockIdx.x - a.first_block[g]; chunk < chunks; chunk += nblocks) {
+    const int64_t e0 = chunk * QUANTILE_CHUNK;
+    // ---- the chunk's samples into LDS ----
+    if (vec) {
+      const int quad = lane & 15, sub = lane >> 4;                            // this lane: elements 4 * quad .. + 3 of sample n0 + sub
+      const int64_t e = e0 + 4 * quad;
+      const bool inside = e < plane;                                          // (plane % 4 == 0: a quad is inside or outside)
+      for (int n0 = 0; n0 < N4; n0 += 4 * QUANTILE_UNROLL) {
+        float r[QUANTILE_UNROLL][4];
+#pragma unroll
+        for (int u = 0; u < QUANTILE_UNROLL; ++u) {
+          const int n = n0 + 4 * u + sub;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) r[u][k] = NAN;
+          if (inside && n < N) ld_w<4>(src + (int64_t)n * plane + e, r[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < QUANTILE_UNROLL; ++u) {
+          const int n = n0 + 4 * u + sub;
+          if (n < N4) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const float p = (logits && n < N) ? sigmoid_exact(r[u][k]) : r[u][k];
+              col[((n >> 2) * QUANTILE_CHUNK + 4 * quad + k) * 4 + (n & 3)] = p;
+            }
+          }
+        }
+      }
+    } else {
+      const bool inside = e0 + lane < plane;
+      for (int n0 = 0; n0 < N4; n0 += 4) {
+        float r[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          r[u] = NAN;
+          if (inside && n0 + u < N) ld_w<1>(src + (int64_t)(n0 + u) * plane + e0 + lane, &r[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (logits && n0 + u < N) r[u] = sigmoid_exact(r[u]);
+        *reinterpret_cast<f32x4*>(col + ((n0 >> 2) * QUANTILE_CHUNK + lane) * 4) = f32x4{r[0], r[1], r[2], r[3]};
+      }
+    }
+    __syncthreads();
+    // ---- lane = element: ranks and the 2 Q order statistics ----
+    float s_lo[MMDYN_QUANTILES_MAX], s_hi[MMDYN_QUANTILES_MAX];
+#pragma unroll
+    for (int j = 0; j < MMDYN_QUANTILES_MAX; ++j) s_lo[j] = s_hi[j] = 0.f;
+    bool nan = false;
+    for (int n0 = 0; n0 < N4; n0 += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(col + ((n0 >> 2) * QUANTILE_CHUNK + lane) * 4);
+      int rank[4] = {0, 0, 0, 0};
+      for (int m0 = 0; m0 < n0; m0 += 4) {                                    // earlier samples: an equal one is in front
+        const f32x4 w = *reinterpret_cast<const f32x4*>(col + ((m0 >> 2) * QUANTILE_CHUNK + lane) * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) rank[i] += w[k] <= v[i] ? 1 : 0;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (k != i) rank[i] += (k < i ? v[k] <= v[i] : v[k] < v[i]) ? 1 : 0;
+      for (int m0 = n0 + 4; m0 < N4; m0 += 4) {                               // later samples: only a smaller one is
+        const f32x4 w = *reinterpret_cast<const f32x4*>(col + ((m0 >> 2) * QUANTILE_CHUNK + lane) * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) rank[i] += w[k] < v[i] ? 1 : 0;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (n0 + i < N) {
+          nan = nan || (v[i] != v[i]);
+#pragma unroll
+          for (int j = 0; j < MMDYN_QUANTILES_MAX; ++j) {
+            if (j < Q) {
+              s_lo[j] = rank[i] == a.lo[j] ? v[i] : s_lo[j];
+              s_hi[j] = rank[i] == a.hi[j] ? v[i] : s_hi[j];
+            }
+          }
+        }
+      }
+    }
+    float res[MMDYN_QUANTILES_MAX];
+#pragma unroll
+    for (int j = 0; j < MMDYN_QUANTILES_MAX; ++j) {
+      res[j] = 0.f;
+      if (j < Q) {
+        res[j] = a.frac[j] == 0.0 ? s_lo[j] : quantile_lerp(s_lo[j], s_hi[j], a.frac[j]);
+        if (nan) res[j] = NAN;
+      }
+    }
+    // ---- the Q results of the chunk ----
+    if (vec) {
+      __syncthreads();                                                        // every lane is done with its column
+#pragma unroll
+      for (int j = 0; j < MMDYN_QUANTILES_MAX; ++j)
+        if (j < Q) col[j * QUANTILE_CHUNK + lane] = res[j];
+      __syncthreads();
+      for (int i = lane; i < Q * (QUANTILE_CHUNK / 4); i += QUANTILE_CHUNK) {
+        const int j = i >> 4, quad = i & 15;
+        const int64_t e = e0 + 4 * quad;
+        if (e < plane) st_w<4>(out + (int64_t)j * plane + e, col + j * QUANTILE_CHUNK + 4 * quad);
+      }
+    } else if (e0 + lane < plane) {
+#pragma unroll
+      for (int j = 0; j < MMDYN_QUANTILES_MAX; ++j)
+        if (j < Q) st_w<1>(out + (int64_t)j * plane + e0 + lane, &res[j]);
+    }
+    __syncthreads();                                                          // LDS is free for the next chunk
+  }
 }
 
 // ---- candidate conditions: the cost table, the winner of each row, and the winner's rows ----
@@ -801,6 +967,47 @@ extern "C" int mmdyn_ensemble_feed(const mmdyn_ensemble_groups* groups, int G, c
   }
   const int blocks = split_blocks(work, G, a.first_block);
   hipLaunchKernelGGL(ensemble_feed_kernel, dim3(blocks), dim3(256), 0, ST, a, reinterpret_cast<const uint32_t*>(obs_avail), G, N);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_ensemble_quantiles(const mmdyn_quantile_groups* groups, int G, int Q, int N, int B, void* stream) {
+  if (!groups) return MMDYN_ERR_NULL;
+  if (G < 1 || G > MMDYN_FEED_GROUPS || Q < 1 || Q > MMDYN_QUANTILES_MAX || N < 1 || B < 1) return MMDYN_ERR_SHAPE;
+  QuantileArgs a{};
+  int64_t work[MMDYN_FEED_GROUPS];
+  for (int g = 0; g < G; ++g) {
+    if (!groups->src[g] || !groups->out[g]) return MMDYN_ERR_NULL;
+    if (groups->row_len[g] < 1) return MMDYN_ERR_SHAPE;
+  }
+  for (int j = 0; j < Q; ++j) {
+    if (groups->lo[j] < 0 || groups->lo[j] >= N || !(groups->frac[j] >= 0.0 && groups->frac[j] < 1.0)) return MMDYN_ERR_SHAPE;
+    a.lo[j] = groups->lo[j];
+    a.hi[j] = groups->lo[j] + 1 < N ? groups->lo[j] + 1 : N - 1;
+    a.frac[j] = groups->frac[j];
+  }
+  if (N > MMDYN_QUANTILE_N_MAX) return MMDYN_ERR_RANGE;
+  for (int g = 0; g < G; ++g) {
+    const int64_t plane = (int64_t)B * groups->row_len[g];
+    if (plane * N >= (1LL << 31) || plane * Q >= (1LL << 31)) return MMDYN_ERR_RANGE;
+    a.src[g] = groups->src[g];
+    a.out[g] = groups->out[g];
+    a.plane[g] = plane;
+    a.logits[g] = groups->logits[g];
+    // 16-byte accesses: both pointers aligned and a sample / quantile stride that keeps the alignment
+    a.vec[g] = (((uintptr_t)groups->src[g] | (uintptr_t)groups->out[g]) & 15) == 0 && plane % 4 == 0;
+    work[g] = ceil_div64(plane, 4 * QUANTILE_CHUNK);                // in blocks of 256 threads, as the cap counts them
+  }
+  // the quantiles of a group are written while other blocks read the samples of EVERY group and write the other groups' quantiles
+  for (int g = 0; g < G; ++g)
+    for (int h = 0; h < G; ++h)
+      if (ranges_overlap(a.out[g], a.plane[g] * Q * 4, a.src[h], a.plane[h] * N * 4) ||
+          (h != g && ranges_overlap(a.out[g], a.plane[g] * Q * 4, a.out[h], a.plane[h] * Q * 4)))
+        return MMDYN_ERR_SHAPE;
+  int blocks = 4 * split_blocks(work, G, a.first_block);            // one wavefront per block: four for each counted block
+  for (int g = 0; g <= MMDYN_FEED_GROUPS; ++g) a.first_block[g] *= 4;
+  const int N4 = (N + 3) & ~3;
+  const size_t lds = (size_t)(N4 > MMDYN_QUANTILES_MAX ? N4 : MMDYN_QUANTILES_MAX) * QUANTILE_CHUNK * sizeof(float);
+  hipLaunchKernelGGL(ensemble_quantiles_kernel, dim3(blocks), dim3(QUANTILE_CHUNK), lds, ST, a, G, Q, N);
   MMDYN_LAUNCH_CHECK();
 }
 

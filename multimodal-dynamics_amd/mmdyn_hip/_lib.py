@@ -40,6 +40,11 @@ class EnsembleGroups(ctypes.Structure):
                 ("row_len", _I * 4), ("logits", _I * 4), ("column", _I * 4)]
 
 
+class QuantileGroups(ctypes.Structure):
+    """mmdyn_quantile_groups (include/mmdyn_hip.h)."""
+    _fields_ = [("src", _P * 4), ("out", _P * 4), ("row_len", _I * 4), ("logits", _I * 4), ("lo", _I * 8), ("frac", ctypes.c_double * 8)]
+
+
 MAX_PASSES = 8
 MAX_EXPERTS = 4
 FEED_GROUPS = 4           # MMDYN_FEED_GROUPS
@@ -167,6 +172,7 @@ _SIGNATURES = {
     "mmdyn_plan_select": "pppppp" + "i" + "ppppp" + "ii" + "ff" + "pp",
     "mmdyn_gather_best": "p" + "i" + "p" + "ii" + "p",
     "mmdyn_ensemble_feed": "p" + "i" + "p" + "ii" + "p",
+    "mmdyn_ensemble_quantiles": "p" + "iiii" + "p",
     "mmdyn_plan_select_steps": "ppppppp" + "i" + "pppppppp" + "iiiii" + "ff" + "pp",
     "mmdyn_gather_best_steps": "p" + "i" + "p" + "iii" + "p",
     "mmdyn_plan_sample": "ppppppp" + "iiii" + "p",

@@ -18,6 +18,7 @@ summation order (tests/test_engine_*.py).  BatchNorm running statistics: encoder
 4 EMA updates as in the reference; decoder buffers receive the live passes' updates only (the
 reference also folds in the discarded passes) unless ``exact_running_stats=True``.
 """
+import math
 import numbers
 import os
 import torch
@@ -2496,7 +2497,16 @@ class MVAEInference:
             res.update(self._terms((tab[:, 0, 0], tab[:, 0, 1], tab[:, 1, 0]), (tv, tt, tp)), kl=tab[:, 2, 0], rows=rows)
         return res
 
-    def _rollout_ensemble(self, T, N, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
+    @staticmethod
+    def _quantile_index(quantiles, N):
+        """The order statistics of the ``linear`` quantile: h = q (N - 1) in fp64, lo = floor(h), frac = h - lo (q = 1: lo = N - 1,
+        frac = 0) -> (lo [Q] ints, frac [Q] floats), what mmdyn_ensemble_quantiles is handed."""
+        h = [float(q) * (N - 1) for q in quantiles]
+        lo = [min(int(math.floor(x)), N - 1) for x in h]
+        return lo, [x - l for x, l in zip(h, lo)]
+
+    def _rollout_ensemble(self, T, N, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav,
+                          quantiles=None):
         """N sampled trajectories per request row, sample-major (row n * B + b).  Step 0 has the structure of :meth:`_iw_score`: the
         encoders, the heads and the PoE launch ONCE on the B rows (z not requested), one [N][B][L] draw, one iw_latent launch, the
         decoders on the N * B rows; every later step is the joint forward of the N * B state rows with one [N * B][L] draw.  ONE
@@ -2504,7 +2514,9 @@ class MVAEInference:
         variance of the prediction over n plus each row's summed variance, from the same read of the decoder outputs.  With
         targets, the row kernels run with G = N passes against the one target (slots 0..N-1 of [N][B] tables, ops.ROW_GROUPS_MAX
         passes per launch) and the assembly of :meth:`_score_tail` on the N * B rows; tables [T][3][2][N][B], cleared by one
-        fill, like ``spread``."""
+        fill, like ``spread``.  With ``quantiles`` (a tuple of Q numbers in [0, 1]) ONE ensemble_quantiles launch follows each
+        step's feed: the Q order statistics per element of the same decoder outputs (the prediction, observed or not) and, with
+        targets, of the step's ``rows`` column, as a fourth group."""
         feed, iw_latent = ops.backend_op("ensemble_feed"), ops.backend_op("iw_latent")
         (B, dev), L, S = self._rows_of(visual, tactile, pose, avail), self.L, self.model.visual_decoder.image_size
         NB = N * B
@@ -2519,6 +2531,11 @@ class MVAEInference:
         if scoring:
             tab = torch.zeros(T, 3, 2, N, B, dtype=torch.float64, device=dev)
             rows = torch.empty(T, N, B, device=dev)
+        if quantiles is not None:
+            quant, Q = ops.backend_op("ensemble_quantiles"), len(quantiles)
+            q_lo, q_frac = self._quantile_index(quantiles, N)
+            qs = [torch.empty((T, Q) + s[1:], device=dev) for s in shapes] + ([] if self.use_pose else [None])
+            rows_q = torch.empty(T, Q, B, device=dev) if scoring else None
         state = [visual, tactile, pose]
         step_of = lambda t, i: None if t is None else t[i]
         rep = lambda t: None if t is None else t.repeat((N,) + (1,) * (t.dim() - 1))      # [B, ...] -> [N * B, ...], sample-major
@@ -2550,12 +2567,19 @@ class MVAEInference:
                     groups.append({"recon": pr, "obs": step_of(op, i), "out": flat(traj[2][i]), "mean": mean[2][i], "var": var[2][i],
                                    "spread": spread[i, 2], "logits": False, "column": 2})
                 feed(groups, step_of(oav, i), N, B)
+                if quantiles is not None:
+                    qg = [{"src": g["recon"], "out": qs[m][i], "logits": g["logits"]} for m, g in enumerate(groups)]
+                    if scoring:
+                        qg.append({"src": rows[i].view(NB), "out": rows_q[i], "logits": False})
+                    quant(qg, q_lo, q_frac, N, B)
                 state = [g["out"] for g in groups] + ([] if self.use_pose else [None])
         res = {"visual": traj[0], "tactile": traj[1], "pose": traj[2], "visual_mean": mean[0], "visual_var": var[0],
                "tactile_mean": mean[1], "tactile_var": var[1], "pose_mean": mean[2], "pose_var": var[2], "spread": spread,
                "means": means, "log_var": log_var, "bce_visual": None, "bce_tactile": None, "mse_pose": None, "kl": None, "rows": None}
         if scoring:
             res.update(self._terms((tab[:, 0, 0], tab[:, 0, 1], tab[:, 1, 0]), (tv, tt, tp)), kl=tab[:, 2, 0], rows=rows)
+        if quantiles is not None:
+            res.update(visual_q=qs[0], tactile_q=qs[1], pose_q=qs[2], rows_q=rows_q)
         return res
 
     def _ensemble_tail(self, N, B, v, t, pr, mu, lv, tv, tt, tp, tavail, tab, rows):
@@ -2608,7 +2632,7 @@ class MVAEInference:
 
     @torch.no_grad()
     def rollout(self, x, pose=None, steps=1, available=None, condition=None, sample=False, observed=None, observed_available=None,
-                targets=None, target_available=None, kl_weight=1.0, pose_multiplier=1000.0, samples=None):
+                targets=None, target_available=None, kl_weight=1.0, pose_multiplier=1000.0, samples=None, quantiles=None):
         """The one-step dynamics model applied to its own output ``steps`` = T times, as ONE captured graph.  With s_0 the request
         (``x``, ``pose``, ``available`` as in :meth:`forward`), for t = 0 .. T-1: the eval-mode forward of s_t (step 0 on the
         request's subset / availability table, later steps on every modality); the prediction p_{t+1} = (sigmoid(visual logits),
@@ -2648,12 +2672,36 @@ class MVAEInference:
         pose model; accumulated by atomics: equal to rounding between runs); ``means`` / ``log_var`` [T, N, B, L] (step 0: the
         request's posterior in all N slots); with targets ``bce_visual`` / ``bce_tactile`` / ``mse_pose`` / ``kl`` fp64 [T, N, B]
         and ``rows`` fp32 [T, N, B], each trajectory against the one target.  The graph key carries N.  ValueError: N no integer
-        >= 1, ``sample=False`` (N identical trajectories), or N past what 32-bit element offsets allow."""
+        >= 1, ``sample=False`` (N identical trajectories), or N past what 32-bit element offsets allow.
+
+        ``quantiles`` (with ``samples``; None: everything above, launch for launch): a sequence of 1 to 8 numbers q in [0, 1], in
+        any order, duplicates allowed, asks for the prediction BAND of the ensemble: per element, the ``linear`` quantile of numpy /
+        ``torch.quantile`` over the N samples of the PREDICTION p_{t+1} -- for every row, observed or not, as the mean and the
+        variance.  With h = q (N - 1), lo = floor(h), frac = h - lo (formed here in fp64) and s the N values in ascending order:
+        s[lo] where frac == 0, fp32(s[lo] + frac * (s[lo + 1] - s[lo])) otherwise, each fp64 operation rounded on its own; a NaN
+        sample makes the quantiles of its element NaN.  One launch per step, directly after the step's feed, in the same graph.
+        The dict then also holds ``visual_q`` / ``tactile_q`` [T, Q, B, 3, S, S], ``pose_q`` [T, Q, B, 7] (None without a pose
+        model) and, with targets, ``rows_q`` fp32 [T, Q, B] = the quantiles over the N trajectories of ``rows`` (None without
+        targets).  The graph key carries the q values.  ValueError: ``quantiles`` without ``samples``, an empty sequence or more
+        than 8 entries, a q outside [0, 1] or NaN, ``samples`` > MMDYN_QUANTILE_N_MAX = 128."""
         T, sample = self._count("steps", steps, "model applications"), bool(sample)
         if samples is not None:
             samples = self._count("samples", samples, "trajectories per row")
             if not sample:
                 raise ValueError("samples needs sample=True: the posterior-mean rollout would give N identical trajectories")
+        if quantiles is not None:
+            if samples is None:
+                raise ValueError("quantiles needs samples=N: they are taken over the N trajectories of an ensemble")
+            if isinstance(quantiles, (str, bytes)) or not hasattr(quantiles, "__len__") or not hasattr(quantiles, "__iter__") or \
+                    torch.is_tensor(quantiles) or not 1 <= len(quantiles) <= ops.QUANTILES_MAX:
+                raise ValueError(f"quantiles must be a sequence of 1 to {ops.QUANTILES_MAX} numbers in [0, 1], got {quantiles!r}")
+            for q in quantiles:
+                if isinstance(q, bool) or not isinstance(q, numbers.Real) or not 0.0 <= float(q) <= 1.0:
+                    raise ValueError(f"quantiles must be a sequence of 1 to {ops.QUANTILES_MAX} numbers in [0, 1], got {q!r} in it")
+            quantiles = tuple(float(q) for q in quantiles)
+            if samples > ops.QUANTILE_N_MAX:
+                raise ValueError(f"samples = {samples} is more than the quantiles rank per element (MMDYN_QUANTILE_N_MAX = "
+                                 f"{ops.QUANTILE_N_MAX})")
         ins, B = self._request("rollout", x, pose, available, cast=True)
         S = self.model.visual_decoder.image_size
         self._fits("steps", T, "", B, 3 * S * S, "trajectory tensor", "steps")
@@ -2686,7 +2734,10 @@ class MVAEInference:
         args = ins + [cond, avail] + obs + [oav] + tg + [tav]
         key = ("rollout", T, sample, self._pose_multiplier, per_step_cond, self._cond_key(cond)) + self._shapes(args, dtype=True)
         if samples is not None:
-            return self._run(key + (("samples", samples),), lambda *a: self._rollout_ensemble(T, samples, per_step_cond, *a), args)
+            key += (("samples", samples),)
+            if quantiles is not None:
+                key += (("quantiles", quantiles),)
+            return self._run(key, lambda *a: self._rollout_ensemble(T, samples, per_step_cond, *a, quantiles=quantiles), args)
         return self._run(key, lambda *a: self._rollout(T, sample, per_step_cond, *a), args)
 
     @torch.no_grad()

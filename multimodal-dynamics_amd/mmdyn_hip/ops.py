@@ -15,13 +15,15 @@ import os
 import torch
 
 from . import _lib
-from ._lib import PassExperts, FeedGroups, GatherGroups, EnsembleGroups, MAX_PASSES, MAX_EXPERTS, FEED_GROUPS, check
+from ._lib import PassExperts, FeedGroups, GatherGroups, EnsembleGroups, QuantileGroups, MAX_PASSES, MAX_EXPERTS, FEED_GROUPS, check
 
 ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
 DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0 = 0, 1, 2, 3, 4
 ROW_GROUPS_MAX = 8         # MMDYN_BCE_GROUPS_MAX: the passes one launch of a *_groups kernel walks over its target
 PLAN_TOP_MAX = 8           # MMDYN_PLAN_TOP_MAX: the longest list of best candidates mmdyn_plan_select_steps keeps per row
 REFIT_N_MAX = 4096         # MMDYN_REFIT_N_MAX: the candidates per row whose cost column mmdyn_plan_refit ranks in LDS
+QUANTILES_MAX = 8          # MMDYN_QUANTILES_MAX: the order statistics one mmdyn_ensemble_quantiles launch forms per element
+QUANTILE_N_MAX = 128       # MMDYN_QUANTILE_N_MAX: the samples per element that launch ranks in LDS
 
 
 def _ptr(t, dtype=torch.float32):
@@ -1360,6 +1362,52 @@ class HipBackend:
             arg.mean[g], arg.var[g], arg.spread[g] = _ptr(grp["mean"]), _ptr(grp.get("var")), _ptr(grp.get("spread"), torch.float64)
             arg.row_len[g], arg.logits[g], arg.column[g] = grp["mean"].numel() // B, int(bool(grp["logits"])), int(grp["column"])
         check(self.lib.mmdyn_ensemble_feed(ctypes.addressof(arg), len(groups), table, N, B, _stream()), "mmdyn_ensemble_feed")
+
+    def ensemble_quantiles(self, groups, lo, frac, N, B):
+        """One launch for up to FEED_GROUPS tensors: ``groups`` is a list of dicts {src, out, logits}.  src: contiguous fp32
+        [N * B, ...], sample-major (the ``recon`` of :meth:`ensemble_feed`); out: contiguous fp32 [Q, B, ...] of the same row shape,
+        overlapping no src and no other out of the call.  ``lo`` (ints in [0, N)) and ``frac`` (floats in [0, 1)), Q = len(lo) =
+        len(frac) in [1, QUANTILES_MAX]: with p = sigmoid(src) where ``logits``, src otherwise, and s the N values of an element in
+        ascending order, out[j] = s[lo[j]] where frac[j] == 0 and fp32(s[lo] + frac * (s[lo + 1] - s[lo])) otherwise, each fp64
+        operation rounded on its own.  A NaN sample makes the Q outputs of its element NaN."""
+        name, N, B = "ensemble_quantiles", int(N), int(B)
+        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
+            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
+                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
+        if B < 1 or not 1 <= N <= QUANTILE_N_MAX:
+            raise ValueError(f"mmdyn_hip: {name}: B = {B} must be positive and N = {N} lie in [1, {QUANTILE_N_MAX}]")
+        if not isinstance(lo, (list, tuple)) or not isinstance(frac, (list, tuple)) or len(lo) != len(frac) or \
+                not 1 <= len(lo) <= QUANTILES_MAX:
+            raise ValueError(f"mmdyn_hip: {name}: lo and frac must be sequences of one length in [1, {QUANTILES_MAX}]")
+        Q = len(lo)
+        for j in range(Q):
+            if isinstance(lo[j], bool) or not isinstance(lo[j], int) or not 0 <= lo[j] < N or not 0.0 <= float(frac[j]) < 1.0:
+                raise ValueError(f"mmdyn_hip: {name}: quantile {j}: lo = {lo[j]!r} must be an int in [0, N={N}) and frac = "
+                                 f"{frac[j]!r} lie in [0, 1)")
+        like = groups[0]["src"]
+        for g, grp in enumerate(groups):
+            src, out = grp["src"], grp["out"]
+            for t, rows, what in ((src, (N * B,), "src"), (out, (Q, B), "out")):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < len(rows) or \
+                        tuple(t.shape[:len(rows)]) != rows:
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor {list(rows)}[...], got "
+                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+            if src.numel() == 0 or tuple(src.shape[1:]) != tuple(out.shape[2:]) or src.device != like.device or out.device != like.device:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: src {tuple(src.shape)} on {src.device} and out {tuple(out.shape)} on "
+                                 f"{out.device} must share a non-empty row shape and the device {like.device}")
+            if max(N, Q) * (src.numel() // N) >= 1 << 31:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: {max(N, Q) * (src.numel() // N)} elements reach 2^31")
+        for g, grp in enumerate(groups):
+            for h, other in enumerate(groups):
+                if self._touch(grp["out"], other["src"]) or (h != g and self._touch(grp["out"], other["out"])):
+                    raise ValueError(f"mmdyn_hip: {name}: the out of group {g} overlaps a tensor of group {h}")
+        arg = QuantileGroups()
+        for g, grp in enumerate(groups):
+            arg.src[g], arg.out[g] = _ptr(grp["src"]), _ptr(grp["out"])
+            arg.row_len[g], arg.logits[g] = grp["src"].numel() // (N * B), int(bool(grp["logits"]))
+        for j in range(Q):
+            arg.lo[j], arg.frac[j] = lo[j], float(frac[j])
+        check(self.lib.mmdyn_ensemble_quantiles(ctypes.addressof(arg), len(groups), Q, N, B, _stream()), "mmdyn_ensemble_quantiles")
 
     # ---- importance-weighted K-sample bound (evaluation only) ----
     @staticmethod

@@ -888,7 +888,7 @@ class DynModeling(SeqModeling):
         tavail = torch.cat((steps_of(has[:, :2], torch.ones(n, 2)), torch.ones(T, n, 1, device=dev)), 2)
         return steps_of, targets, tavail
 
-    def rollout(self, data_input, data_target, steps=None, observe=(), sample=False, samples=None):
+    def rollout(self, data_input, data_target, steps=None, observe=(), sample=False, samples=None, quantiles=None):
         """The one-step predictor applied to its own output along each sequence of one loader batch (cnn-mvae; n sequences of l
         frames as flat [n*l, ...] tensors): :meth:`mmdyn_hip.engine.MVAEInference.rollout` from frame 0 of every sequence (with its
         ``data[3]`` availability) for ``steps`` <= l steps (default l), scored against the recorded sequence.  The target of step
@@ -899,7 +899,8 @@ class DynModeling(SeqModeling):
         keeps arriving after vision is lost).  ``data[4]`` per frame is the per-step condition of a ``--conditional`` model.
         Eval-mode arithmetic: the model is put in ``eval()`` for the call and goes back to the mode it was in; the engine is
         built on first use and re-packs the weights on every call.  ``samples`` = N (with ``sample=True``): an ensemble of N sampled
-        trajectories per sequence and its per-element mean / variance, as the engine's ``rollout(samples=N)`` returns them.
+        trajectories per sequence and its per-element mean / variance, as the engine's ``rollout(samples=N)`` returns them;
+        ``quantiles`` (with ``samples``): the per-element quantiles of the ensemble's prediction and of ``rows``, likewise.
         Returns clones of the engine's dict."""
         if 'mvae' not in str(self.parameters.get('model_name')):
             raise ValueError(f"rollout() serves the multimodal VAE (cnn-mvae), not {self.parameters.get('model_name')!r}")
@@ -938,7 +939,8 @@ class DynModeling(SeqModeling):
             res = eng.rollout([data[0][::l].to(dev), data[1][::l].to(dev)], pose=data[2][::l].to(dev) if use_pose else None,
                               steps=T, available=data[3][::l].to(dev), condition=cond, sample=sample, observed=observed,
                               observed_available=oavail, targets=targets, target_available=tavail, kl_weight=self._kl_weight,
-                              pose_multiplier=self._pose_multiplier, **({} if samples is None else {"samples": samples}))
+                              pose_multiplier=self._pose_multiplier, **({} if samples is None else {"samples": samples}),
+                              **({} if quantiles is None else {"quantiles": quantiles}))
             return {k: None if v is None else v.clone() for k, v in res.items()}
 
     def plan(self, data_input, data_target, candidates=None):
