@@ -900,6 +900,46 @@ int mmdyn_plan_refit(const float* cost, const float* cand, const float* mean_in,
                      float* std_out, uint8_t* elite, int* count, int K, int N, int B, int T, int cd, float alpha, float std_min,
                      void* stream);
 
+/* ---- MPPI weights and the receding horizon (MVAEInference.plan_refine(temperature=..., warm_start=...)) --------------------
+ * mmdyn_plan_refit_weighted: mmdyn_plan_refit with a weight on every elite.  Layouts, limits, the in-place allowance (mean_out /
+ * std_out may be exactly mean_in / std_in) and the error codes are those of mmdyn_plan_refit.  Per row b:
+ *   the ELITES are mmdyn_plan_refit's: the K smallest costs, ties to the lower n, a NaN never, +-Inf ordinary; K' their number.
+ *   K == N cuts nothing, so nothing is ranked: n is an elite iff cost[n][b] is no NaN.
+ *   c_min = the smallest elite cost.  In fp64, every operation rounded on its own (no fused multiply-add):
+ *     w_n = 0 for a non-elite; w_n = 1, exactly, for an elite with cost_n == c_min (c_min = +-Inf included); otherwise
+ *     w_n = exp(-(((double)cost_n - (double)c_min) / (double)temperature)) -- an elite at +Inf over a finite c_min: exp(-inf) = 0.
+ *   W = sum w_n and Q = sum w_n * w_n in ascending n; ess[b] = (float)(W * W / Q), in [1, K'], and 0 when K' == 0.
+ *   K' == 0: mean_out = mean_in, std_out = std_in, bit for bit.  Otherwise per element (t, d), over the candidates with
+ *   w_n != 0 in ascending n (a candidate of weight zero is not loaded: its Inf / NaN reach nothing):
+ *     m = (sum w_n * (double)c_n) / W;  v = (sum w_n * (((double)c_n - m) * ((double)c_n - m))) / W;  s = sqrt(v);
+ *   then mmdyn_plan_refit's blend with alpha and its fmaxf(., std_min).  Equal elite costs make every weight 1 and W = K': the
+ *   outputs then have the bits mmdyn_plan_refit writes.
+ * weight (may be null): [N][B] double, w_n for every n, zeros included; ess (may be null): [B] float.  Neither may overlap any
+ * other argument.  One block of 256 threads per row; LDS: mmdyn_plan_refit's 20 KB plus the fp64 weight column,
+ * MMDYN_REFIT_N_MAX * 8 bytes = 32 KB (52 KB static).  No atomics, one fixed summation order: the same bits in every run.  The
+ * only operation whose rounding the device's math library decides is exp (documented within 1 ulp).
+ * Checked on the host: as mmdyn_plan_refit, and a weight that is not 8-byte aligned or weight / ess overlapping anything:
+ * MMDYN_ERR_SHAPE; temperature not finite or not > 0: MMDYN_ERR_RANGE.
+ *
+ * mmdyn_plan_shift: the warm start of a horizon that has moved `shift` steps on, in one launch.  Every tensor [B][T][cd] fp32;
+ * prev_keep and keep_out (the incumbent: the previous winner) are optional and come together.  For t + shift < T:
+ *   mean_out[b][t] = prev_mean[b][t + shift];  keep_out[b][t] = prev_keep[b][t + shift];
+ *   std_out[b][t] = fmaxf(prev_std[b][t + shift], widen * init_std[b][t]), the product one fp32 multiply (no fused operation);
+ * for t + shift >= T (the tail): mean_out = keep_out = init_mean[b][t], std_out = init_std[b][t].  NaN and Inf are copied as
+ * they are; fmaxf returns its other argument where one is a NaN (a NaN prev_std gives widen * init_std, a NaN product gives
+ * prev_std) and a NaN where both are.  widen == 0 is the pure shift for non-negative std.  One element per thread, or 16-byte
+ * accesses where cd % 4 == 0 and every pointer is 16-byte aligned (the same values either way).  No LDS, no atomics.
+ * Checked on the host: prev_mean, prev_std, init_mean, init_std, mean_out or std_out null, or one of prev_keep / keep_out without
+ * the other: MMDYN_ERR_NULL; B, T or cd < 1, shift outside [0, T], widen negative or not finite, or an output overlapping an
+ * input or another output: MMDYN_ERR_SHAPE; B * T * cd >= 2^31: MMDYN_ERR_RANGE.
+ * Both added without touching an existing signature or workspace: the revision stays 6. */
+int mmdyn_plan_refit_weighted(const float* cost, const float* cand, const float* mean_in, const float* std_in, float* mean_out,
+                              float* std_out, uint8_t* elite, int* count, double* weight, float* ess, int K, int N, int B, int T,
+                              int cd, float temperature, float alpha, float std_min, void* stream);
+int mmdyn_plan_shift(const float* prev_mean, const float* prev_std, const float* prev_keep, const float* init_mean,
+                     const float* init_std, float* mean_out, float* std_out, float* keep_out, int B, int T, int cd, int shift,
+                     float widen, void* stream);
+
 /* ---- Adam (torch.optim.Adam defaults, problems.py:137-138) ----------------------------------- */
 /* state: 3 doubles {step count, step size, sqrt(bias_correction2)}, advanced on the device by this call
  * (graph-replay safe); p/g/m/v: flat fp32 buffers of n elements; g is multiplied by grad_scale first */

@@ -32,7 +32,11 @@
 //     (MVAEInference.plan_refine).  plan_sample writes an iteration's candidates mean + std * eps (slot 0: the incumbent), clamped,
 //     straight into the [T][N * B][cd] layout the steps read; plan_refit ranks a row's [N] cost column in LDS, flags the K smallest
 //     and refits mean / std over them in fp64, one block per row.
-// Memory-bound, no LDS (plan_refit: 20 KB; ensemble_quantiles: 256 bytes per sample, 32 KB at most), no scratch; no atomics except
+//   - plan_refit_weighted / plan_shift: MPPI and the receding horizon (plan_refine(temperature=..., warm_start=...)).
+//     plan_refit_weighted is plan_refit with the weight exp(-(cost - cost_min) / temperature) on every elite (K == N: nothing is
+//     ranked); plan_shift moves a previous plan's mean / std / winner `shift` steps on and fills the tail from the initial
+//     distribution, one launch in front of the loop.
+// Memory-bound, no LDS (plan_refit: 20 KB; plan_refit_weighted: 52 KB; ensemble_quantiles: 256 bytes per sample, 32 KB at most), no scratch; no atomics except
 // ensemble_feed's spread accumulator.
 #include "common.h"
 
@@ -800,6 +804,196 @@ __global__ __launch_bounds__(256) void plan_refit_kernel(const float* __restrict
   }
 }
 
+// ---- MPPI: the refit under exponential weights, and the warm start of a horizon that has moved on ----
+
+// The weighted refit's arithmetic in its written order, every operation rounded on its own (the pragma as in plan_cost).
+// w = exp(-(((double)c - (double)c_min) / (double)temperature)) for c != c_min.
+__device__ __forceinline__ double mppi_weight(float c, float c_min, float temperature) {
+#pragma clang fp contract(off)
+  const double d = (double)c - (double)c_min;
+  const double q = d / (double)temperature;
+  return exp(-q);
+}
+__device__ __forceinline__ double add_weighted(double acc, double w, double c) {
+#pragma clang fp contract(off)
+  const double p = w * c;
+  return acc + p;
+}
+__device__ __forceinline__ double add_weighted_square(double acc, double w, double c, double m) {
+#pragma clang fp contract(off)
+  const double d = c - m;
+  const double sq = d * d;
+  const double p = w * sq;
+  return acc + p;
+}
+__device__ __forceinline__ float effective_samples(double W, double Q) {
+#pragma clang fp contract(off)
+  const double ww = W * W;
+  return (float)(ww / Q);
+}
+
+constexpr int REFIT_WALK = 8;                // candidate loads of one thread in flight while it walks a weight column
+
+// plan_refit_kernel with a weight per elite: the same block, the same flags (K == N: no candidate is cut, so nothing is ranked
+// and the flag is cost == cost), then c_min = the smallest elite cost (an order-free block reduction), the fp64 weight column
+// in LDS (32 KB next to plan_refit's 20 KB: 52 KB static), W = sum w and Q = sum w * w walked by every thread in ascending n
+// from LDS broadcasts (the walk an element's sums take anyway; one order, no reduction tree), and per element the weighted
+// mean and spread over the candidates of non-zero weight only.  All weights 1 (equal elite costs): add_weighted(acc, 1, c) is
+// acc + c and W is K', so the outputs have plan_refit_kernel's bits.
+__global__ __launch_bounds__(256) void plan_refit_weighted_kernel(const float* __restrict__ cost, const float* __restrict__ cand,
+                                                                  const float* mean_in, const float* std_in, float* mean_out,
+                                                                  float* std_out, uint8_t* __restrict__ elite,
+                                                                  int* __restrict__ count, double* __restrict__ weight,
+                                                                  float* __restrict__ ess, int K, int N, int B, int T, int cd,
+                                                                  float temperature, float alpha, float std_min) {
+  __shared__ __attribute__((aligned(16))) float cost_s[MMDYN_REFIT_N_MAX];
+  __shared__ __attribute__((aligned(16))) double w_s[MMDYN_REFIT_N_MAX];
+  __shared__ uint8_t flag_s[MMDYN_REFIT_N_MAX];
+  __shared__ int part_s[4];
+  __shared__ float low_s[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int N4 = (N + 3) & ~3;
+  for (int n = tid; n < N4; n += 256) cost_s[n] = n < N ? cost[(size_t)n * B + b] : NAN;
+  __syncthreads();
+  int mine = 0;
+  float low = INFINITY;                                  // over this thread's elites; used only where K' > 0
+  for (int n = tid; n < N; n += 256) {
+    const float c = cost_s[n];
+    int ahead = 0;
+    if (K < N) {
+      for (int m = 0; m < N4; m += 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(cost_s + m);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ahead += (q[k] < c || (q[k] == c && m + k < n)) ? 1 : 0;
+      }
+    }
+    const int flag = (c == c && ahead < K) ? 1 : 0;
+    flag_s[n] = (uint8_t)flag;
+    if (elite) elite[(size_t)n * B + b] = (uint8_t)flag;
+    mine += flag;
+    if (flag && c < low) low = c;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    mine += __shfl_xor(mine, off, 64);
+    const float other = __shfl_xor(low, off, 64);
+    low = other < low ? other : low;
+  }
+  if ((tid & 63) == 0) {
+    part_s[tid >> 6] = mine;
+    low_s[tid >> 6] = low;
+  }
+  __syncthreads();
+  const int kp = part_s[0] + part_s[1] + part_s[2] + part_s[3];
+  float c_min = low_s[0];
+#pragma unroll
+  for (int k = 1; k < 4; ++k) c_min = low_s[k] < c_min ? low_s[k] : c_min;
+  if (count && tid == 0) count[b] = kp;
+  for (int n = tid; n < N; n += 256) {
+    const float c = cost_s[n];
+    double w = 0.0;
+    if (flag_s[n]) w = c == c_min ? 1.0 : mppi_weight(c, c_min, temperature);
+    w_s[n] = w;
+    if (weight) weight[(size_t)n * B + b] = w;
+  }
+  __syncthreads();
+  double W = 0.0, Q = 0.0;
+  if (kp != 0) {
+    for (int n = 0; n < N; ++n) {
+      const double w = w_s[n];
+      W += w;
+      Q = add_weighted(Q, w, w);
+    }
+  }
+  if (ess && tid == 0) ess[b] = kp == 0 ? 0.f : effective_samples(W, Q);
+  const double a = (double)alpha;
+  const size_t step = (size_t)N * B * cd;                // the floats of one step slice of cand
+  for (int e = tid; e < T * cd; e += 256) {
+    const int t = e / cd, d = e % cd;
+    const size_t o = ((size_t)b * T + t) * cd + d;
+    const float m_in = mean_in[o], s_in = std_in[o];
+    if (kp == 0) {
+      mean_out[o] = m_in;
+      std_out[o] = s_in;
+      continue;
+    }
+    const float* src = cand + (size_t)t * step + (size_t)b * cd + d;    // + n * B * cd per candidate
+    // One walk over n = 0 .. N-1 in ascending order, REFIT_WALK candidates at a time: their loads (only where the weight is
+    // not zero) are all issued before the first is folded in, so a thread waits for memory once per group, not once per
+    // candidate; the folds keep their order.  Every index into the register arrays is a compile-time constant (no scratch).
+    auto walk = [&](auto&& fold) {
+      int n = 0;
+      for (; n + REFIT_WALK <= N; n += REFIT_WALK) {
+        double w[REFIT_WALK];
+        float c[REFIT_WALK];
+#pragma unroll
+        for (int u = 0; u < REFIT_WALK; ++u) {
+          w[u] = w_s[n + u];
+          c[u] = 0.f;
+          if (w[u] != 0.0) c[u] = src[(size_t)(n + u) * B * cd];
+        }
+#pragma unroll
+        for (int u = 0; u < REFIT_WALK; ++u)
+          if (w[u] != 0.0) fold(w[u], (double)c[u]);
+      }
+      for (; n < N; ++n) {
+        const double w = w_s[n];
+        if (w != 0.0) fold(w, (double)src[(size_t)n * B * cd]);
+      }
+    };
+    double sum = 0.0;
+    walk([&](double w, double c) { sum = add_weighted(sum, w, c); });
+    const double m = sum / W;
+    double acc = 0.0;
+    walk([&](double w, double c) { acc = add_weighted_square(acc, w, c, m); });
+    const double s = sqrt(acc / W);
+    mean_out[o] = (float)blend(a, (double)m_in, m);
+    std_out[o] = fmaxf((float)blend(a, (double)s_in, s), std_min);
+  }
+}
+
+// widen * init_std as one fp32 product (the pragma as in plan_cost), then the larger of it and the shifted std.
+__device__ __forceinline__ float widened(float prev, float widen, float init) {
+#pragma clang fp contract(off)
+  const float floor = widen * init;
+  return fmaxf(prev, floor);
+}
+
+// [B][T][cd] as items of W floats (W = 4: cd % 4 == 0 and every pointer 16-byte aligned, so an item lies in one (b, t) row and the
+// shifted offset is a multiple of four as well; W = 1 otherwise), one item per thread.  Step t of the output is step t + shift of
+// the previous plan; past its end (the tail) the initial distribution.  keep / keep_out: both or neither.
+template <int W>
+__global__ __launch_bounds__(256) void plan_shift_kernel(const float* __restrict__ prev_mean, const float* __restrict__ prev_std,
+                                                         const float* __restrict__ prev_keep, const float* __restrict__ init_mean,
+                                                         const float* __restrict__ init_std, float* __restrict__ mean_out,
+                                                         float* __restrict__ std_out, float* __restrict__ keep_out, int T, int cd,
+                                                         int shift, float widen, int64_t items) {
+  const int per_row = cd / W;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t o = i * W;                             // (b * T + t) * cd + d
+    const int t = (int)((i / per_row) % T);
+    float m[W], s[W], k[W];
+    if (t + shift < T) {
+      const int64_t src = o + (int64_t)shift * cd;
+      float is[W];
+      ld_w<W>(prev_mean + src, m);
+      ld_w<W>(prev_std + src, s);
+      ld_w<W>(init_std + o, is);
+#pragma unroll
+      for (int j = 0; j < W; ++j) s[j] = widened(s[j], widen, is[j]);
+      if (keep_out) ld_w<W>(prev_keep + src, k);
+    } else {
+      ld_w<W>(init_mean + o, m);
+      ld_w<W>(init_std + o, s);
+#pragma unroll
+      for (int j = 0; j < W; ++j) k[j] = m[j];
+    }
+    st_w<W>(mean_out + o, m);
+    st_w<W>(std_out + o, s);
+    if (keep_out) st_w<W>(keep_out + o, k);
+  }
+}
+
 bool ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
   return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
@@ -1112,5 +1306,62 @@ extern "C" int mmdyn_plan_refit(const float* cost, const float* cand, const floa
   }
   hipLaunchKernelGGL(plan_refit_kernel, dim3(B), dim3(256), 0, ST, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, K, N,
                      B, T, cd, alpha, std_min);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_plan_refit_weighted(const float* cost, const float* cand, const float* mean_in, const float* std_in,
+                                         float* mean_out, float* std_out, uint8_t* elite, int* count, double* weight, float* ess,
+                                         int K, int N, int B, int T, int cd, float temperature, float alpha, float std_min,
+                                         void* stream) {
+  if (!cost || !cand || !mean_in || !std_in || !mean_out || !std_out) return MMDYN_ERR_NULL;
+  if (B < 1 || T < 1 || cd < 1 || N < 1 || N > MMDYN_REFIT_N_MAX || K < 1 || K > N) return MMDYN_ERR_SHAPE;
+  if (!(alpha >= 0.f && alpha < 1.f) || !(std_min >= 0.f) || ((uintptr_t)weight & 7)) return MMDYN_ERR_SHAPE;
+  if (!(temperature > 0.f) || temperature == INFINITY) return MMDYN_ERR_RANGE;
+  const int64_t n = (int64_t)N * B * T * cd, row = (int64_t)B * T * cd, nb = (int64_t)N * B;
+  if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  // as in mmdyn_plan_refit: mean_out / std_out may be exactly their inputs; weight and ess overlap nothing
+  struct Range { const void* p; int64_t bytes; };
+  const Range in[4] = {{cost, nb * 4}, {cand, n * 4}, {mean_in, row * 4}, {std_in, row * 4}};
+  const Range outs[6] = {{mean_out, row * 4}, {std_out, row * 4}, {elite, nb}, {count, (int64_t)B * 4}, {weight, nb * 8},
+                         {ess, (int64_t)B * 4}};
+  for (int i = 0; i < 6; ++i) {
+    if (!outs[i].p) continue;
+    for (int j = 0; j < 4; ++j)
+      if (!(i < 2 && j == i + 2 && outs[i].p == in[j].p) && ranges_overlap(outs[i].p, outs[i].bytes, in[j].p, in[j].bytes))
+        return MMDYN_ERR_SHAPE;
+    for (int j = i + 1; j < 6; ++j)
+      if (outs[j].p && ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return MMDYN_ERR_SHAPE;
+  }
+  hipLaunchKernelGGL(plan_refit_weighted_kernel, dim3(B), dim3(256), 0, ST, cost, cand, mean_in, std_in, mean_out, std_out, elite,
+                     count, weight, ess, K, N, B, T, cd, temperature, alpha, std_min);
+  MMDYN_LAUNCH_CHECK();
+}
+
+extern "C" int mmdyn_plan_shift(const float* prev_mean, const float* prev_std, const float* prev_keep, const float* init_mean,
+                                const float* init_std, float* mean_out, float* std_out, float* keep_out, int B, int T, int cd,
+                                int shift, float widen, void* stream) {
+  if (!prev_mean || !prev_std || !init_mean || !init_std || !mean_out || !std_out || (prev_keep == nullptr) != (keep_out == nullptr))
+    return MMDYN_ERR_NULL;
+  if (B < 1 || T < 1 || cd < 1 || shift < 0 || shift > T || !(widen >= 0.f) || widen == INFINITY) return MMDYN_ERR_SHAPE;
+  const int64_t n = (int64_t)B * T * cd;
+  if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  // every output is written while other threads read every input: no aliasing
+  const float* in[5] = {prev_mean, prev_std, prev_keep, init_mean, init_std};
+  float* outs[3] = {mean_out, std_out, keep_out};
+  for (int i = 0; i < 3; ++i) {
+    if (!outs[i]) continue;
+    for (int j = 0; j < 5; ++j)
+      if (in[j] && ranges_overlap(outs[i], n * 4, in[j], n * 4)) return MMDYN_ERR_SHAPE;
+    for (int j = i + 1; j < 3; ++j)
+      if (outs[j] && ranges_overlap(outs[i], n * 4, outs[j], n * 4)) return MMDYN_ERR_SHAPE;
+  }
+  const uintptr_t ptrs = (uintptr_t)prev_mean | (uintptr_t)prev_std | (uintptr_t)prev_keep | (uintptr_t)init_mean |
+                         (uintptr_t)init_std | (uintptr_t)mean_out | (uintptr_t)std_out | (uintptr_t)keep_out;
+  if ((ptrs & 15) == 0 && cd % 4 == 0)
+    hipLaunchKernelGGL(plan_shift_kernel<4>, dim3(ew_grid(n / 4)), dim3(256), 0, ST, prev_mean, prev_std, prev_keep, init_mean,
+                       init_std, mean_out, std_out, keep_out, T, cd, shift, widen, n / 4);
+  else
+    hipLaunchKernelGGL(plan_shift_kernel<1>, dim3(ew_grid(n)), dim3(256), 0, ST, prev_mean, prev_std, prev_keep, init_mean, init_std,
+                       mean_out, std_out, keep_out, T, cd, shift, widen, n);
   MMDYN_LAUNCH_CHECK();
 }

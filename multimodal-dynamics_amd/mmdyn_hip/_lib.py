@@ -177,6 +177,8 @@ _SIGNATURES = {
     "mmdyn_gather_best_steps": "p" + "i" + "p" + "iii" + "p",
     "mmdyn_plan_sample": "ppppppp" + "iiii" + "p",
     "mmdyn_plan_refit": "pppppppp" + "iiiii" + "ff" + "p",
+    "mmdyn_plan_refit_weighted": "pppppppppp" + "iiiii" + "fff" + "p",
+    "mmdyn_plan_shift": "pppppppp" + "iiii" + "f" + "p",
 }
 _CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "Q": _Q}
 

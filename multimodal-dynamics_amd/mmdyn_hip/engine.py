@@ -18,6 +18,7 @@ summation order (tests/test_engine_*.py).  BatchNorm running statistics: encoder
 4 EMA updates as in the reference; decoder buffers receive the live passes' updates only (the
 reference also folds in the discarded passes) unless ``exact_running_stats=True``.
 """
+import collections.abc
 import math
 import numbers
 import os
@@ -2332,15 +2333,20 @@ class MVAEInference:
                ("candidates", N, per_row)) + self._shapes(ins + tg + [weight]) + self._shapes((avail, tavail), "avail")
         return self._run(key, lambda *a: self._plan_rollout(N, T, Tg, sample, top, *a), args)
 
-    def _plan_refine(self, N, K, I, T, Tg, sample, alpha, std_min, visual, tactile, pose, gv, gt, gp, init_mean, init_std, lo, hi,
-                     avail, tavail, weight):
+    def _plan_refine(self, N, K, I, T, Tg, sample, alpha, std_min, temperature, warm, visual, tactile, pose, gv, gt, gp, init_mean,
+                     init_std, lo, hi, avail, tavail, weight, prev_mean=None, prev_std=None, prev_keep=None):
         """The cross-entropy method on the horizon planner, I iterations in one captured region.  Once per request: the trunks and
         the pose heads on the B rows (:meth:`_trunks`).  Per iteration: one [N][B][T][cd] draw and its commit, one plan_sample (slot
         0 = the previous iteration's winner), one fill of the tables, the steps of :meth:`_plan_rollout` from the image heads on,
         one plan_select_steps and one plan_refit (in place from the second iteration on).  Every buffer is allocated once; the
         winner's cost and the elite count of iteration i are written straight into row i of ``history`` / ``elite_count``.  One
-        gather_best_steps on the last iteration's trajectories closes the request."""
-        select, gather, sample_op, refit = (ops.backend_op(k) for k in ("plan_select_steps", "gather_best_steps", "plan_sample", "plan_refit"))
+        gather_best_steps on the last iteration's trajectories closes the request.  ``temperature`` (MPPI): every refit is
+        plan_refit_weighted, which also writes row i of ``ess`` and the [N][B] weights.  ``warm`` = (shift, widen): one plan_shift in
+        front of the loop writes ``mean`` / ``std`` and the incumbent of round 0 from the previous plan; round 0 then samples from
+        them and refits in place."""
+        select, gather, sample_op, refit = (ops.backend_op(k) for k in ("plan_select_steps", "gather_best_steps", "plan_sample",
+                                                                        "plan_refit" if temperature is None else "plan_refit_weighted"))
+        shift_op = None if warm is None else ops.backend_op("plan_shift")
         ops.backend_op("rollout_feed")
         ops.backend_op("concat_condition_tiled")        # (a backend without the join: an error before anything is launched)
         (B, dev), L, S, cd = self._rows_of(visual, tactile, pose, avail), self.L, self.model.visual_decoder.image_size, self.condition_dim
@@ -2356,21 +2362,32 @@ class MVAEInference:
         best, best_cond = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, T, cd, device=dev)
         history, count = torch.empty(I, B, device=dev), torch.empty(I, B, dtype=torch.int32, device=dev)
         avail_rows = None if avail is None else avail.repeat(N, 1)
+        extra, keep0 = {}, None
+        if temperature is not None:
+            extra = {"ess": torch.empty(I, B, device=dev), "weight": torch.empty(N, B, dtype=torch.float64, device=dev)}
+        if warm is not None:
+            keep0 = torch.empty(B, T, cd, device=dev)
         with self._index_scope():
             trunks = self._trunks(visual, tactile, pose)
             if trunks[2] is not None:
                 trunks[2] = trunks[2].repeat(N, 1)                    # the pose heads see no condition: their N * B rows once
             step0 = lambda c_0: self._heads_of(trunks, c_0, x_rows=B)
+            if warm is not None:
+                shift_op(prev_mean, prev_std, prev_keep, init_mean, init_std, mean, std, keep0, B, T, warm[0], warm[1])
             for i in range(I):
                 eps = self.noise.eps((N, B, T, cd), dev)
                 self.noise.commit()
-                m_in, s_in = (init_mean, init_std) if i == 0 else (mean, std)
-                sample_op(m_in, s_in, eps, None if i == 0 else best_cond, lo, hi, cand, N, B, T)
+                m_in, s_in = (init_mean, init_std) if i == 0 and warm is None else (mean, std)
+                sample_op(m_in, s_in, eps, keep0 if i == 0 else best_cond, lo, hi, cand, N, B, T)
                 tab.zero_()
                 self._candidate_steps_forward(N, T, Tg, sample, B, dev, step0, cand, avail_rows, gv, gt, gp, traj, means, log_var, tab)
                 select(tab[:2] if gv is not None or gt is not None else None, tab[2] if gp is not None else None, kl, tavail, weight,
                        cand, cost, step_cost, best, history[i], best_cond, None, None, N, B, T, Tg, self._pose_multiplier, 1.0, self._klw)
-                refit(cost, cand, m_in, s_in, mean, std, None, count[i], K, N, B, T, alpha, std_min)
+                if temperature is None:
+                    refit(cost, cand, m_in, s_in, mean, std, None, count[i], K, N, B, T, alpha, std_min)
+                else:
+                    refit(cost, cand, m_in, s_in, mean, std, None, count[i], extra["weight"], extra["ess"][i], K, N, B, T, temperature,
+                          alpha, std_min)
         outs = [{"src": x, "out": torch.empty((T, B) + tuple(x.shape[2:]), device=dev), "logits": False} for x in traj if x is not None]
         gather(outs, best, N, B, T)
         split = lambda x: None if x is None else x.view((T, N, B) + tuple(x.shape[2:]))
@@ -2378,12 +2395,12 @@ class MVAEInference:
                 "trajectory": [g["out"] for g in outs] + ([] if self.use_pose else [None]),
                 "visual": split(traj[0]), "tactile": split(traj[1]), "pose": split(traj[2]),
                 **self._terms(tab[:3], (gv, gt, gp)), "kl": kl, "means": split(means), "log_var": split(log_var),
-                "mean": mean, "std": std, "candidates": split(cand), "history": history, "elite_count": count}
+                "mean": mean, "std": std, "candidates": split(cand), "history": history, "elite_count": count, **extra}
 
     @torch.no_grad()
     def plan_refine(self, x, pose=None, steps=1, goal=None, init_mean=None, init_std=None, candidates=64, elites=8, iterations=4,
                     alpha=0.0, std_min=0.0, bounds=None, step_weight=None, kl_weight=0.0, pose_multiplier=1000.0, available=None,
-                    goal_available=None, sample=False):
+                    goal_available=None, sample=False, temperature=None, warm_start=None, shift=1, widen=0.0):
         """:meth:`plan_rollout` with the candidates made and refined on the device: the cross-entropy method (CEM) over a horizon,
         for models with real-valued conditions.  A distribution N(mean, std^2) over condition sequences [T, condition_dim] per row
         starts at ``init_mean`` / ``init_std``; each of ``iterations`` = I rounds draws ``candidates`` = N sequences per row from
@@ -2404,7 +2421,23 @@ class MVAEInference:
         The Philox stream: round i draws its [N, B, T, cd] candidate block first, then (``sample=True``) the T latent blocks of its
         steps.  With n_c = ceil(N B T cd / 4), n_l = ceil(B L / 4) and per = n_c + (T n_l if sample else 0), round i of eager call c
         (on an engine that served nothing else) draws its candidates at counter (c I + i) per and the latent block of step t at
-        (c I + i) per + n_c + t n_l.  The draw of slot 0 is taken and not used.
+        (c I + i) per + n_c + t n_l.  The draw of slot 0 is taken and not used.  ``temperature`` and ``warm_start`` change none of
+        this.
+
+        ``temperature`` (a number > 0, rounded to fp32; None: the plain CEM above): MPPI.  Every refit weighs elite n of a row by
+        w_n = exp(-(cost_n - cost_min) / temperature) in fp64 (mmdyn_plan_refit_weighted): mean and std become the weighted mean
+        and the weighted population standard deviation over the ``elites`` = K cheapest; ``elites=candidates`` is pure MPPI, which
+        ranks nothing.  Equal elite costs give the bits of CEM.  The result gains ``ess`` fp32 [I, B], each round's effective
+        sample size (sum w)^2 / sum w^2 in [1, K'] (0 when no cost was a number), and ``weight`` fp64 [N, B], the last round's
+        weights; the key gains ("mppi", temperature).
+
+        ``warm_start`` (a mapping with ``mean``, ``std`` and ``best_condition``, floating point [B, T, condition_dim] each -- the
+        dict an earlier call returned qualifies; static inputs of the graph): the receding horizon.  One mmdyn_plan_shift in front
+        of the loop moves the previous plan ``shift`` steps on (an integer in [0, T]): step t of the new distribution and of round
+        0's incumbent is step t + shift of the previous ``mean`` / ``std`` / ``best_condition``, the std not below ``widen`` *
+        ``init_std`` (``widen`` >= 0, rounded to fp32); the last ``shift`` steps are ``init_mean`` / ``init_std`` (which stay
+        required) with the incumbent at ``init_mean``.  Round 0 samples from that, so the previous winner is a candidate again.
+        The key gains ("warm", shift, widen).
 
         Returns a dict of the graph's static outputs (copy what must survive the next call of the same shapes): everything
         :meth:`plan_rollout` returns (without ``top``), for the LAST round; ``mean`` / ``std`` fp32 [B, T, condition_dim], after the
@@ -2412,8 +2445,10 @@ class MVAEInference:
         best cost; ``elite_count`` int32 [I, B], the elites each refit found (< K when fewer costs were no NaN; 0 leaves the
         distribution as it was).  ValueError: what :meth:`plan_rollout` refuses, a categorical or unconditional model, N outside
         [1, 4096], K outside [1, N], I < 1, ``alpha`` outside [0, 1), ``std_min`` < 0, wrong shapes or dtypes of ``init_mean`` /
-        ``init_std`` / ``bounds``.  Out of scope: MPPI weights, categorical distributions, a receding-horizon shift helper,
-        observations inside a plan, ``loss_mask``."""
+        ``init_std`` / ``bounds``, a ``temperature`` that is no finite number > 0 in fp32, a ``warm_start`` that is no such
+        mapping, ``shift`` outside [0, T], ``widen`` < 0, or ``shift`` / ``widen`` away from their defaults without ``warm_start``.
+        Out of scope: categorical distributions, observations inside a plan, ``loss_mask``, a temperature scaled by the cost
+        range, weights in :meth:`plan_rollout`'s ``top``."""
         if not self.conditional:
             raise ValueError("plan_refine refits a distribution over conditions: it was asked of an unconditional model")
         if self.categorical:
@@ -2433,6 +2468,18 @@ class MVAEInference:
         alpha, std_min = float(torch.tensor(float(alpha), dtype=torch.float32)), float(torch.tensor(float(std_min), dtype=torch.float32))
         if not alpha < 1.0:
             raise ValueError("alpha rounds to 1.0 in fp32: it must lie in [0, 1)")
+        as_f32 = lambda v: float(torch.tensor(float(v), dtype=torch.float32))
+        if temperature is not None:
+            if isinstance(temperature, bool) or not isinstance(temperature, numbers.Real) or not 0.0 < as_f32(temperature) < float("inf"):
+                raise ValueError(f"temperature must be None (CEM) or a number that is finite and > 0 in fp32 (MPPI), got {temperature!r}")
+            temperature = as_f32(temperature)
+        if isinstance(shift, bool) or not isinstance(shift, numbers.Integral) or not 0 <= shift <= T:
+            raise ValueError(f"shift must be an integer in [0, steps = {T}] (the steps the horizon has moved on), got {shift!r}")
+        if isinstance(widen, bool) or not isinstance(widen, numbers.Real) or not 0.0 <= as_f32(widen) < float("inf"):
+            raise ValueError(f"widen must be a finite number >= 0 (the floor of the shifted std, in units of init_std), got {widen!r}")
+        shift, widen = int(shift), as_f32(widen)
+        if warm_start is None and (shift != 1 or widen != 0.0):
+            raise ValueError(f"shift = {shift} and widen = {widen} move a previous plan on: they need warm_start")
         ins, B = self._request("plan_refine", x, pose, available, cast=True)
         S, cd = self.model.visual_decoder.image_size, self.condition_dim
         most = min(((1 << 31) - 1) // (T * B * 3 * S * S), ((1 << 31) - 1) // (B * self._decoder_row()))
@@ -2451,14 +2498,29 @@ class MVAEInference:
                     torch.is_tensor(t) and t.dtype.is_floating_point and tuple(t.shape) == (cd,) for t in bounds):
                 raise ValueError(f"bounds must be a pair (lo, hi) of floating-point tensors [{cd}] or None")
             lo, hi = (t.detach().to(device=self.dev, dtype=torch.float32).contiguous() for t in bounds)
+        prev = []
+        if warm_start is not None:
+            if not isinstance(warm_start, collections.abc.Mapping) or not all(k in warm_start for k in ("mean", "std", "best_condition")):
+                raise ValueError("warm_start must be a mapping with mean, std and best_condition (the result of an earlier plan_refine)")
+            for name in ("mean", "std", "best_condition"):
+                t = warm_start[name]
+                if not torch.is_tensor(t) or not t.dtype.is_floating_point or tuple(t.shape) != (B, T, cd):
+                    raise ValueError(f"warm_start[{name!r}] must be a floating-point tensor [B={B}, T={T}, {cd}], got "
+                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+                prev.append(t.detach().to(device=self.dev, dtype=torch.float32).contiguous())
         tg, tavail, weight, Tg = self._horizon_goal("plan_refine", goal, goal_available, step_weight, T, B)
         self._set_weights(kl_weight, pose_multiplier)
         sample = bool(sample)
         avail = self._availability(available, B)
-        args = ins + tg + dist + [lo, hi, avail, tavail, weight]
+        args = ins + tg + dist + [lo, hi, avail, tavail, weight] + prev
         key = ("plan_refine", I, N, K, T, Tg, sample, alpha, std_min, self._pose_multiplier, bounds is not None) + \
             self._shapes(ins + tg + dist + [weight]) + self._shapes((avail, tavail), "avail")
-        return self._run(key, lambda *a: self._plan_refine(N, K, I, T, Tg, sample, alpha, std_min, *a), args)
+        if temperature is not None:
+            key += (("mppi", temperature),)
+        if warm_start is not None:
+            key += (("warm", shift, widen),)
+        warm = None if warm_start is None else (shift, widen)
+        return self._run(key, lambda *a: self._plan_refine(N, K, I, T, Tg, sample, alpha, std_min, temperature, warm, *a), args)
 
     def _rollout(self, T, sample, per_step_cond, visual, tactile, pose, cond, avail, ov, ot, op, oav, tv, tt, tp, tav):
         """T forwards in a row, each followed by ONE feed launch that writes the next state into its trajectory slot, where the

@@ -1318,6 +1318,84 @@ class HipBackend:
         ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
         check(self.lib.mmdyn_plan_refit(*ptrs, K, N, B, T, cd, alpha, std_min, _stream()), "mmdyn_plan_refit")
 
+    # ---- MPPI weights and the receding horizon ----
+    def plan_refit_weighted(self, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, weight, ess, K, N, B, T,
+                            temperature=1.0, alpha=0.0, std_min=0.0):
+        """:meth:`plan_refit` with the weight w_n = exp(-(cost_n - c_min) / temperature) on every elite (c_min: the smallest elite
+        cost; exactly 1 where cost_n == c_min, 0 for a non-elite; fp64, each operation rounded on its own).  K == N ranks nothing:
+        every candidate whose cost is no NaN is an elite.  W = sum w, Q = sum w^2 in ascending n; m = (sum w c) / W, s =
+        sqrt((sum w (c - m)^2) / W) over the candidates of non-zero weight, then plan_refit's blend and floor; K' = 0: the inputs,
+        bit for bit.  Equal elite costs: the bits of plan_refit.  weight: fp64 [N][B] or None; ess: fp32 [B] = W^2 / Q (0 when
+        K' = 0) or None; neither overlaps anything.  Everything else as in plan_refit."""
+        name, K, N, B, T = "plan_refit_weighted", int(K), int(N), int(B), int(T)
+        temperature, alpha, std_min = float(temperature), float(alpha), float(std_min)
+        if B < 1 or T < 1 or not 1 <= N <= REFIT_N_MAX or not 1 <= K <= N:
+            raise ValueError(f"mmdyn_plan_refit_weighted: B = {B} and T = {T} must be positive, N = {N} lie in [1, {REFIT_N_MAX}] and "
+                             f"K = {K} in [1, N]")
+        if not 0.0 <= alpha < 1.0 or not std_min >= 0.0:
+            raise ValueError(f"mmdyn_plan_refit_weighted: alpha = {alpha} must lie in [0, 1) and std_min = {std_min} be >= 0")
+        if not 0.0 < temperature < float("inf"):
+            raise ValueError(f"mmdyn_plan_refit_weighted: temperature = {temperature} must be finite and > 0")
+        if any(t is None for t in (cost, cand, mean_in, std_in, mean_out, std_out)):
+            raise ValueError("mmdyn_plan_refit_weighted: cost, cand, mean_in, std_in, mean_out and std_out are required")
+        if not torch.is_tensor(cand) or cand.dim() != 3 or cand.shape[2] < 1:
+            raise ValueError(f"mmdyn_plan_refit_weighted: cand must be fp32 [T = {T}][N * B = {N * B}][cd], got "
+                             f"{tuple(cand.shape) if torch.is_tensor(cand) else type(cand).__name__}")
+        cd = cand.shape[2]
+        if N * B * T * cd >= 1 << 31:
+            raise ValueError(f"mmdyn_plan_refit_weighted: N * B * T * cd = {N * B * T * cd} elements reach 2^31")
+        f32 = torch.float32
+        specs = ((cost, (N, B), "cost", f32), (cand, (T, N * B, cd), "cand", f32), (mean_in, (B, T, cd), "mean_in", f32),
+                 (std_in, (B, T, cd), "std_in", f32), (mean_out, (B, T, cd), "mean_out", f32), (std_out, (B, T, cd), "std_out", f32),
+                 (elite, (N, B), "elite", torch.uint8), (count, (B,), "count", torch.int32),
+                 (weight, (N, B), "weight", torch.float64), (ess, (B,), "ess", f32))
+        self._check_tables(name, *specs)
+        ins, outs = specs[:4], specs[4:]
+        for i, (o, _, what, _) in enumerate(outs):
+            for j, (t, _, other, _) in enumerate(ins):
+                own = i < 2 and j == i + 2 and o.data_ptr() == t.data_ptr()
+                if not own and self._touch(o, t):
+                    raise ValueError(f"mmdyn_plan_refit_weighted: {what} overlaps {other} (an output may only be exactly its own input)")
+            for p, _, other, _ in outs[i + 1:]:
+                if self._touch(o, p):
+                    raise ValueError(f"mmdyn_plan_refit_weighted: {what} overlaps {other}")
+        ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
+        check(self.lib.mmdyn_plan_refit_weighted(*ptrs, K, N, B, T, cd, temperature, alpha, std_min, _stream()),
+              "mmdyn_plan_refit_weighted")
+
+    def plan_shift(self, prev_mean, prev_std, prev_keep, init_mean, init_std, mean_out, std_out, keep_out, B, T, shift=1, widen=0.0):
+        """The warm start of a horizon that has moved ``shift`` steps on.  Every tensor fp32 [B][T][cd]; prev_keep / keep_out: both or
+        neither.  For t + shift < T: mean_out[b][t] = prev_mean[b][t + shift], keep_out likewise, std_out[b][t] =
+        fmax(prev_std[b][t + shift], widen * init_std[b][t]) (one fp32 product; fmax takes the other side of a NaN); past that, the
+        tail: mean_out = keep_out = init_mean[b][t], std_out = init_std[b][t].  No output overlaps an input or another output."""
+        name, B, T, shift, widen = "plan_shift", int(B), int(T), int(shift), float(widen)
+        if B < 1 or T < 1 or not 0 <= shift <= T:
+            raise ValueError(f"mmdyn_plan_shift: B = {B} and T = {T} must be positive and shift = {shift} lie in [0, T]")
+        if not 0.0 <= widen < float("inf"):
+            raise ValueError(f"mmdyn_plan_shift: widen = {widen} must be finite and >= 0")
+        if any(t is None for t in (prev_mean, prev_std, init_mean, init_std, mean_out, std_out)):
+            raise ValueError("mmdyn_plan_shift: prev_mean, prev_std, init_mean, init_std, mean_out and std_out are required")
+        if (prev_keep is None) != (keep_out is None):
+            raise ValueError("mmdyn_plan_shift: prev_keep and keep_out come together")
+        if not torch.is_tensor(prev_mean) or prev_mean.dim() != 3 or prev_mean.shape[2] < 1:
+            raise ValueError(f"mmdyn_plan_shift: prev_mean must be fp32 [B = {B}][T = {T}][cd], got "
+                             f"{tuple(prev_mean.shape) if torch.is_tensor(prev_mean) else type(prev_mean).__name__}")
+        cd = prev_mean.shape[2]
+        if B * T * cd >= 1 << 31:
+            raise ValueError(f"mmdyn_plan_shift: B * T * cd = {B * T * cd} elements reach 2^31")
+        f32 = torch.float32
+        specs = tuple((t, (B, T, cd), what, f32) for t, what in (
+            (prev_mean, "prev_mean"), (prev_std, "prev_std"), (prev_keep, "prev_keep"), (init_mean, "init_mean"), (init_std, "init_std"),
+            (mean_out, "mean_out"), (std_out, "std_out"), (keep_out, "keep_out")))
+        self._check_tables(name, *specs)
+        ins, outs = specs[:5], specs[5:]
+        for i, (o, _, what, _) in enumerate(outs):
+            for t, _, other, _ in ins + outs[i + 1:]:
+                if self._touch(o, t):
+                    raise ValueError(f"mmdyn_plan_shift: {what} overlaps {other}")
+        ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
+        check(self.lib.mmdyn_plan_shift(*ptrs, B, T, cd, shift, widen, _stream()), "mmdyn_plan_shift")
+
     # ---- ensemble rollout: the N * B decoder rows of a step -> the N * B next states + the ensemble's statistics ----
     def ensemble_feed(self, groups, obs_avail, N, B):
         """One launch for up to FEED_GROUPS tensors: ``groups`` is a list of dicts {recon, obs | None, out, mean, var | None,

@@ -1030,14 +1030,15 @@ class DynModeling(SeqModeling):
         return out
 
     def plan_refine(self, data_input, data_target, steps=None, candidates=64, elites=8, iterations=4, init_mean=None, init_std=None,
-                    bounds=None, alpha=0.0, std_min=0.0, step_weight=None, sample=False):
+                    bounds=None, alpha=0.0, std_min=0.0, step_weight=None, sample=False, temperature=None, warm_start=None, shift=1,
+                    widen=0.0):
         """The shock sequence that takes frame 0 of each of the n sequences of one loader batch along its recorded continuation,
         searched by the cross-entropy method (cnn-mvae, ``--conditional`` with real-valued shocks):
         :meth:`mmdyn_hip.engine.MVAEInference.plan_refine` on the request :meth:`plan_rollout` builds, every step scored, the
         problem's KL weight and pose multiplier.  ``init_mean`` / ``init_std`` default to the per-(step, dimension) mean and
         population standard deviation of the batch's n recorded shock sequences, ``bounds`` to their per-dimension minimum and
-        maximum; ``candidates`` / ``elites`` / ``iterations`` / ``alpha`` / ``std_min`` / ``step_weight`` / ``sample``: as the
-        engine takes them.  Eval-mode arithmetic as in :meth:`plan`.  Returns clones of the engine's dict plus ``recorded``."""
+        maximum; ``candidates`` / ``elites`` / ``iterations`` / ``alpha`` / ``std_min`` / ``step_weight`` / ``sample`` / ``temperature`` (MPPI weights) /
+        ``warm_start`` / ``shift`` / ``widen`` (the previous result, moved on: a receding horizon): as the engine takes them.  Eval-mode arithmetic as in :meth:`plan`.  Returns clones of the engine's dict plus ``recorded``."""
         T, start, goal, goal_has, recorded = self._horizon_batch('plan_refine', data_input, data_target, steps)
         if self._model.categorical_conditions:
             raise ValueError("plan_refine() refits a distribution over real-valued shocks; a categorical model is out of scope")
@@ -1053,5 +1054,5 @@ class DynModeling(SeqModeling):
             res = eng.plan_refine(steps=T, goal=goal, init_mean=init_mean, init_std=init_std, candidates=candidates, elites=elites,
                                   iterations=iterations, alpha=alpha, std_min=std_min, bounds=bounds, step_weight=step_weight,
                                   kl_weight=self._kl_weight, pose_multiplier=self._pose_multiplier, goal_available=goal_has,
-                                  sample=sample, **start)
+                                  sample=sample, temperature=temperature, warm_start=warm_start, shift=shift, widen=widen, **start)
             return self._cloned(res, recorded)
