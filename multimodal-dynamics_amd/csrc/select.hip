@@ -20,7 +20,8 @@
 //   - plan_select_steps / gather_best_steps: N candidate condition SEQUENCES per request rolled out over T steps
 //     (MVAEInference.plan_rollout).  plan_select_steps forms plan_select's cost per scored step, the weighted total over the steps
 //     in fp64 and each row's winner (and, on request, the K best); gather_best_steps copies the winner's rows of all T steps out of
-//     the [T][N * B] trajectory tensors in one launch, with gather_best's element scheme on every step slice.
+//     the [T][N * B] trajectory tensors in one launch, with gather_best's element scheme on every step slice.  One kernel per
+//     pair: plan_select and gather_best are the T = 1 launches of these two.
 //   - ensemble_feed: the rollout feed of N sampled trajectories per request row (MVAEInference.rollout(samples=N)).  The N * B
 //     decoder rows of a step become the N * B next states under observations that exist once per request row, and the same read
 //     of the logits leaves the ensemble's per-element mean and variance and each row's summed variance.  An element scheme of
@@ -34,10 +35,10 @@
 //     and refits mean / std over them in fp64, one block per row.
 //   - plan_refit_weighted / plan_shift: MPPI and the receding horizon (plan_refine(temperature=..., warm_start=...)).
 //     plan_refit_weighted is plan_refit with the weight exp(-(cost - cost_min) / temperature) on every elite (K == N: nothing is
-//     ranked); plan_shift moves a previous plan's mean / std / winner `shift` steps on and fills the tail from the initial
-//     distribution, one launch in front of the loop.
-// Memory-bound, no LDS (plan_refit: 20 KB; plan_refit_weighted: 52 KB; ensemble_quantiles: 256 bytes per sample, 32 KB at most), no scratch; no atomics except
-// ensemble_feed's spread accumulator.
+//     ranked) -- the two instantiations of one kernel body; plan_shift moves a previous plan's mean / std / winner `shift` steps on
+//     and fills the tail from the initial distribution, one launch in front of the loop.
+// Memory-bound, no LDS (except plan_refit_kernel: 20 KB in its unweighted instantiation, 52 KB in the weighted one; and
+// ensemble_quantiles: 256 bytes per sample, 32 KB at most), no scratch; no atomics except ensemble_feed's spread accumulator.
 #include "common.h"
 
 namespace {
@@ -115,11 +116,6 @@ __global__ __launch_bounds__(256) void rollout_feed_kernel(const FeedArgs a, con
   select_rows(a.obs[g], a.recon[g], avail, a.column[g], a.out[g], a.n[g], a.n4[g], a.row_len[g], a.logits[g],
               (int64_t)((int)blockIdx.x - a.first_block[g]) * blockDim.x + threadIdx.x,
               (int64_t)(a.first_block[g + 1] - a.first_block[g]) * blockDim.x);
-}
-
-bool overlap(const float* p, const float* q, int64_t n) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q, bytes = (uintptr_t)n * sizeof(float);
-  return q != nullptr && a < b + bytes && b < a + bytes;
 }
 
 // ---- ensemble rollout: the feed of N trajectories per request row, with the ensemble's statistics from the same read ----
@@ -443,45 +439,6 @@ __device__ __forceinline__ double plan_cost(double bce_v, double bce_t, double m
   return (rec + pose) + klt;
 }
 
-// One thread per row b walks the candidates n = 0 .. N-1, so the table reads coalesce across b.  A table that is not given, and an
-// absent (row, term), enter plan_cost as +0.0 (x + 0.0 == x for every x the tables hold).  Selection on the fp64 value: smallest
-// wins, the first of equals wins, NaN never wins (every comparison with it is false), +-Inf are ordinary values.
-__global__ __launch_bounds__(256) void plan_select_kernel(double* __restrict__ bce, double* __restrict__ mse,
-                                                          const double* __restrict__ kl, const uint32_t* __restrict__ tavail,
-                                                          const float* __restrict__ cand, const int64_t* __restrict__ cand_idx, int cd,
-                                                          float* __restrict__ cost, int* __restrict__ best,
-                                                          float* __restrict__ best_cost, float* __restrict__ best_cond,
-                                                          int64_t* __restrict__ best_idx, int N, int B, float pose_multiplier,
-                                                          float kl_weight_arg, const float* __restrict__ kl_weight_dev) {
-  const float kl_weight = kl_weight_dev ? kl_weight_arg * kl_weight_dev[0] : kl_weight_arg;
-  const double pm = (double)pose_multiplier, klw = (double)kl_weight;
-  const size_t NB = (size_t)N * B;
-  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
-    const uint32_t word = tavail ? tavail[b] : ALL_PRESENT;
-    const bool has0 = has(word, 0), has1 = has(word, 1), has2 = has(word, 2);
-    double low = NAN;
-    int win = -1;
-    for (int n = 0; n < N; ++n) {
-      const size_t o = (size_t)n * B + b;
-      const double v = bce && has0 ? bce[o] : 0.0, t = bce && has1 ? bce[NB + o] : 0.0, p = mse && has2 ? mse[o] : 0.0;
-      if (bce && !has0) bce[o] = 0.0;
-      if (bce && !has1) bce[NB + o] = 0.0;
-      if (mse && !has2) mse[o] = 0.0;
-      const double c = plan_cost(v, t, p, kl[o], pm, klw);
-      cost[o] = (float)c;
-      if (c == c && (win < 0 || c < low)) {
-        low = c;
-        win = n;
-      }
-    }
-    best[b] = win;
-    best_cost[b] = (float)low;
-    if (best_idx) best_idx[b] = win < 0 ? (int64_t)-1 : cand_idx[(size_t)win * B + b];
-    if (best_cond)
-      for (int j = 0; j < cd; ++j) best_cond[(size_t)b * cd + j] = win < 0 ? NAN : cand[((size_t)win * B + b) * cd + j];
-  }
-}
-
 // out [B][row_len] = f(src[best[b] * B + b]) over the flat out array, in the element scheme of select_rows with no observed side:
 // quads [0, n4) by 16-byte stores, the elements from 4 * n4 on one by one.  The source of out element e of row b is element
 // e + best[b] * n of src (n = B * row_len); a quad inside one row loads 16 bytes where that offset keeps the alignment and four
@@ -518,24 +475,6 @@ __device__ __forceinline__ void gather_rows(const float* src, const int* best, f
     *reinterpret_cast<f32x4*>(out + e0) = v;
   }
   for (int64_t i = 4 * n4 + tid; i < n; i += nthreads) out[i] = value(taken((int)(i / row_len)), i);
-}
-
-struct GatherArgs {
-  const float* src[MMDYN_FEED_GROUPS];
-  float* out[MMDYN_FEED_GROUPS];
-  int64_t n[MMDYN_FEED_GROUPS], n4[MMDYN_FEED_GROUPS];
-  int row_len[MMDYN_FEED_GROUPS], logits[MMDYN_FEED_GROUPS];
-  int first_block[MMDYN_FEED_GROUPS + 1];
-};
-
-__global__ __launch_bounds__(256) void gather_best_kernel(const GatherArgs a, const int* __restrict__ best, int G, int N) {
-  int g = 0;
-#pragma unroll
-  for (int k = 1; k < MMDYN_FEED_GROUPS; ++k)
-    if (k < G && (int)blockIdx.x >= a.first_block[k]) g = k;
-  gather_rows(a.src[g], best, a.out[g], a.n[g], a.n4[g], a.row_len[g], N, a.logits[g],
-              (int64_t)((int)blockIdx.x - a.first_block[g]) * blockDim.x + threadIdx.x,
-              (int64_t)(a.first_block[g + 1] - a.first_block[g]) * blockDim.x);
 }
 
 // ---- candidate condition SEQUENCES over T steps: the weighted total, the winner of each row, the winner's trajectory ----
@@ -580,30 +519,40 @@ struct TopList {
 
 // One thread per row b walks the candidates n and, inside, the scored steps t: c_t = plan_cost of the step's table entries,
 // total = sum_t w_t * c_t in t order.  The tables are [Tg][N][B] (bce: [2][Tg][N][B]), tavail [Tg][B] words, so every read
-// coalesces across b.  Selection on the fp64 total by plan_select_kernel's rules; Tg = T = 1 without weights is that kernel.
-template <bool TOP>
+// coalesces across b.  A table that is not given, and an absent (row, term), enter plan_cost as +0.0 (x + 0.0 == x for every x
+// the tables hold).  Selection on the fp64 total: smallest wins, the first of equals wins, NaN never wins (every comparison
+// with it is false), +-Inf are ordinary values.  Tg = T = 1 without weights and without step_cost is the one-step planner's
+// launch (mmdyn_plan_select): the total is c_0 itself and cost is the step's table.  STEPS = false makes T = Tg = 1 and the two
+// null pointers compile-time facts: no step loop, no weight, no per-step store (measurements: docs/LAB_NOTES.md AD).
+template <bool TOP, bool STEPS>
 __global__ __launch_bounds__(256) void plan_select_steps_kernel(double* __restrict__ bce, double* __restrict__ mse,
                                                                 const double* __restrict__ kl, const uint32_t* __restrict__ tavail,
-                                                                const float* __restrict__ step_weight, const float* __restrict__ cand,
+                                                                const float* __restrict__ step_weight_arg, const float* __restrict__ cand,
                                                                 const int64_t* __restrict__ cand_idx, int cd, float* __restrict__ cost,
-                                                                float* __restrict__ step_cost, int* __restrict__ best,
+                                                                float* __restrict__ step_cost_arg, int* __restrict__ best,
                                                                 float* __restrict__ best_cost, float* __restrict__ best_cond,
                                                                 int64_t* __restrict__ best_idx, int* __restrict__ top,
-                                                                float* __restrict__ top_cost, int K, int N, int B, int T, int Tg,
+                                                                float* __restrict__ top_cost, int K, int N, int B, int T_arg, int Tg_arg,
                                                                 float pose_multiplier, float kl_weight_arg,
                                                                 const float* __restrict__ kl_weight_dev) {
   const float kl_weight = kl_weight_dev ? kl_weight_arg * kl_weight_dev[0] : kl_weight_arg;
   const double pm = (double)pose_multiplier, klw = (double)kl_weight;
+  const int T = STEPS ? T_arg : 1, Tg = STEPS ? Tg_arg : 1;
+  const float* step_weight = STEPS ? step_weight_arg : nullptr;
+  float* step_cost = STEPS ? step_cost_arg : nullptr;
   const size_t NB = (size_t)N * B, TNB = (size_t)Tg * NB;
   for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
     double low = NAN;
     int win = -1;
     TopList list;
     if (TOP) list.clear();
+    // step 0's word is read once per row, not once per candidate: with Tg = 1 no load of the table is left inside the walk, whose
+    // table loads then wait for memory together
+    const uint32_t word0 = tavail ? tavail[b] : ALL_PRESENT;
     for (int n = 0; n < N; ++n) {
       double total = 0.0;
       for (int t = 0; t < Tg; ++t) {
-        const uint32_t word = tavail ? tavail[(size_t)t * B + b] : ALL_PRESENT;
+        const uint32_t word = (t == 0 || !tavail) ? word0 : tavail[(size_t)t * B + b];
         const bool has0 = has(word, 0), has1 = has(word, 1), has2 = has(word, 2);
         const size_t o = ((size_t)t * N + n) * B + b;
         const double v = bce && has0 ? bce[o] : 0.0, u = bce && has1 ? bce[TNB + o] : 0.0, p = mse && has2 ? mse[o] : 0.0;
@@ -611,7 +560,7 @@ __global__ __launch_bounds__(256) void plan_select_steps_kernel(double* __restri
         if (bce && !has1) bce[TNB + o] = 0.0;
         if (mse && !has2) mse[o] = 0.0;
         const double c = plan_cost(v, u, p, kl[o], pm, klw);
-        step_cost[o] = (float)c;
+        if (step_cost) step_cost[o] = (float)c;
         total = add_step(total, c, step_weight ? (double)step_weight[t] : 1.0, step_weight != nullptr, t == 0);
       }
       cost[(size_t)n * B + b] = (float)total;
@@ -652,8 +601,10 @@ struct GatherStepsArgs {
 };
 
 // gather_rows on every step slice: the group's blocks walk its T * per_step (step, chunk) pieces, so the step -- and with it the
-// slice pointers and whether they allow 16-byte accesses -- is block-uniform.  A piece is what one block of a per_step-block
-// gather_best launch on that slice does.
+// slice pointers and whether they allow 16-byte accesses -- is block-uniform.  T = 1 is the one-step planner's launch
+// (mmdyn_gather_best): a piece is then one chunk of its only slice, which STEPS = false makes a compile-time fact (no 64-bit
+// division per piece; measurements: docs/LAB_NOTES.md AD).
+template <bool STEPS>
 __global__ __launch_bounds__(256) void gather_best_steps_kernel(const GatherStepsArgs a, const int* __restrict__ best, int G, int N,
                                                                 int T) {
   int g = 0;
@@ -662,8 +613,8 @@ __global__ __launch_bounds__(256) void gather_best_steps_kernel(const GatherStep
     if (k < G && (int)blockIdx.x >= a.first_block[k]) g = k;
   const int blocks = a.first_block[g + 1] - a.first_block[g], per_step = a.per_step[g];
   const int64_t n = a.n[g];
-  for (int64_t piece = (int)blockIdx.x - a.first_block[g]; piece < (int64_t)T * per_step; piece += blocks) {
-    const int t = (int)(piece / per_step), chunk = (int)(piece % per_step);
+  for (int64_t piece = (int)blockIdx.x - a.first_block[g]; piece < (STEPS ? (int64_t)T * per_step : per_step); piece += blocks) {
+    const int t = STEPS ? (int)(piece / per_step) : 0, chunk = STEPS ? (int)(piece % per_step) : (int)piece;
     const float* src = a.src[g] + (int64_t)t * N * n;
     float* out = a.out[g] + (int64_t)t * n;
     const bool vec = (((uintptr_t)src | (uintptr_t)out) & 15) == 0;
@@ -742,71 +693,7 @@ __device__ __forceinline__ double blend(double alpha, double prev, double fit) {
   return a + f;
 }
 
-// One block of 256 threads per row b.  The row's cost column goes into LDS (padded with NaN to a multiple of four, so the rank
-// walk reads quads; every lane reads the same address: a broadcast); thread n counts the candidates in front of n -- a smaller
-// cost, or an equal one with a smaller index; a NaN is in front of nothing and is itself never an elite -- and n is an elite iff
-// fewer than K are.  The flags stay in LDS; their number K' is summed by the shuffle and four LDS words.  Each thread then owns
-// elements (t, d) and walks n = 0 .. N-1 twice, loading the candidates of the elites only: one fixed summation order, no
-// compaction.  mean_out / std_out may be mean_in / std_in (an element is read and written by the same thread).
-__global__ __launch_bounds__(256) void plan_refit_kernel(const float* __restrict__ cost, const float* __restrict__ cand,
-                                                         const float* mean_in, const float* std_in, float* mean_out, float* std_out,
-                                                         uint8_t* __restrict__ elite, int* __restrict__ count, int K, int N, int B,
-                                                         int T, int cd, float alpha, float std_min) {
-  __shared__ __attribute__((aligned(16))) float cost_s[MMDYN_REFIT_N_MAX];
-  __shared__ uint8_t flag_s[MMDYN_REFIT_N_MAX];
-  __shared__ int part_s[4];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int N4 = (N + 3) & ~3;
-  for (int n = tid; n < N4; n += 256) cost_s[n] = n < N ? cost[(size_t)n * B + b] : NAN;
-  __syncthreads();
-  int mine = 0;
-  for (int n = tid; n < N; n += 256) {
-    const float c = cost_s[n];
-    int ahead = 0;
-    for (int m = 0; m < N4; m += 4) {
-      const f32x4 q = *reinterpret_cast<const f32x4*>(cost_s + m);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ahead += (q[k] < c || (q[k] == c && m + k < n)) ? 1 : 0;
-    }
-    const int flag = (c == c && ahead < K) ? 1 : 0;
-    flag_s[n] = (uint8_t)flag;
-    if (elite) elite[(size_t)n * B + b] = (uint8_t)flag;
-    mine += flag;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if ((tid & 63) == 0) part_s[tid >> 6] = mine;
-  __syncthreads();
-  const int kp = part_s[0] + part_s[1] + part_s[2] + part_s[3];
-  if (count && tid == 0) count[b] = kp;
-  const double a = (double)alpha, inv = (double)kp;
-  const size_t step = (size_t)N * B * cd;                // the floats of one step slice of cand
-  for (int e = tid; e < T * cd; e += 256) {
-    const int t = e / cd, d = e % cd;
-    const size_t o = ((size_t)b * T + t) * cd + d;
-    const float m_in = mean_in[o], s_in = std_in[o];
-    if (kp == 0) {
-      mean_out[o] = m_in;
-      std_out[o] = s_in;
-      continue;
-    }
-    const float* src = cand + (size_t)t * step + (size_t)b * cd + d;    // + n * B * cd per candidate
-    double sum = 0.0;
-    for (int n = 0; n < N; ++n)
-      if (flag_s[n]) sum += (double)src[(size_t)n * B * cd];
-    const double m = sum / inv;
-    double acc = 0.0;
-    for (int n = 0; n < N; ++n)
-      if (flag_s[n]) acc = add_square(acc, (double)src[(size_t)n * B * cd], m);
-    const double s = sqrt(acc / inv);
-    mean_out[o] = (float)blend(a, (double)m_in, m);
-    std_out[o] = fmaxf((float)blend(a, (double)s_in, s), std_min);
-  }
-}
-
-// ---- MPPI: the refit under exponential weights, and the warm start of a horizon that has moved on ----
-
-// The weighted refit's arithmetic in its written order, every operation rounded on its own (the pragma as in plan_cost).
+// The weighted (MPPI) refit's arithmetic in its written order, every operation rounded on its own (the pragma as in plan_cost).
 // w = exp(-(((double)c - (double)c_min) / (double)temperature)) for c != c_min.
 __device__ __forceinline__ double mppi_weight(float c, float c_min, float temperature) {
 #pragma clang fp contract(off)
@@ -834,20 +721,29 @@ __device__ __forceinline__ float effective_samples(double W, double Q) {
 
 constexpr int REFIT_WALK = 8;                // candidate loads of one thread in flight while it walks a weight column
 
-// plan_refit_kernel with a weight per elite: the same block, the same flags (K == N: no candidate is cut, so nothing is ranked
-// and the flag is cost == cost), then c_min = the smallest elite cost (an order-free block reduction), the fp64 weight column
-// in LDS (32 KB next to plan_refit's 20 KB: 52 KB static), W = sum w and Q = sum w * w walked by every thread in ascending n
-// from LDS broadcasts (the walk an element's sums take anyway; one order, no reduction tree), and per element the weighted
-// mean and spread over the candidates of non-zero weight only.  All weights 1 (equal elite costs): add_weighted(acc, 1, c) is
-// acc + c and W is K', so the outputs have plan_refit_kernel's bits.
-__global__ __launch_bounds__(256) void plan_refit_weighted_kernel(const float* __restrict__ cost, const float* __restrict__ cand,
-                                                                  const float* mean_in, const float* std_in, float* mean_out,
-                                                                  float* std_out, uint8_t* __restrict__ elite,
-                                                                  int* __restrict__ count, double* __restrict__ weight,
-                                                                  float* __restrict__ ess, int K, int N, int B, int T, int cd,
-                                                                  float temperature, float alpha, float std_min) {
+// One block of 256 threads per row b.  The row's cost column goes into LDS (padded with NaN to a multiple of four, so the rank
+// walk reads quads; every lane reads the same address: a broadcast); thread n counts the candidates in front of n -- a smaller
+// cost, or an equal one with a smaller index; a NaN is in front of nothing and is itself never an elite -- and n is an elite iff
+// fewer than K are (K == N: no candidate is cut, ahead <= N - 1 < K, so nothing is ranked and the flag is cost == cost).  The
+// flags stay in LDS; their number K' is summed by the shuffle and four LDS words.  Each thread then owns elements (t, d) and
+// walks n = 0 .. N-1 twice over a weight column, loading the candidates of non-zero weight only: one fixed summation order, no
+// compaction.  mean_out / std_out may be mean_in / std_in (an element is read and written by the same thread).
+//   WEIGHTED = false (CEM, mmdyn_plan_refit): the weight column is the flags and the divisor W is K'; 20 KB static LDS.
+//   WEIGHTED = true (MPPI, mmdyn_plan_refit_weighted): c_min = the smallest elite cost (an order-free block reduction), the fp64
+//     weight column in LDS (32 KB more: 52 KB static), W = sum w and Q = sum w * w walked by every thread in ascending n from LDS
+//     broadcasts (the walk an element's sums take anyway; one order, no reduction tree).  All weights 1 (equal elite costs):
+//     add_weighted(acc, 1, c) is acc + c and W is K', so the outputs have the other instantiation's bits.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void plan_refit_kernel(const float* __restrict__ cost, const float* __restrict__ cand,
+                                                         const float* mean_in, const float* std_in, float* mean_out, float* std_out,
+                                                         uint8_t* __restrict__ elite, int* __restrict__ count,
+                                                         double* __restrict__ weight, float* __restrict__ ess, int K, int N, int B,
+                                                         int T, int cd, float temperature, float alpha, float std_min) {
   __shared__ __attribute__((aligned(16))) float cost_s[MMDYN_REFIT_N_MAX];
-  __shared__ __attribute__((aligned(16))) double w_s[MMDYN_REFIT_N_MAX];
+  // w_s and low_s: every reference sits under `if constexpr (WEIGHTED)`, so the unweighted instantiation has none and the
+  // compiler allocates neither (its 20496 bytes are cost_s + flag_s + part_s; the resource table of docs/LAB_NOTES.md AD, taken
+  // with -Rpass-analysis=kernel-resource-usage, is the check to repeat when this body changes)
+  __shared__ __attribute__((aligned(16))) double w_s[WEIGHTED ? MMDYN_REFIT_N_MAX : 1];
   __shared__ uint8_t flag_s[MMDYN_REFIT_N_MAX];
   __shared__ int part_s[4];
   __shared__ float low_s[4];
@@ -871,41 +767,51 @@ __global__ __launch_bounds__(256) void plan_refit_weighted_kernel(const float* _
     flag_s[n] = (uint8_t)flag;
     if (elite) elite[(size_t)n * B + b] = (uint8_t)flag;
     mine += flag;
-    if (flag && c < low) low = c;
+    if (WEIGHTED && flag && c < low) low = c;
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     mine += __shfl_xor(mine, off, 64);
-    const float other = __shfl_xor(low, off, 64);
-    low = other < low ? other : low;
+    if constexpr (WEIGHTED) {
+      const float other = __shfl_xor(low, off, 64);
+      low = other < low ? other : low;
+    }
   }
   if ((tid & 63) == 0) {
     part_s[tid >> 6] = mine;
-    low_s[tid >> 6] = low;
+    if constexpr (WEIGHTED) low_s[tid >> 6] = low;
   }
   __syncthreads();
   const int kp = part_s[0] + part_s[1] + part_s[2] + part_s[3];
-  float c_min = low_s[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) c_min = low_s[k] < c_min ? low_s[k] : c_min;
   if (count && tid == 0) count[b] = kp;
-  for (int n = tid; n < N; n += 256) {
-    const float c = cost_s[n];
-    double w = 0.0;
-    if (flag_s[n]) w = c == c_min ? 1.0 : mppi_weight(c, c_min, temperature);
-    w_s[n] = w;
-    if (weight) weight[(size_t)n * B + b] = w;
-  }
-  __syncthreads();
-  double W = 0.0, Q = 0.0;
-  if (kp != 0) {
-    for (int n = 0; n < N; ++n) {
-      const double w = w_s[n];
-      W += w;
-      Q = add_weighted(Q, w, w);
+  double W = (double)kp;                                 // unweighted: every elite weighs 1
+  if constexpr (WEIGHTED) {
+    float c_min = low_s[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) c_min = low_s[k] < c_min ? low_s[k] : c_min;
+    for (int n = tid; n < N; n += 256) {
+      const float c = cost_s[n];
+      double w = 0.0;
+      if (flag_s[n]) w = c == c_min ? 1.0 : mppi_weight(c, c_min, temperature);
+      w_s[n] = w;
+      if (weight) weight[(size_t)n * B + b] = w;
     }
+    __syncthreads();
+    double Q = 0.0;
+    W = 0.0;
+    if (kp != 0) {
+      for (int n = 0; n < N; ++n) {
+        const double w = w_s[n];
+        W += w;
+        Q = add_weighted(Q, w, w);
+      }
+    }
+    if (ess && tid == 0) ess[b] = kp == 0 ? 0.f : effective_samples(W, Q);
   }
-  if (ess && tid == 0) ess[b] = kp == 0 ? 0.f : effective_samples(W, Q);
+  auto weight_of = [&](int n) {
+    if constexpr (WEIGHTED) return w_s[n];
+    else return flag_s[n];
+  };
   const double a = (double)alpha;
   const size_t step = (size_t)N * B * cd;                // the floats of one step slice of cand
   for (int e = tid; e < T * cd; e += 256) {
@@ -924,28 +830,34 @@ __global__ __launch_bounds__(256) void plan_refit_weighted_kernel(const float* _
     auto walk = [&](auto&& fold) {
       int n = 0;
       for (; n + REFIT_WALK <= N; n += REFIT_WALK) {
-        double w[REFIT_WALK];
+        decltype(weight_of(0)) w[REFIT_WALK];
         float c[REFIT_WALK];
 #pragma unroll
         for (int u = 0; u < REFIT_WALK; ++u) {
-          w[u] = w_s[n + u];
+          w[u] = weight_of(n + u);
           c[u] = 0.f;
-          if (w[u] != 0.0) c[u] = src[(size_t)(n + u) * B * cd];
+          if (w[u] != 0) c[u] = src[(size_t)(n + u) * B * cd];
         }
 #pragma unroll
         for (int u = 0; u < REFIT_WALK; ++u)
-          if (w[u] != 0.0) fold(w[u], (double)c[u]);
+          if (w[u] != 0) fold(w[u], (double)c[u]);
       }
       for (; n < N; ++n) {
-        const double w = w_s[n];
-        if (w != 0.0) fold(w, (double)src[(size_t)n * B * cd]);
+        const auto w = weight_of(n);
+        if (w != 0) fold(w, (double)src[(size_t)n * B * cd]);
       }
     };
     double sum = 0.0;
-    walk([&](double w, double c) { sum = add_weighted(sum, w, c); });
+    walk([&](auto w, double c) {
+      if constexpr (WEIGHTED) sum = add_weighted(sum, w, c);
+      else sum += c;
+    });
     const double m = sum / W;
     double acc = 0.0;
-    walk([&](double w, double c) { acc = add_weighted_square(acc, w, c, m); });
+    walk([&](auto w, double c) {
+      if constexpr (WEIGHTED) acc = add_weighted_square(acc, w, c, m);
+      else acc = add_square(acc, c, m);
+    });
     const double s = sqrt(acc / W);
     mean_out[o] = (float)blend(a, (double)m_in, m);
     std_out[o] = fmaxf((float)blend(a, (double)s_in, s), std_min);
@@ -994,9 +906,25 @@ __global__ __launch_bounds__(256) void plan_shift_kernel(const float* __restrict
   }
 }
 
-bool ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
+// The aliasing rule of every launch here whose outputs are written while other threads read the inputs and write the other
+// outputs: no output range may touch an input or another output.  A null pointer: not given.  own (one entry per output, -1:
+// none): output i may be EXACTLY input own[i] -- the same address, where an element is read and written by one thread.
+struct Range {
+  const void* p;
+  int64_t bytes;
+};
+bool ranges_overlap(const Range& x, const Range& y) {
+  const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+  return x.p && y.p && a < b + (uintptr_t)y.bytes && b < a + (uintptr_t)x.bytes;
+}
+bool aliased(const Range* outs, int n_out, const Range* in, int n_in, const int* own = nullptr) {
+  for (int i = 0; i < n_out; ++i) {
+    for (int j = 0; j < n_in; ++j)
+      if (!(own && own[i] == j && outs[i].p == in[j].p) && ranges_overlap(outs[i], in[j])) return true;
+    for (int j = i + 1; j < n_out; ++j)
+      if (ranges_overlap(outs[i], outs[j])) return true;
+  }
+  return false;
 }
 
 // The grid of a launch whose blocks belong to one group each: every group at least one block; past the element-wise cap the groups
@@ -1019,6 +947,97 @@ int split_blocks(const int64_t* work, int G, int* first_block) {
 }  // namespace
 
 #define ST ((hipStream_t)stream)
+
+// The launchers behind the paired entries: the one-step planner's entry is the T = 1 call of the horizon planner's, and the
+// CEM refit the unweighted instantiation of the MPPI refit.
+
+// step_cost may be null here (mmdyn_plan_select has none; mmdyn_plan_select_steps requires it before it calls).
+static int launch_plan_select(double* bce_rows, double* mse_rows, const double* kl_rows, const uint8_t* tavail, const float* step_weight,
+                              const float* cand, const int64_t* cand_idx, int cd, float* cost, float* step_cost, int* best,
+                              float* best_cost, float* best_cond, int64_t* best_idx, int* top, float* top_cost, int K, int N, int B,
+                              int T, int Tg, float pose_multiplier, float kl_weight, const float* kl_weight_dev, void* stream) {
+  if (!kl_rows || !cost || !best || !best_cost) return MMDYN_ERR_NULL;
+  // exactly one kind of candidates, and the winner's conditions in that kind; the list and its costs together
+  if ((cand == nullptr) == (cand_idx == nullptr) || (cand != nullptr) != (best_cond != nullptr) ||
+      (cand_idx != nullptr) != (best_idx != nullptr) || (top == nullptr) != (top_cost == nullptr))
+    return MMDYN_ERR_NULL;
+  if (N < 1 || B < 1 || T < 1 || Tg < 1 || cd < 1 || (Tg != 1 && Tg != T) || ((uintptr_t)tavail & 3)) return MMDYN_ERR_SHAPE;
+  if (top && (K < 1 || K > MMDYN_PLAN_TOP_MAX)) return MMDYN_ERR_SHAPE;
+  if ((int64_t)T * N * B * (cand ? cd : 1) >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  const uint32_t* tab = reinterpret_cast<const uint32_t*>(tavail);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(ew_grid(B)), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows, tab, step_weight, cand, cand_idx, cd, cost,
+                       step_cost, best, best_cost, best_cond, best_idx, top, top_cost, top ? K : 0, N, B, T, Tg, pose_multiplier, kl_weight,
+                       kl_weight_dev);
+  };
+  if (top)
+    launch(plan_select_steps_kernel<true, true>);
+  else if (T == 1 && !step_weight && !step_cost)                       // (what mmdyn_plan_select asks for)
+    launch(plan_select_steps_kernel<false, false>);
+  else
+    launch(plan_select_steps_kernel<false, true>);
+  MMDYN_LAUNCH_CHECK();
+}
+
+static int launch_gather_best(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, int T, void* stream) {
+  if (!groups || !best) return MMDYN_ERR_NULL;
+  if (G < 1 || G > MMDYN_FEED_GROUPS || N < 1 || B < 1 || T < 1) return MMDYN_ERR_SHAPE;
+  GatherStepsArgs a{};
+  int64_t work[MMDYN_FEED_GROUPS];
+  Range outs[MMDYN_FEED_GROUPS], in[MMDYN_FEED_GROUPS + 1];
+  for (int g = 0; g < G; ++g) {
+    if (!groups->src[g] || !groups->out[g]) return MMDYN_ERR_NULL;
+    if (groups->row_len[g] < 1) return MMDYN_ERR_SHAPE;
+    const int64_t n = (int64_t)B * groups->row_len[g];
+    if (n * N * T >= (1LL << 31)) return MMDYN_ERR_RANGE;
+    // (16-byte accesses are decided per step slice in the kernel; the blocks are counted for the slices that allow them)
+    const bool vec = (((uintptr_t)groups->src[g] | (uintptr_t)groups->out[g]) & 15) == 0;
+    a.src[g] = groups->src[g];
+    a.out[g] = groups->out[g];
+    a.n[g] = n;
+    a.row_len[g] = groups->row_len[g];
+    a.logits[g] = groups->logits[g];
+    a.per_step[g] = (int)ceil_div64(vec && n >= 4 ? n / 4 : n, 256);
+    work[g] = (int64_t)T * a.per_step[g];
+    outs[g] = {a.out[g], n * T * 4};
+    in[g] = {a.src[g], n * N * T * 4};
+  }
+  // the winner's rows of a group are written while other blocks read the indices and the candidates' rows of EVERY group and
+  // write the other groups' rows: an out[g] may touch none of them
+  in[G] = {best, (int64_t)B * 4};
+  if (aliased(outs, G, in, G + 1)) return MMDYN_ERR_SHAPE;
+  const int blocks = split_blocks(work, G, a.first_block);
+  if (T == 1)
+    hipLaunchKernelGGL(gather_best_steps_kernel<false>, dim3(blocks), dim3(256), 0, ST, a, best, G, N, T);
+  else
+    hipLaunchKernelGGL(gather_best_steps_kernel<true>, dim3(blocks), dim3(256), 0, ST, a, best, G, N, T);
+  MMDYN_LAUNCH_CHECK();
+}
+
+// weight / ess / temperature: the weighted instantiation's only (its entry checks the temperature and the weight's alignment).
+static int launch_plan_refit(bool weighted, const float* cost, const float* cand, const float* mean_in, const float* std_in,
+                             float* mean_out, float* std_out, uint8_t* elite, int* count, double* weight, float* ess, int K, int N,
+                             int B, int T, int cd, float temperature, float alpha, float std_min, void* stream) {
+  if (!cost || !cand || !mean_in || !std_in || !mean_out || !std_out) return MMDYN_ERR_NULL;
+  if (B < 1 || T < 1 || cd < 1 || N < 1 || N > MMDYN_REFIT_N_MAX || K < 1 || K > N) return MMDYN_ERR_SHAPE;
+  if (!(alpha >= 0.f && alpha < 1.f) || !(std_min >= 0.f) || ((uintptr_t)weight & 7)) return MMDYN_ERR_SHAPE;
+  if (weighted && (!(temperature > 0.f) || temperature == INFINITY)) return MMDYN_ERR_RANGE;
+  const int64_t n = (int64_t)N * B * T * cd, row = (int64_t)B * T * cd, nb = (int64_t)N * B;
+  if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
+  // mean_out / std_out may be exactly their inputs (an element is read and written by one thread); every other overlap is refused
+  const Range in[4] = {{cost, nb * 4}, {cand, n * 4}, {mean_in, row * 4}, {std_in, row * 4}};
+  const Range outs[6] = {{mean_out, row * 4}, {std_out, row * 4}, {elite, nb}, {count, (int64_t)B * 4}, {weight, nb * 8},
+                         {ess, (int64_t)B * 4}};
+  const int own[6] = {2, 3, -1, -1, -1, -1};
+  if (aliased(outs, 6, in, 4, own)) return MMDYN_ERR_SHAPE;
+  if (weighted)
+    hipLaunchKernelGGL(plan_refit_kernel<true>, dim3(B), dim3(256), 0, ST, cost, cand, mean_in, std_in, mean_out, std_out, elite, count,
+                       weight, ess, K, N, B, T, cd, temperature, alpha, std_min);
+  else
+    hipLaunchKernelGGL(plan_refit_kernel<false>, dim3(B), dim3(256), 0, ST, cost, cand, mean_in, std_in, mean_out, std_out, elite, count,
+                       weight, ess, K, N, B, T, cd, temperature, alpha, std_min);
+  MMDYN_LAUNCH_CHECK();
+}
 
 extern "C" int mmdyn_complete_select(const float* x, const float* recon, const uint8_t* avail, int modality, float* out, int B,
                                      int row_len, int logits, void* stream) {
@@ -1045,7 +1064,8 @@ extern "C" int mmdyn_rollout_feed(const mmdyn_feed_groups* groups, int G, const 
     const int64_t n = (int64_t)B * groups->row_len[g];
     if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
     // the next state is written while the step's outputs and the observation are read by other threads: no aliasing
-    if (overlap(groups->out[g], groups->recon[g], n) || overlap(groups->out[g], groups->obs[g], n)) return MMDYN_ERR_SHAPE;
+    const Range out = {groups->out[g], n * 4}, in[2] = {{groups->recon[g], n * 4}, {groups->obs[g], n * 4}};
+    if (aliased(&out, 1, in, 2)) return MMDYN_ERR_SHAPE;
     const bool vec = (((uintptr_t)groups->obs[g] | (uintptr_t)groups->recon[g] | (uintptr_t)groups->out[g]) & 15) == 0;
     a.recon[g] = groups->recon[g];
     a.obs[g] = groups->obs[g];
@@ -1066,50 +1086,12 @@ extern "C" int mmdyn_plan_select(double* bce_rows, double* mse_rows, const doubl
                                  const int64_t* cand_idx, int cd, float* cost, int* best, float* best_cost, float* best_cond,
                                  int64_t* best_idx, int N, int B, float pose_multiplier, float kl_weight, const float* kl_weight_dev,
                                  void* stream) {
-  if (!kl_rows || !cost || !best || !best_cost) return MMDYN_ERR_NULL;
-  // exactly one kind of candidates, and the winner's condition in that kind
-  if ((cand == nullptr) == (cand_idx == nullptr) || (cand != nullptr) != (best_cond != nullptr) ||
-      (cand_idx != nullptr) != (best_idx != nullptr))
-    return MMDYN_ERR_NULL;
-  if (N < 1 || B < 1 || cd < 1 || ((uintptr_t)tavail & 3)) return MMDYN_ERR_SHAPE;
-  if ((int64_t)N * B * (cand ? cd : 1) >= (1LL << 31)) return MMDYN_ERR_RANGE;
-  hipLaunchKernelGGL(plan_select_kernel, dim3(ew_grid(B)), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows,
-                     reinterpret_cast<const uint32_t*>(tavail), cand, cand_idx, cd, cost, best, best_cost, best_cond, best_idx, N, B,
-                     pose_multiplier, kl_weight, kl_weight_dev);
-  MMDYN_LAUNCH_CHECK();
+  return launch_plan_select(bce_rows, mse_rows, kl_rows, tavail, nullptr, cand, cand_idx, cd, cost, nullptr, best, best_cost,
+                            best_cond, best_idx, nullptr, nullptr, 0, N, B, 1, 1, pose_multiplier, kl_weight, kl_weight_dev, stream);
 }
 
 extern "C" int mmdyn_gather_best(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, void* stream) {
-  if (!groups || !best) return MMDYN_ERR_NULL;
-  if (G < 1 || G > MMDYN_FEED_GROUPS || N < 1 || B < 1) return MMDYN_ERR_SHAPE;
-  GatherArgs a{};
-  int64_t work[MMDYN_FEED_GROUPS];
-  for (int g = 0; g < G; ++g) {
-    if (!groups->src[g] || !groups->out[g]) return MMDYN_ERR_NULL;
-    if (groups->row_len[g] < 1) return MMDYN_ERR_SHAPE;
-    const int64_t n = (int64_t)B * groups->row_len[g];
-    if (n * N >= (1LL << 31)) return MMDYN_ERR_RANGE;
-    const bool vec = (((uintptr_t)groups->src[g] | (uintptr_t)groups->out[g]) & 15) == 0;
-    a.src[g] = groups->src[g];
-    a.out[g] = groups->out[g];
-    a.n[g] = n;
-    a.n4[g] = vec ? n / 4 : 0;
-    a.row_len[g] = groups->row_len[g];
-    a.logits[g] = groups->logits[g];
-    work[g] = ceil_div64(a.n4[g] ? a.n4[g] : n, 256);
-  }
-  // the winner's rows of a group are written while other blocks read the indices and the candidates' rows of EVERY group and
-  // write the other groups' rows: an out[g] may touch none of them
-  for (int g = 0; g < G; ++g) {
-    if (ranges_overlap(a.out[g], a.n[g] * 4, best, (int64_t)B * 4)) return MMDYN_ERR_SHAPE;
-    for (int h = 0; h < G; ++h)
-      if (ranges_overlap(a.out[g], a.n[g] * 4, a.src[h], a.n[h] * N * 4) ||
-          (h != g && ranges_overlap(a.out[g], a.n[g] * 4, a.out[h], a.n[h] * 4)))
-        return MMDYN_ERR_SHAPE;
-  }
-  const int blocks = split_blocks(work, G, a.first_block);
-  hipLaunchKernelGGL(gather_best_kernel, dim3(blocks), dim3(256), 0, ST, a, best, G, N);
-  MMDYN_LAUNCH_CHECK();
+  return launch_gather_best(groups, G, best, N, B, 1, stream);
 }
 
 extern "C" int mmdyn_ensemble_feed(const mmdyn_ensemble_groups* groups, int G, const uint8_t* obs_avail, int N, int B, void* stream) {
@@ -1141,24 +1123,17 @@ extern "C" int mmdyn_ensemble_feed(const mmdyn_ensemble_groups* groups, int G, c
   }
   // the outputs of a group are written while other blocks read the inputs of EVERY group and the table and write the other
   // outputs: an output may touch none of them
-  struct Range { const void* p; int64_t bytes; };
   Range in[2 * MMDYN_FEED_GROUPS + 1], outs[4 * MMDYN_FEED_GROUPS];
-  int n_in = 0, n_out = 0;
   for (int g = 0; g < G; ++g) {
-    in[n_in++] = {a.recon[g], a.plane[g] * N * 4};
-    if (a.obs[g]) in[n_in++] = {a.obs[g], a.plane[g] * 4};
-    outs[n_out++] = {a.out[g], a.plane[g] * N * 4};
-    outs[n_out++] = {a.mean[g], a.plane[g] * 4};
-    if (a.var[g]) outs[n_out++] = {a.var[g], a.plane[g] * 4};
-    if (a.spread[g]) outs[n_out++] = {a.spread[g], (int64_t)B * 8};
+    in[2 * g] = {a.recon[g], a.plane[g] * N * 4};
+    in[2 * g + 1] = {a.obs[g], a.plane[g] * 4};
+    outs[4 * g] = {a.out[g], a.plane[g] * N * 4};
+    outs[4 * g + 1] = {a.mean[g], a.plane[g] * 4};
+    outs[4 * g + 2] = {a.var[g], a.plane[g] * 4};
+    outs[4 * g + 3] = {a.spread[g], (int64_t)B * 8};
   }
-  if (obs_avail) in[n_in++] = {obs_avail, (int64_t)B * MMDYN_MAX_EXPERTS};
-  for (int i = 0; i < n_out; ++i) {
-    for (int j = 0; j < n_in; ++j)
-      if (ranges_overlap(outs[i].p, outs[i].bytes, in[j].p, in[j].bytes)) return MMDYN_ERR_SHAPE;
-    for (int j = i + 1; j < n_out; ++j)
-      if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return MMDYN_ERR_SHAPE;
-  }
+  in[2 * G] = {obs_avail, (int64_t)B * MMDYN_MAX_EXPERTS};
+  if (aliased(outs, 4 * G, in, 2 * G + 1)) return MMDYN_ERR_SHAPE;
   const int blocks = split_blocks(work, G, a.first_block);
   hipLaunchKernelGGL(ensemble_feed_kernel, dim3(blocks), dim3(256), 0, ST, a, reinterpret_cast<const uint32_t*>(obs_avail), G, N);
   MMDYN_LAUNCH_CHECK();
@@ -1192,11 +1167,12 @@ extern "C" int mmdyn_ensemble_quantiles(const mmdyn_quantile_groups* groups, int
     work[g] = ceil_div64(plane, 4 * QUANTILE_CHUNK);                // in blocks of 256 threads, as the cap counts them
   }
   // the quantiles of a group are written while other blocks read the samples of EVERY group and write the other groups' quantiles
-  for (int g = 0; g < G; ++g)
-    for (int h = 0; h < G; ++h)
-      if (ranges_overlap(a.out[g], a.plane[g] * Q * 4, a.src[h], a.plane[h] * N * 4) ||
-          (h != g && ranges_overlap(a.out[g], a.plane[g] * Q * 4, a.out[h], a.plane[h] * Q * 4)))
-        return MMDYN_ERR_SHAPE;
+  Range outs[MMDYN_FEED_GROUPS], in[MMDYN_FEED_GROUPS];
+  for (int g = 0; g < G; ++g) {
+    outs[g] = {a.out[g], a.plane[g] * Q * 4};
+    in[g] = {a.src[g], a.plane[g] * N * 4};
+  }
+  if (aliased(outs, G, in, G)) return MMDYN_ERR_SHAPE;
   int blocks = 4 * split_blocks(work, G, a.first_block);            // one wavefront per block: four for each counted block
   for (int g = 0; g <= MMDYN_FEED_GROUPS; ++g) a.first_block[g] *= 4;
   const int N4 = (N + 3) & ~3;
@@ -1210,57 +1186,13 @@ extern "C" int mmdyn_plan_select_steps(double* bce_rows, double* mse_rows, const
                                        float* step_cost, int* best, float* best_cost, float* best_cond, int64_t* best_idx, int* top,
                                        float* top_cost, int K, int N, int B, int T, int Tg, float pose_multiplier, float kl_weight,
                                        const float* kl_weight_dev, void* stream) {
-  if (!kl_rows || !cost || !step_cost || !best || !best_cost) return MMDYN_ERR_NULL;
-  // exactly one kind of candidates, and the winner's conditions in that kind; the list and its costs together
-  if ((cand == nullptr) == (cand_idx == nullptr) || (cand != nullptr) != (best_cond != nullptr) ||
-      (cand_idx != nullptr) != (best_idx != nullptr) || (top == nullptr) != (top_cost == nullptr))
-    return MMDYN_ERR_NULL;
-  if (N < 1 || B < 1 || T < 1 || Tg < 1 || cd < 1 || (Tg != 1 && Tg != T) || ((uintptr_t)tavail & 3)) return MMDYN_ERR_SHAPE;
-  if (top && (K < 1 || K > MMDYN_PLAN_TOP_MAX)) return MMDYN_ERR_SHAPE;
-  if ((int64_t)T * N * B * (cand ? cd : 1) >= (1LL << 31)) return MMDYN_ERR_RANGE;
-  const uint32_t* tab = reinterpret_cast<const uint32_t*>(tavail);
-  if (top)
-    hipLaunchKernelGGL(plan_select_steps_kernel<true>, dim3(ew_grid(B)), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows, tab,
-                       step_weight, cand, cand_idx, cd, cost, step_cost, best, best_cost, best_cond, best_idx, top, top_cost, K, N, B, T,
-                       Tg, pose_multiplier, kl_weight, kl_weight_dev);
-  else
-    hipLaunchKernelGGL(plan_select_steps_kernel<false>, dim3(ew_grid(B)), dim3(256), 0, ST, bce_rows, mse_rows, kl_rows, tab,
-                       step_weight, cand, cand_idx, cd, cost, step_cost, best, best_cost, best_cond, best_idx, top, top_cost, 0, N, B, T,
-                       Tg, pose_multiplier, kl_weight, kl_weight_dev);
-  MMDYN_LAUNCH_CHECK();
+  if (!step_cost) return MMDYN_ERR_NULL;
+  return launch_plan_select(bce_rows, mse_rows, kl_rows, tavail, step_weight, cand, cand_idx, cd, cost, step_cost, best, best_cost,
+                            best_cond, best_idx, top, top_cost, K, N, B, T, Tg, pose_multiplier, kl_weight, kl_weight_dev, stream);
 }
 
 extern "C" int mmdyn_gather_best_steps(const mmdyn_gather_groups* groups, int G, const int* best, int N, int B, int T, void* stream) {
-  if (!groups || !best) return MMDYN_ERR_NULL;
-  if (G < 1 || G > MMDYN_FEED_GROUPS || N < 1 || B < 1 || T < 1) return MMDYN_ERR_SHAPE;
-  GatherStepsArgs a{};
-  int64_t work[MMDYN_FEED_GROUPS];
-  for (int g = 0; g < G; ++g) {
-    if (!groups->src[g] || !groups->out[g]) return MMDYN_ERR_NULL;
-    if (groups->row_len[g] < 1) return MMDYN_ERR_SHAPE;
-    const int64_t n = (int64_t)B * groups->row_len[g];
-    if (n * N * T >= (1LL << 31)) return MMDYN_ERR_RANGE;
-    // (16-byte accesses are decided per step slice in the kernel; the blocks are counted for the slices that allow them)
-    const bool vec = (((uintptr_t)groups->src[g] | (uintptr_t)groups->out[g]) & 15) == 0;
-    a.src[g] = groups->src[g];
-    a.out[g] = groups->out[g];
-    a.n[g] = n;
-    a.row_len[g] = groups->row_len[g];
-    a.logits[g] = groups->logits[g];
-    a.per_step[g] = (int)ceil_div64(vec && n >= 4 ? n / 4 : n, 256);
-    work[g] = (int64_t)T * a.per_step[g];
-  }
-  // as in mmdyn_gather_best, over all T steps: an out[g] may touch neither the indices, nor any src, nor another out
-  for (int g = 0; g < G; ++g) {
-    if (ranges_overlap(a.out[g], a.n[g] * T * 4, best, (int64_t)B * 4)) return MMDYN_ERR_SHAPE;
-    for (int h = 0; h < G; ++h)
-      if (ranges_overlap(a.out[g], a.n[g] * T * 4, a.src[h], a.n[h] * N * T * 4) ||
-          (h != g && ranges_overlap(a.out[g], a.n[g] * T * 4, a.out[h], a.n[h] * T * 4)))
-        return MMDYN_ERR_SHAPE;
-  }
-  const int blocks = split_blocks(work, G, a.first_block);
-  hipLaunchKernelGGL(gather_best_steps_kernel, dim3(blocks), dim3(256), 0, ST, a, best, G, N, T);
-  MMDYN_LAUNCH_CHECK();
+  return launch_gather_best(groups, G, best, N, B, T, stream);
 }
 
 extern "C" int mmdyn_plan_sample(const float* mean, const float* std, const float* eps, const float* keep, const float* lo,
@@ -1270,10 +1202,9 @@ extern "C" int mmdyn_plan_sample(const float* mean, const float* std, const floa
   const int64_t n = (int64_t)N * B * T * cd, row = (int64_t)B * T * cd;
   if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
   // the candidates are written while other threads read every input: no aliasing
-  const struct { const void* p; int64_t bytes; } in[6] = {{mean, row * 4}, {std, row * 4}, {eps, n * 4}, {keep, row * 4},
-                                                          {lo, (int64_t)cd * 4}, {hi, (int64_t)cd * 4}};
-  for (int i = 0; i < 6; ++i)
-    if (in[i].p && ranges_overlap(cand, n * 4, in[i].p, in[i].bytes)) return MMDYN_ERR_SHAPE;
+  const Range out = {cand, n * 4};
+  const Range in[6] = {{mean, row * 4}, {std, row * 4}, {eps, n * 4}, {keep, row * 4}, {lo, (int64_t)cd * 4}, {hi, (int64_t)cd * 4}};
+  if (aliased(&out, 1, in, 6)) return MMDYN_ERR_SHAPE;
   const uintptr_t ptrs = (uintptr_t)mean | (uintptr_t)std | (uintptr_t)eps | (uintptr_t)keep | (uintptr_t)lo | (uintptr_t)hi |
                          (uintptr_t)cand;
   if ((ptrs & 15) == 0 && cd % 4 == 0)
@@ -1287,54 +1218,16 @@ extern "C" int mmdyn_plan_sample(const float* mean, const float* std, const floa
 extern "C" int mmdyn_plan_refit(const float* cost, const float* cand, const float* mean_in, const float* std_in, float* mean_out,
                                 float* std_out, uint8_t* elite, int* count, int K, int N, int B, int T, int cd, float alpha,
                                 float std_min, void* stream) {
-  if (!cost || !cand || !mean_in || !std_in || !mean_out || !std_out) return MMDYN_ERR_NULL;
-  if (B < 1 || T < 1 || cd < 1 || N < 1 || N > MMDYN_REFIT_N_MAX || K < 1 || K > N) return MMDYN_ERR_SHAPE;
-  if (!(alpha >= 0.f && alpha < 1.f) || !(std_min >= 0.f)) return MMDYN_ERR_SHAPE;
-  const int64_t n = (int64_t)N * B * T * cd, row = (int64_t)B * T * cd, nb = (int64_t)N * B;
-  if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
-  // an output may be exactly its own input (an element is read and written by one thread); every other overlap is refused
-  struct Range { const void* p; int64_t bytes; };
-  const Range in[4] = {{cost, nb * 4}, {cand, n * 4}, {mean_in, row * 4}, {std_in, row * 4}};
-  const Range outs[4] = {{mean_out, row * 4}, {std_out, row * 4}, {elite, nb}, {count, (int64_t)B * 4}};
-  for (int i = 0; i < 4; ++i) {
-    if (!outs[i].p) continue;
-    for (int j = 0; j < 4; ++j)
-      if (!(i < 2 && j == i + 2 && outs[i].p == in[j].p) && ranges_overlap(outs[i].p, outs[i].bytes, in[j].p, in[j].bytes))
-        return MMDYN_ERR_SHAPE;
-    for (int j = i + 1; j < 4; ++j)
-      if (outs[j].p && ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return MMDYN_ERR_SHAPE;
-  }
-  hipLaunchKernelGGL(plan_refit_kernel, dim3(B), dim3(256), 0, ST, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, K, N,
-                     B, T, cd, alpha, std_min);
-  MMDYN_LAUNCH_CHECK();
+  return launch_plan_refit(false, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, nullptr, nullptr, K, N, B, T, cd, 0.f,
+                           alpha, std_min, stream);
 }
 
 extern "C" int mmdyn_plan_refit_weighted(const float* cost, const float* cand, const float* mean_in, const float* std_in,
                                          float* mean_out, float* std_out, uint8_t* elite, int* count, double* weight, float* ess,
                                          int K, int N, int B, int T, int cd, float temperature, float alpha, float std_min,
                                          void* stream) {
-  if (!cost || !cand || !mean_in || !std_in || !mean_out || !std_out) return MMDYN_ERR_NULL;
-  if (B < 1 || T < 1 || cd < 1 || N < 1 || N > MMDYN_REFIT_N_MAX || K < 1 || K > N) return MMDYN_ERR_SHAPE;
-  if (!(alpha >= 0.f && alpha < 1.f) || !(std_min >= 0.f) || ((uintptr_t)weight & 7)) return MMDYN_ERR_SHAPE;
-  if (!(temperature > 0.f) || temperature == INFINITY) return MMDYN_ERR_RANGE;
-  const int64_t n = (int64_t)N * B * T * cd, row = (int64_t)B * T * cd, nb = (int64_t)N * B;
-  if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
-  // as in mmdyn_plan_refit: mean_out / std_out may be exactly their inputs; weight and ess overlap nothing
-  struct Range { const void* p; int64_t bytes; };
-  const Range in[4] = {{cost, nb * 4}, {cand, n * 4}, {mean_in, row * 4}, {std_in, row * 4}};
-  const Range outs[6] = {{mean_out, row * 4}, {std_out, row * 4}, {elite, nb}, {count, (int64_t)B * 4}, {weight, nb * 8},
-                         {ess, (int64_t)B * 4}};
-  for (int i = 0; i < 6; ++i) {
-    if (!outs[i].p) continue;
-    for (int j = 0; j < 4; ++j)
-      if (!(i < 2 && j == i + 2 && outs[i].p == in[j].p) && ranges_overlap(outs[i].p, outs[i].bytes, in[j].p, in[j].bytes))
-        return MMDYN_ERR_SHAPE;
-    for (int j = i + 1; j < 6; ++j)
-      if (outs[j].p && ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return MMDYN_ERR_SHAPE;
-  }
-  hipLaunchKernelGGL(plan_refit_weighted_kernel, dim3(B), dim3(256), 0, ST, cost, cand, mean_in, std_in, mean_out, std_out, elite,
-                     count, weight, ess, K, N, B, T, cd, temperature, alpha, std_min);
-  MMDYN_LAUNCH_CHECK();
+  return launch_plan_refit(true, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, weight, ess, K, N, B, T, cd, temperature,
+                           alpha, std_min, stream);
 }
 
 extern "C" int mmdyn_plan_shift(const float* prev_mean, const float* prev_std, const float* prev_keep, const float* init_mean,
@@ -1346,15 +1239,9 @@ extern "C" int mmdyn_plan_shift(const float* prev_mean, const float* prev_std, c
   const int64_t n = (int64_t)B * T * cd;
   if (n >= (1LL << 31)) return MMDYN_ERR_RANGE;
   // every output is written while other threads read every input: no aliasing
-  const float* in[5] = {prev_mean, prev_std, prev_keep, init_mean, init_std};
-  float* outs[3] = {mean_out, std_out, keep_out};
-  for (int i = 0; i < 3; ++i) {
-    if (!outs[i]) continue;
-    for (int j = 0; j < 5; ++j)
-      if (in[j] && ranges_overlap(outs[i], n * 4, in[j], n * 4)) return MMDYN_ERR_SHAPE;
-    for (int j = i + 1; j < 3; ++j)
-      if (outs[j] && ranges_overlap(outs[i], n * 4, outs[j], n * 4)) return MMDYN_ERR_SHAPE;
-  }
+  const Range in[5] = {{prev_mean, n * 4}, {prev_std, n * 4}, {prev_keep, n * 4}, {init_mean, n * 4}, {init_std, n * 4}};
+  const Range outs[3] = {{mean_out, n * 4}, {std_out, n * 4}, {keep_out, n * 4}};
+  if (aliased(outs, 3, in, 5)) return MMDYN_ERR_SHAPE;
   const uintptr_t ptrs = (uintptr_t)prev_mean | (uintptr_t)prev_std | (uintptr_t)prev_keep | (uintptr_t)init_mean |
                          (uintptr_t)init_std | (uintptr_t)mean_out | (uintptr_t)std_out | (uintptr_t)keep_out;
   if ((ptrs & 15) == 0 && cd % 4 == 0)

@@ -1096,6 +1096,52 @@ class HipBackend:
         check(self.lib.mmdyn_rollout_feed(ctypes.addressof(arg), len(groups), table, B, _stream()), "mmdyn_rollout_feed")
 
     # ---- candidate conditions: the cost table, the winner of each row, the winner's rows ----
+    @staticmethod
+    def _candidate_kind(name, candidates, N, B, T=None):
+        """(index, cd, shape of candidates, shape of best_condition) of a planner's candidates: fp32 with cd reals per row or
+        int64 indices; T = None: the one-step layout [N * B], otherwise step-major [T][N * B] with the winner's [B][T]."""
+        lead, lead_txt = ((), "") if T is None else ((T,), "[T]")
+        if not torch.is_tensor(candidates) or candidates.dtype not in (torch.float32, torch.int64):
+            raise ValueError(f"mmdyn_{name}: candidates must be fp32 {lead_txt}[N * B][cd] or int64 {lead_txt}[N * B], got "
+                             f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
+        if candidates.dtype == torch.int64:
+            return True, 1, lead + (N * B,), (B,) + lead
+        if candidates.dim() != len(lead) + 2 or candidates.shape[-1] < 1:
+            raise ValueError(f"mmdyn_{name}: real-valued candidates must be {'' if T is None else f'[T = {T}]'}[N * B = {N * B}][cd], "
+                             f"got {tuple(candidates.shape)}")
+        cd = candidates.shape[-1]
+        return False, cd, lead + (N * B, cd), (B,) + lead + (cd,)
+
+    @staticmethod
+    def _gather_groups(name, groups, best, N, B, T=None):
+        """The checked GatherGroups of :meth:`gather_best` (T = None: src [N * B, ...], out [B, ...]) and of
+        :meth:`gather_best_steps` (src [T, N * B, ...], out [T, B, ...])."""
+        lead = () if T is None else (T,)
+        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
+            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
+                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
+        if min(N, B, *lead) < 1:
+            raise ValueError(f"mmdyn_hip: {name}: " + (f"N = {N} and B = {B}" if T is None else f"N = {N}, B = {B} and T = {T}") +
+                             " must be positive")
+        if not torch.is_tensor(best) or best.dtype != torch.int32 or tuple(best.shape) != (B,) or not best.is_contiguous():
+            raise ValueError(f"mmdyn_hip: {name}: best must be a contiguous int32 [B={B}] tensor")
+        arg, d = GatherGroups(), len(lead) + 1
+        for g, grp in enumerate(groups):
+            src, out = grp["src"], grp["out"]
+            for t, rows, what in ((src, N * B, "src"), (out, B, "out")):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < d or \
+                        tuple(t.shape[:d]) != lead + (rows,):
+                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor " +
+                                     (f"of {rows} rows" if T is None else f"[T={T}][{rows}][...]") +
+                                     f", got {(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+            if src.numel() == 0 or tuple(src.shape[d:]) != tuple(out.shape[d:]) or src.device != best.device or out.device != best.device:
+                raise ValueError(f"mmdyn_hip: {name}: group {g}: src {tuple(src.shape)} on {src.device} and out {tuple(out.shape)} on "
+                                 f"{out.device} must share a non-empty row shape and the device of best")
+        for g, grp in enumerate(groups):
+            arg.src[g], arg.out[g] = _ptr(grp["src"]), _ptr(grp["out"])
+            arg.row_len[g], arg.logits[g] = grp["out"].numel() // (B * (T or 1)), int(bool(grp["logits"]))
+        return arg
+
     def plan_select(self, bce_rows, mse_rows, kl_rows, tavail, candidates, cost, best, best_cost, best_condition, N, B,
                     pose_multiplier, kl_weight=1.0, kl_weight_dev=None):
         """cost [N][B] fp32 = ((bce_rows[0] + bce_rows[1]) + pose_multiplier * mse_rows) + kl_weight * kl_rows, formed in fp64 in that
@@ -1107,17 +1153,7 @@ class HipBackend:
         name, N, B = "plan_select", int(N), int(B)
         if N < 1 or B < 1:
             raise ValueError(f"mmdyn_plan_select: N = {N} and B = {B} must be positive")
-        if not torch.is_tensor(candidates) or candidates.dtype not in (torch.float32, torch.int64):
-            raise ValueError(f"mmdyn_plan_select: candidates must be fp32 [N * B][cd] or int64 [N * B], got "
-                             f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
-        index = candidates.dtype == torch.int64
-        if index:
-            cd, shapes = 1, ((N * B,), (B,))
-        else:
-            if candidates.dim() != 2 or candidates.shape[1] < 1:
-                raise ValueError(f"mmdyn_plan_select: real-valued candidates must be [N * B = {N * B}][cd], got {tuple(candidates.shape)}")
-            cd = candidates.shape[1]
-            shapes = ((N * B, cd), (B, cd))
+        index, cd, *shapes = self._candidate_kind(name, candidates, N, B)
         if any(t is None for t in (kl_rows, cost, best, best_cost, best_condition)):
             raise ValueError("mmdyn_plan_select: kl_rows, cost, best, best_cost and best_condition are required")
         f32, f64, ctype = torch.float32, torch.float64, candidates.dtype
@@ -1135,27 +1171,8 @@ class HipBackend:
         b]) with f = sigmoid where ``logits``, the identity otherwise.  src: contiguous fp32 [N * B, ...]; out: contiguous fp32
         [B, ...] of the same row shape, overlapping no src and no other out of the call; best: int32 [B] -- a row whose index is
         -1 (or anywhere outside [0, N)) is filled with NaN and reads nothing.  A taken row has the bits of :meth:`complete_select` (x = None) on it."""
-        name, N, B = "gather_best", int(N), int(B)
-        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
-            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
-                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
-        if N < 1 or B < 1:
-            raise ValueError(f"mmdyn_hip: {name}: N = {N} and B = {B} must be positive")
-        if not torch.is_tensor(best) or best.dtype != torch.int32 or tuple(best.shape) != (B,) or not best.is_contiguous():
-            raise ValueError(f"mmdyn_hip: {name}: best must be a contiguous int32 [B={B}] tensor")
-        arg = GatherGroups()
-        for g, grp in enumerate(groups):
-            src, out = grp["src"], grp["out"]
-            for t, rows, what in ((src, N * B, "src"), (out, B, "out")):
-                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.shape[0] != rows:
-                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor of {rows} rows, got "
-                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
-            if src.numel() == 0 or tuple(src.shape[1:]) != tuple(out.shape[1:]) or src.device != best.device or out.device != best.device:
-                raise ValueError(f"mmdyn_hip: {name}: group {g}: src {tuple(src.shape)} on {src.device} and out {tuple(out.shape)} on "
-                                 f"{out.device} must share a non-empty row shape and the device of best")
-        for g, grp in enumerate(groups):
-            arg.src[g], arg.out[g] = _ptr(grp["src"]), _ptr(grp["out"])
-            arg.row_len[g], arg.logits[g] = grp["out"].numel() // B, int(bool(grp["logits"]))
+        N, B = int(N), int(B)
+        arg = self._gather_groups("gather_best", groups, best, N, B)
         check(self.lib.mmdyn_gather_best(ctypes.addressof(arg), len(groups), _ptr(best, torch.int32), N, B, _stream()),
               "mmdyn_gather_best")
 
@@ -1172,18 +1189,7 @@ class HipBackend:
         name, N, B, T, Tg = "plan_select_steps", int(N), int(B), int(T), int(Tg)
         if N < 1 or B < 1 or T < 1 or Tg not in (1, T):
             raise ValueError(f"mmdyn_plan_select_steps: N = {N}, B = {B} and T = {T} must be positive and Tg = {Tg} be 1 or T")
-        if not torch.is_tensor(candidates) or candidates.dtype not in (torch.float32, torch.int64):
-            raise ValueError(f"mmdyn_plan_select_steps: candidates must be fp32 [T][N * B][cd] or int64 [T][N * B], got "
-                             f"{candidates.dtype if torch.is_tensor(candidates) else type(candidates).__name__}")
-        index = candidates.dtype == torch.int64
-        if index:
-            cd, shapes = 1, ((T, N * B), (B, T))
-        else:
-            if candidates.dim() != 3 or candidates.shape[2] < 1:
-                raise ValueError(f"mmdyn_plan_select_steps: real-valued candidates must be [T = {T}][N * B = {N * B}][cd], got "
-                                 f"{tuple(candidates.shape)}")
-            cd = candidates.shape[2]
-            shapes = ((T, N * B, cd), (B, T, cd))
+        index, cd, *shapes = self._candidate_kind(name, candidates, N, B, T)
         if any(t is None for t in (kl_rows, cost, step_cost, best, best_cost, best_condition)):
             raise ValueError("mmdyn_plan_select_steps: kl_rows, cost, step_cost, best, best_cost and best_condition are required")
         if (top is None) != (top_cost is None):
@@ -1217,28 +1223,8 @@ class HipBackend:
         f(src[t][best[b] * B + b]).  src: contiguous fp32 [T, N * B, ...]; out: contiguous fp32 [T, B, ...] of the same row shape,
         overlapping no src and no other out of the call; best: int32 [B] -- a row whose index lies outside [0, N) is filled with
         NaN in every step and reads nothing.  The bits of T :meth:`gather_best` calls on the step slices."""
-        name, N, B, T = "gather_best_steps", int(N), int(B), int(T)
-        if not isinstance(groups, (list, tuple)) or not 1 <= len(groups) <= FEED_GROUPS:
-            raise ValueError(f"mmdyn_hip: {name}: between 1 and {FEED_GROUPS} groups, got "
-                             f"{len(groups) if isinstance(groups, (list, tuple)) else type(groups).__name__}")
-        if N < 1 or B < 1 or T < 1:
-            raise ValueError(f"mmdyn_hip: {name}: N = {N}, B = {B} and T = {T} must be positive")
-        if not torch.is_tensor(best) or best.dtype != torch.int32 or tuple(best.shape) != (B,) or not best.is_contiguous():
-            raise ValueError(f"mmdyn_hip: {name}: best must be a contiguous int32 [B={B}] tensor")
-        arg = GatherGroups()
-        for g, grp in enumerate(groups):
-            src, out = grp["src"], grp["out"]
-            for t, rows, what in ((src, N * B, "src"), (out, B, "out")):
-                if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 2 or \
-                        tuple(t.shape[:2]) != (T, rows):
-                    raise ValueError(f"mmdyn_hip: {name}: group {g}: {what} must be a contiguous fp32 tensor [T={T}][{rows}][...], got "
-                                     f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
-            if src.numel() == 0 or tuple(src.shape[2:]) != tuple(out.shape[2:]) or src.device != best.device or out.device != best.device:
-                raise ValueError(f"mmdyn_hip: {name}: group {g}: src {tuple(src.shape)} on {src.device} and out {tuple(out.shape)} on "
-                                 f"{out.device} must share a non-empty row shape and the device of best")
-        for g, grp in enumerate(groups):
-            arg.src[g], arg.out[g] = _ptr(grp["src"]), _ptr(grp["out"])
-            arg.row_len[g], arg.logits[g] = grp["out"].numel() // (T * B), int(bool(grp["logits"]))
+        N, B, T = int(N), int(B), int(T)
+        arg = self._gather_groups("gather_best_steps", groups, best, N, B, T)
         check(self.lib.mmdyn_gather_best_steps(ctypes.addressof(arg), len(groups), _ptr(best, torch.int32), N, B, T, _stream()),
               "mmdyn_gather_best_steps")
 
@@ -1250,6 +1236,45 @@ class HipBackend:
             return False
         pa, pb = a.data_ptr(), b.data_ptr()
         return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+    def _disjoint(self, name, ins, outs, own=()):
+        """ValueError where an output of op ``name`` touches an input or another output (``ins`` / ``outs``: specs as in
+        :meth:`_check_tables`, None tensors skipped).  own: pairs (i, j) -- output i may be exactly input j."""
+        for i, (o, _, what, _) in enumerate(outs):
+            for j, (t, _, other, _) in enumerate(ins):
+                if self._touch(o, t) and not ((i, j) in own and o.data_ptr() == t.data_ptr()):
+                    raise ValueError(f"mmdyn_{name}: {what} overlaps {other}" +
+                                     (" (an output may only be exactly its own input)" if own else ""))
+            for p, _, other, _ in outs[i + 1:]:
+                if self._touch(o, p):
+                    raise ValueError(f"mmdyn_{name}: {what} overlaps {other}")
+
+    def _refit(self, name, cost, cand, mean_in, std_in, mean_out, std_out, elite, count, K, N, B, T, alpha, std_min,
+               temperature=None, extra=()):
+        """The checks of :meth:`plan_refit` and :meth:`plan_refit_weighted` (``temperature`` and the ``extra`` output specs: the
+        weighted one's): (cd, the pointers in the order of the entry's arguments)."""
+        if B < 1 or T < 1 or not 1 <= N <= REFIT_N_MAX or not 1 <= K <= N:
+            raise ValueError(f"mmdyn_{name}: B = {B} and T = {T} must be positive, N = {N} lie in [1, {REFIT_N_MAX}] and "
+                             f"K = {K} in [1, N]")
+        if not 0.0 <= alpha < 1.0 or not std_min >= 0.0:
+            raise ValueError(f"mmdyn_{name}: alpha = {alpha} must lie in [0, 1) and std_min = {std_min} be >= 0")
+        if temperature is not None and not 0.0 < temperature < float("inf"):
+            raise ValueError(f"mmdyn_{name}: temperature = {temperature} must be finite and > 0")
+        if any(t is None for t in (cost, cand, mean_in, std_in, mean_out, std_out)):
+            raise ValueError(f"mmdyn_{name}: cost, cand, mean_in, std_in, mean_out and std_out are required")
+        if not torch.is_tensor(cand) or cand.dim() != 3 or cand.shape[2] < 1:
+            raise ValueError(f"mmdyn_{name}: cand must be fp32 [T = {T}][N * B = {N * B}][cd], got "
+                             f"{tuple(cand.shape) if torch.is_tensor(cand) else type(cand).__name__}")
+        cd = cand.shape[2]
+        if N * B * T * cd >= 1 << 31:
+            raise ValueError(f"mmdyn_{name}: N * B * T * cd = {N * B * T * cd} elements reach 2^31")
+        f32 = torch.float32
+        specs = ((cost, (N, B), "cost", f32), (cand, (T, N * B, cd), "cand", f32), (mean_in, (B, T, cd), "mean_in", f32),
+                 (std_in, (B, T, cd), "std_in", f32), (mean_out, (B, T, cd), "mean_out", f32), (std_out, (B, T, cd), "std_out", f32),
+                 (elite, (N, B), "elite", torch.uint8), (count, (B,), "count", torch.int32)) + tuple(extra)
+        self._check_tables(name, *specs)
+        self._disjoint(name, specs[:4], specs[4:], own=((0, 2), (1, 3)))
+        return cd, [_ptr(t, dtype) for t, _, _, dtype in specs]
 
     def plan_sample(self, mean, std, eps, keep, lo, hi, cand, N, B, T):
         """cand [T][N * B][cd] fp32 = the candidates of one refinement iteration: row n * B + b of step t is mean[b][t] + std[b][t] *
@@ -1274,9 +1299,7 @@ class HipBackend:
         specs = ((mean, (B, T, cd), "mean", f32), (std, (B, T, cd), "std", f32), (eps, (N, B, T, cd), "eps", f32),
                  (keep, (B, T, cd), "keep", f32), (lo, (cd,), "lo", f32), (hi, (cd,), "hi", f32), (cand, (T, N * B, cd), "cand", f32))
         self._check_tables(name, *specs)
-        for t, _, what, _ in specs[:-1]:
-            if self._touch(cand, t):
-                raise ValueError(f"mmdyn_plan_sample: cand overlaps {what}")
+        self._disjoint(name, specs[:-1], specs[-1:])
         ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
         check(self.lib.mmdyn_plan_sample(*ptrs, N, B, T, cd, _stream()), "mmdyn_plan_sample")
 
@@ -1287,35 +1310,8 @@ class HipBackend:
         own: m = sum c / K', s = sqrt(sum (c - m)^2 / K'); mean_out = fp32(alpha * mean_in + (1 - alpha) * m), std_out =
         fmax(fp32(alpha * std_in + (1 - alpha) * s), std_min); K' = 0: the inputs, bit for bit.  mean_* / std_*: fp32 [B][T][cd],
         an output may be exactly its input and overlaps nothing else; elite: uint8 [N][B] or None; count: int32 [B] or None."""
-        name, K, N, B, T = "plan_refit", int(K), int(N), int(B), int(T)
-        alpha, std_min = float(alpha), float(std_min)
-        if B < 1 or T < 1 or not 1 <= N <= REFIT_N_MAX or not 1 <= K <= N:
-            raise ValueError(f"mmdyn_plan_refit: B = {B} and T = {T} must be positive, N = {N} lie in [1, {REFIT_N_MAX}] and K = {K} in [1, N]")
-        if not 0.0 <= alpha < 1.0 or not std_min >= 0.0:
-            raise ValueError(f"mmdyn_plan_refit: alpha = {alpha} must lie in [0, 1) and std_min = {std_min} be >= 0")
-        if any(t is None for t in (cost, cand, mean_in, std_in, mean_out, std_out)):
-            raise ValueError("mmdyn_plan_refit: cost, cand, mean_in, std_in, mean_out and std_out are required")
-        if not torch.is_tensor(cand) or cand.dim() != 3 or cand.shape[2] < 1:
-            raise ValueError(f"mmdyn_plan_refit: cand must be fp32 [T = {T}][N * B = {N * B}][cd], got "
-                             f"{tuple(cand.shape) if torch.is_tensor(cand) else type(cand).__name__}")
-        cd = cand.shape[2]
-        if N * B * T * cd >= 1 << 31:
-            raise ValueError(f"mmdyn_plan_refit: N * B * T * cd = {N * B * T * cd} elements reach 2^31")
-        f32 = torch.float32
-        specs = ((cost, (N, B), "cost", f32), (cand, (T, N * B, cd), "cand", f32), (mean_in, (B, T, cd), "mean_in", f32),
-                 (std_in, (B, T, cd), "std_in", f32), (mean_out, (B, T, cd), "mean_out", f32), (std_out, (B, T, cd), "std_out", f32),
-                 (elite, (N, B), "elite", torch.uint8), (count, (B,), "count", torch.int32))
-        self._check_tables(name, *specs)
-        ins, outs = specs[:4], specs[4:]
-        for i, (o, _, what, _) in enumerate(outs):
-            for j, (t, _, other, _) in enumerate(ins):
-                own = i < 2 and j == i + 2 and o.data_ptr() == t.data_ptr()
-                if not own and self._touch(o, t):
-                    raise ValueError(f"mmdyn_plan_refit: {what} overlaps {other} (an output may only be exactly its own input)")
-            for p, _, other, _ in outs[i + 1:]:
-                if self._touch(o, p):
-                    raise ValueError(f"mmdyn_plan_refit: {what} overlaps {other}")
-        ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
+        K, N, B, T, alpha, std_min = int(K), int(N), int(B), int(T), float(alpha), float(std_min)
+        cd, ptrs = self._refit("plan_refit", cost, cand, mean_in, std_in, mean_out, std_out, elite, count, K, N, B, T, alpha, std_min)
         check(self.lib.mmdyn_plan_refit(*ptrs, K, N, B, T, cd, alpha, std_min, _stream()), "mmdyn_plan_refit")
 
     # ---- MPPI weights and the receding horizon ----
@@ -1327,39 +1323,10 @@ class HipBackend:
         sqrt((sum w (c - m)^2) / W) over the candidates of non-zero weight, then plan_refit's blend and floor; K' = 0: the inputs,
         bit for bit.  Equal elite costs: the bits of plan_refit.  weight: fp64 [N][B] or None; ess: fp32 [B] = W^2 / Q (0 when
         K' = 0) or None; neither overlaps anything.  Everything else as in plan_refit."""
-        name, K, N, B, T = "plan_refit_weighted", int(K), int(N), int(B), int(T)
+        K, N, B, T = int(K), int(N), int(B), int(T)
         temperature, alpha, std_min = float(temperature), float(alpha), float(std_min)
-        if B < 1 or T < 1 or not 1 <= N <= REFIT_N_MAX or not 1 <= K <= N:
-            raise ValueError(f"mmdyn_plan_refit_weighted: B = {B} and T = {T} must be positive, N = {N} lie in [1, {REFIT_N_MAX}] and "
-                             f"K = {K} in [1, N]")
-        if not 0.0 <= alpha < 1.0 or not std_min >= 0.0:
-            raise ValueError(f"mmdyn_plan_refit_weighted: alpha = {alpha} must lie in [0, 1) and std_min = {std_min} be >= 0")
-        if not 0.0 < temperature < float("inf"):
-            raise ValueError(f"mmdyn_plan_refit_weighted: temperature = {temperature} must be finite and > 0")
-        if any(t is None for t in (cost, cand, mean_in, std_in, mean_out, std_out)):
-            raise ValueError("mmdyn_plan_refit_weighted: cost, cand, mean_in, std_in, mean_out and std_out are required")
-        if not torch.is_tensor(cand) or cand.dim() != 3 or cand.shape[2] < 1:
-            raise ValueError(f"mmdyn_plan_refit_weighted: cand must be fp32 [T = {T}][N * B = {N * B}][cd], got "
-                             f"{tuple(cand.shape) if torch.is_tensor(cand) else type(cand).__name__}")
-        cd = cand.shape[2]
-        if N * B * T * cd >= 1 << 31:
-            raise ValueError(f"mmdyn_plan_refit_weighted: N * B * T * cd = {N * B * T * cd} elements reach 2^31")
-        f32 = torch.float32
-        specs = ((cost, (N, B), "cost", f32), (cand, (T, N * B, cd), "cand", f32), (mean_in, (B, T, cd), "mean_in", f32),
-                 (std_in, (B, T, cd), "std_in", f32), (mean_out, (B, T, cd), "mean_out", f32), (std_out, (B, T, cd), "std_out", f32),
-                 (elite, (N, B), "elite", torch.uint8), (count, (B,), "count", torch.int32),
-                 (weight, (N, B), "weight", torch.float64), (ess, (B,), "ess", f32))
-        self._check_tables(name, *specs)
-        ins, outs = specs[:4], specs[4:]
-        for i, (o, _, what, _) in enumerate(outs):
-            for j, (t, _, other, _) in enumerate(ins):
-                own = i < 2 and j == i + 2 and o.data_ptr() == t.data_ptr()
-                if not own and self._touch(o, t):
-                    raise ValueError(f"mmdyn_plan_refit_weighted: {what} overlaps {other} (an output may only be exactly its own input)")
-            for p, _, other, _ in outs[i + 1:]:
-                if self._touch(o, p):
-                    raise ValueError(f"mmdyn_plan_refit_weighted: {what} overlaps {other}")
-        ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
+        cd, ptrs = self._refit("plan_refit_weighted", cost, cand, mean_in, std_in, mean_out, std_out, elite, count, K, N, B, T, alpha,
+                               std_min, temperature, ((weight, (N, B), "weight", torch.float64), (ess, (B,), "ess", torch.float32)))
         check(self.lib.mmdyn_plan_refit_weighted(*ptrs, K, N, B, T, cd, temperature, alpha, std_min, _stream()),
               "mmdyn_plan_refit_weighted")
 
@@ -1388,11 +1355,7 @@ class HipBackend:
             (prev_mean, "prev_mean"), (prev_std, "prev_std"), (prev_keep, "prev_keep"), (init_mean, "init_mean"), (init_std, "init_std"),
             (mean_out, "mean_out"), (std_out, "std_out"), (keep_out, "keep_out")))
         self._check_tables(name, *specs)
-        ins, outs = specs[:5], specs[5:]
-        for i, (o, _, what, _) in enumerate(outs):
-            for t, _, other, _ in ins + outs[i + 1:]:
-                if self._touch(o, t):
-                    raise ValueError(f"mmdyn_plan_shift: {what} overlaps {other}")
+        self._disjoint(name, specs[:5], specs[5:])
         ptrs = [_ptr(t, dtype) for t, _, _, dtype in specs]
         check(self.lib.mmdyn_plan_shift(*ptrs, B, T, cd, shift, widen, _stream()), "mmdyn_plan_shift")
 

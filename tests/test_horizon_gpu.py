@@ -84,6 +84,29 @@ def test_gather_steps_is_gather_best_per_step(row_lens, B, N, T, shift):
     E.check_gather_steps(HIP, DEV, row_lens, B, N, T, shift)
 
 
+@pytest.mark.parametrize("row_lens,B,N,T,shift", [((48, 48, 7), 5, 3, 3, 0), ((12, 12), 3, 3, 2, 1)])
+def test_gather_steps_is_complete_select_on_the_picked_rows(row_lens, B, N, T, shift):
+    """The independent form of the check above (one kernel serves both gather entries, so that one compares it with itself): every
+    step of every group against mmdyn_complete_select(x = null) on the rows a torch index picks from src[t] -- the same bits in
+    every taken row; a row with best = -1 or best = N is all NaN in every step."""
+    best = torch.randint(0, N, (B,), generator=torch.Generator().manual_seed(7 + B)).to(torch.int32)
+    best[1], best[B - 1] = -1, N
+    best = best.to(DEV)
+    taken = (best >= 0) & (best < N)
+    rows = torch.where(taken, best.long(), torch.zeros_like(best).long()) * B + torch.arange(B, device=DEV)
+    groups = [dict(src=(3.0 * gen(970 + g, T, N * B, n)).to(DEV), out=E.shifted(DEV, (T, B, n), shift), logits=g == 1)
+              for g, n in enumerate(row_lens)]
+    HIP.gather_best_steps(groups, best, N, B, T)
+    assert int(taken.sum()) >= 1
+    for g in groups:
+        for t in range(T):
+            want = torch.empty(B, g["src"].shape[2], device=DEV)
+            HIP.complete_select(None, g["src"][t][rows], None, 0, want, g["logits"])
+            diff = dirty.first_diff(g["out"][t][taken], want[taken])
+            assert diff is None, (t, diff)
+            assert bool(torch.isfinite(g["out"][t][taken]).all()) and bool(torch.isnan(g["out"][t][~taken]).all())
+
+
 def test_gather_steps_on_dirty_destinations_and_bad_arguments():
     B, N, T, row_lens = 5, 3, 3, (48, 48, 7)
     best = torch.tensor([2, 0, 1, 0, 2], dtype=torch.int32)

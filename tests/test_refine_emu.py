@@ -385,7 +385,9 @@ def check_problem_layer(device, root):
 
 # ---- the CPU suite -------------------------------------------------------------------------------------------------------------
 SAMPLE_SHAPES = [(1, 1, 1, 1, 0), (5, 9, 3, 3, 0), (3, 2, 2, 4, 0), (300, 2, 2, 2, 0), (3, 2, 2, 4, 1)]
-REFIT_SHAPES = [(1, 1, 1, 1, 1), (5, 9, 3, 3, 3), (2, 300, 40, 2, 2), (3, 4096, 64, 1, 1)]
+# (the last three: K == N, where nothing is ranked -- N = one walk group of eight and a tail of one, two groups and a tail, one group)
+REFIT_SHAPES = [(1, 1, 1, 1, 1), (5, 9, 3, 3, 3), (2, 300, 40, 2, 2), (3, 4096, 64, 1, 1), (2, 9, 9, 2, 3), (2, 17, 17, 1, 4),
+                (3, 8, 8, 2, 1)]
 
 
 @pytest.mark.parametrize("B,N,T,cd,shift", SAMPLE_SHAPES)
