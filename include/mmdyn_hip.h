@@ -345,7 +345,9 @@ int mmdyn_bn_finalize(const float* partial, float* mean, float* rstd, float* run
  * memory that no other launch in flight uses.  With it the two stages run as ONE launch: every block publishes its
  * partial sums (agent-scope release), draws a ticket, and the block that arrives last (agent-scope acquire) adds the
  * partials in the same fixed order as the separate second kernel -- bit-identical results -- and puts the word back to
- * zero (a HIP-graph replay finds it zero again).  Without it: two launches. */
+ * zero (a HIP-graph replay finds it zero again).  Without it: two launches.  The two BatchNorm finalize entry points take the
+ * single launch only for T < 640 (where both forms add the tile sums in the same four slices or fewer); a larger table runs as two
+ * launches with or without a ticket, and the word is not touched. */
 /* a = swish(gamma*(y-mean)*rstd + beta) */
 int mmdyn_bn_swish_fwd(const float* y, const float* mean, const float* rstd, const float* gamma,
                        const float* beta, float* a, int G, int rows_per_group, int C, void* stream);
@@ -358,7 +360,8 @@ int mmdyn_bn_bwd_finalize(const float* partial, float* sums, float* dgamma, floa
                           double* scratch /* [32][G][2][C] */, int G, int T, int C, float beta_acc,
                           uint32_t* ticket, void* stream);
 /* eval mode (model.eval(): nn.BatchNorm2d with training=False): mean[g][c] = running_mean[c],
- * rstd[g][c] = 1/sqrt(running_var[c] + eps); mmdyn_bn_swish_fwd then applies them.  No buffer update. */
+ * rstd[g][c] = 1/sqrt(running_var[c] + eps), formed in fp64 and rounded once; mmdyn_bn_swish_fwd then applies them.  No buffer
+ * update. */
 int mmdyn_bn_eval_stats(const float* running_mean, const float* running_var, float* mean, float* rstd, int G, int C,
                         float eps, void* stream);
 /* Synchronised BatchNorm across data-parallel ranks (optional): the per-channel sums are

@@ -100,8 +100,9 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const TA* __restrict__ y
 // blockIdx.z (a 32-channel layer has only G x 1 channel blocks; the slices give the big layers 100+ blocks):
 // out[s][g][2][C] (double accumulate); the finish kernels add the S slices in a fixed order.
 constexpr int BN_MAX_SPLITS = 32;
-// single-launch ("last block finishes") form: every block arrives on ONE counter (~12 ns per arrival), so it runs with few,
-// fat slices -- at most 4 x groups x channel slabs <= 128 blocks -- instead of the 1024 the two-launch form spreads the sums over
+// single-launch ("last block finishes") form: every block arrives on ONE counter (~12 ns per arrival), so it is offered only
+// where the sums take few, fat slices -- at most 4 x groups x channel slabs <= 128 blocks; from T = 640 on, where the two-launch form
+// spreads the sums over more slices (up to 1024 blocks), a launch with a ticket takes the two launches
 constexpr int TICKET_MAX_SPLITS = 4;
 static inline int bn_splits(int T) {
   int s = T / 128;
@@ -145,7 +146,8 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ running_mean, con
   if (i >= G * C) return;
   const int c = i % C;
   mean[i] = running_mean[c];
-  rstd[i] = 1.0f / sqrtf(running_var[c] + eps);
+  // in fp64 and rounded once, as bn_stats_finish_channel forms the train-mode rstd (three fp32 roundings reached 1.25 ulp)
+  rstd[i] = (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
 }
 
 // adds the S slices of tile_sum_kernel: out[g][2][C] (the quantity a synchronised BatchNorm all-reduces)
@@ -542,9 +544,11 @@ extern "C" int mmdyn_bn_finalize(const float* partial, float* mean, float* rstd,
   if (!partial || !mean || !rstd || !g_sums) return MMDYN_ERR_NULL;
   if (!bn_shape_ok(G, rows_per_group, C) || T <= 0) return MMDYN_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  int S = bn_splits(T);
-  if (ticket) {           // one launch: the last-arriving block of the tile sums finishes the statistics
-    if (S > TICKET_MAX_SPLITS) S = TICKET_MAX_SPLITS;
+  const int S = bn_splits(T);
+  // one launch: the last-arriving block of the tile sums finishes the statistics.  Only where the two-launch form takes no more
+  // than TICKET_MAX_SPLITS slices (T < 640): the bits are promised to be the two-launch form's, and another slice count adds the
+  // fp64 tile sums in another grouping (tests/bn_cases.py, table "crafted") -- larger tables take the two launches below
+  if (ticket && S <= TICKET_MAX_SPLITS) {
     BnFinish f{};
     f.kind = 1;
     f.mean = mean;
@@ -686,9 +690,8 @@ extern "C" int mmdyn_bn_bwd_finalize(const float* partial, float* sums, float* d
   if (!partial || !sums || !g_sums) return MMDYN_ERR_NULL;
   if (!bn_shape_ok(G, 1, C) || T <= 0) return MMDYN_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  int S = bn_splits(T);
-  if (ticket) {
-    if (S > TICKET_MAX_SPLITS) S = TICKET_MAX_SPLITS;
+  const int S = bn_splits(T);
+  if (ticket && S <= TICKET_MAX_SPLITS) {           // (as in mmdyn_bn_finalize: the same slices in both forms)
     BnFinish f{};
     f.kind = 2;
     f.sums_f = sums;

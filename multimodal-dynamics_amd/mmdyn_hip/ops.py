@@ -113,7 +113,8 @@ class HipBackend:
         # BatchNorm finalize launches whose partial-sum table has at most this many (group, tile) rows take the single-launch
         # "last block finishes" form (0: none, rounds 3-5 -- the form lost on the whole step when EVERY finalize took it).  Same
         # box, interleaved (profiles/r6/ab_bn_finalize_small_tables.txt, bench.py --ticket-max-work): 1024 = nothing on the
-        # power-bound configs[1] step, +1.1 % on bf16s bs 128, 18 launches fewer per step; bit-identical results either way
+        # power-bound configs[1] step, +1.1 % on bf16s bs 128, 18 launches fewer per step; bit-identical results either way (a table
+        # of 640 tiles or more per group runs as two launches inside the library even with a ticket: csrc/bn.hip)
         self.ticket_max_work = 1024
         # "fp32": v_mfma_f32_32x32x2_f32 (the reference's arithmetic, the default and the BASELINE configs[1] path);
         # "bf16": operands rounded to bf16 on their way into the matrix cores, fp32 accumulate (configs[2]);

@@ -330,23 +330,28 @@ class EmuBackend:
         partial[:, 0, 1] = (v * v).sum(1)
 
     def bn_finalize(self, partial, mean, rstd, rm, rv, nbt, scratch, G, T, C, rpg, eps, momentum, repeat):
+        # eps and momentum arrive as floats; one update of a running estimate is (1 - momentum) * r + momentum * fp32(x) on fp32
+        # values (formed here in fp64 and rounded once: the kernel's multiply-add is within an ulp of it)
+        eps, momentum = float(np.float32(eps)), float(np.float32(momentum))
+        keep = float(np.float32(1.0) - np.float32(momentum))
         s = partial.reshape(G, T, 2, C).double().sum(1)
         m = s[:, 0] / rpg
         var = (s[:, 1] / rpg - m * m).clamp_min(0)
         mean.copy_(m.float())
         rstd.copy_((1 / torch.sqrt(var + eps)).float())
         for g in range(G):
+            unb = (var[g] * (rpg / max(rpg - 1, 1))).float()
             for _ in range(repeat):
                 if rm is not None:
-                    rm.mul_(1 - momentum).add_(momentum * m[g].float())
+                    rm.copy_((keep * rm.double() + momentum * m[g].float().double()).float())
                 if rv is not None:
-                    rv.mul_(1 - momentum).add_(momentum * (var[g] * rpg / max(rpg - 1, 1)).float())
+                    rv.copy_((keep * rv.double() + momentum * unb.double()).float())
         if nbt is not None:
             nbt += G * repeat
 
     def bn_eval_stats(self, rm, rv, mean, rstd, G, C, eps):
         mean.copy_(rm.reshape(1, C).expand(G, C))
-        rstd.copy_((1.0 / torch.sqrt(rv + eps)).reshape(1, C).expand(G, C))
+        rstd.copy_((1.0 / torch.sqrt(rv.double() + float(np.float32(eps)))).float().reshape(1, C).expand(G, C))
 
     def bn_reduce_partials(self, partial, sums, scratch, G, T, C):
         sums.copy_(partial.reshape(G, T, 2, C).double().sum(1))
@@ -379,12 +384,12 @@ class EmuBackend:
         partial[:, 0, 1] = (du * xh).sum(1)
 
     def bn_bwd_finalize(self, partial, sums, dgamma, dbeta, scratch, G, T, C, beta_acc):
-        s = partial.reshape(G, T, 2, C).sum(1)
-        sums.copy_(s)
+        s = partial.reshape(G, T, 2, C).double().sum(1)         # (the kernel adds the tile sums in fp64)
+        sums.copy_(s.float())
         if dbeta is not None:
-            dbeta.copy_((beta_acc * dbeta if beta_acc else 0) + s[:, 0].sum(0))
+            dbeta.copy_((beta_acc * dbeta if beta_acc else 0) + s[:, 0].sum(0).float())
         if dgamma is not None:
-            dgamma.copy_((beta_acc * dgamma if beta_acc else 0) + s[:, 1].sum(0))
+            dgamma.copy_((beta_acc * dgamma if beta_acc else 0) + s[:, 1].sum(0).float())
 
     def igemm_nt_dgrad_bn(self, A, Bp, C, stats, y, mean, rstd, gamma, beta, mode, G, Bg, Hi, Wi, Cin, Ho, Wo, N,
                           stride, offset):

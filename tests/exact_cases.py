@@ -656,19 +656,69 @@ def run_col2im(be, dev, Bt, Hi, Wi, C, stride, pad, tap_major, ld_extra, family,
 
 
 # ---- pure sums (family A only) ---------------------------------------------------------------------------------------------------
+# G, rows per group, C.  The first four reach the 32-row tile of the column reductions only (csrc/bn.hip, tile_rows_for); the others:
+# 64-row tiles with T = 257 and a last tile of one row; 64-row tiles with 4 row lanes, a last tile of 63 rows and a group boundary;
+# 96-row tiles; 512-row tiles (four trips of the 4-row unrolled loop with 32 row lanes) with a last tile of one row; 32-row tiles
+# with T = 257.  T = 257 takes two slices of the tile sums later.
+COLSTATS_SHAPES = [(1, 1, 32), (4, 700, 128), (2, 4097, 64), (3, 255, 256),
+                   (1, 16385, 32), (2, 16447, 256), (1, 24576 + 33, 128), (1, 131073, 32), (3, 8224, 64)]
+EVAL_TABLE_SHAPES = [(2, 16447, 256), (1, 131073, 32), (3, 8224, 64)]
+
+
+def _no_junk(P, what):
+    """Every element of the declared extent was written: none keeps the sentinel."""
+    sentinel = bits(fill_(torch.empty(1, dtype=P.buf.dtype), JUNK))[0]
+    left = (bits(P.values()) == sentinel).nonzero()
+    assert left.numel() == 0, (f"{what}: {left.numel()} elements of the output were never written, the first at row "
+                               f"{int(left[0]) // P.width}, column {int(left[0]) % P.width}")
+
+
+def run_colstats(be, dev, shape, what=""):
+    """mmdyn_colstats on integers: the table summed over its T tiles is the exact column sum of y and of y * y."""
+    G, rpg, C = shape
+    y = ints((G * rpg, C), 91, 3)
+    r = y.double().reshape(G, rpg, C)
+    assert float(r.abs().sum(1).max()) < LIMIT and float((r * r).sum(1).max()) < LIMIT
+    T = be.colstats_tiles(rpg)
+    P = Guarded(G * T * 2, C, torch.float32, dev)
+    be.colstats(_dev(y, dev), P.view(G, T, 2, C), G, rpg, C)
+    P.check(f"{what}colstats {G, rpg, C}: partial")
+    _no_junk(P, f"{what}colstats {G, rpg, C}: partial")
+    check_exact(P.values().double().reshape(G, T, 2, C).sum(1).reshape(-1, C), torch.stack([r.sum(1), (r * r).sum(1)], 1).reshape(-1, C),
+                f"{what}colstats {G, rpg, C}: partial summed over {T} tiles")
+
+
+def run_eval_table(be, dev, shape, what=""):
+    """The `partial` table of mmdyn_bn_eval_swish_bwd on integers: da_is_du = 1 with integer da, mean = 0 and rstd = 1, so xhat = y
+    is an integer and the table summed over its tiles is the exact (sum du, sum du * y); gamma = +-2^k, so dy = du * gamma is exact
+    as well."""
+    G, rpg, C = shape
+    y, da = ints((G * rpg, C), 101, 3), ints((G * rpg, C), 102, 3)
+    r, d = y.double().reshape(G, rpg, C), da.double().reshape(G, rpg, C)
+    assert float(d.abs().sum(1).max()) < LIMIT and float((d * r).abs().sum(1).max()) < LIMIT
+    gamma, beta = pow2(C, 103), ints((C,), 104, 3)
+    mean, rstd = torch.zeros(G, C), torch.ones(G, C)
+    T = be.colstats_tiles(rpg)
+    P, dy = Guarded(G * T * 2, C, torch.float32, dev), Guarded(G * rpg, C, torch.float32, dev)
+    be.bn_eval_swish_bwd(_dev(da, dev), _dev(y, dev), _dev(mean, dev), _dev(rstd, dev), _dev(gamma, dev), _dev(beta, dev),
+                         dy.view(G * rpg, C), P.view(G, T, 2, C), G, rpg, C, True)
+    what = f"{what}bn_eval_swish_bwd {G, rpg, C}"
+    P.check(f"{what}: partial")
+    dy.check(f"{what}: dy")
+    _no_junk(P, f"{what}: partial")
+    check_exact(P.values().double().reshape(G, T, 2, C).sum(1).reshape(-1, C), torch.stack([d.sum(1), (d * r).sum(1)], 1).reshape(-1, C),
+                f"{what}: partial summed over {T} tiles")
+    check_exact(dy.values(), (d * gamma.double()).reshape(-1, C), f"{what}: dy")
+
+
 def run_sums(be, dev, what=""):
     """mmdyn_colstats, mmdyn_colsum (perm 0 / 2, beta 0 / 1), mmdyn_sum_blocks, mmdyn_dropout_expand / _reduce with p_drop = 0.5
-    (the scale 2 is exact), mmdyn_linear_small_fwd / _bwd on integers."""
-    for G, rpg, C in ((1, 1, 32), (4, 700, 128), (2, 4097, 64), (3, 255, 256)):
-        y = ints((G * rpg, C), 91, 3)
-        r = y.double().reshape(G, rpg, C)
-        assert float(r.abs().sum(1).max()) < LIMIT and float((r * r).sum(1).max()) < LIMIT
-        T = be.colstats_tiles(rpg)
-        P = Guarded(G * T * 2, C, torch.float32, dev)
-        be.colstats(_dev(y, dev), P.view(G, T, 2, C), G, rpg, C)
-        P.check(f"{what}colstats {G, rpg, C}: partial")
-        check_exact(P.values().double().reshape(G, T, 2, C).sum(1).reshape(-1, C), torch.stack([r.sum(1), (r * r).sum(1)], 1).reshape(-1, C),
-                    f"{what}colstats {G, rpg, C}: partial summed over {T} tiles")
+    (the scale 2 is exact), mmdyn_linear_small_fwd / _bwd on integers; the `partial` table of mmdyn_bn_eval_swish_bwd on three of
+    the column-statistics shapes."""
+    for shape in COLSTATS_SHAPES:
+        run_colstats(be, dev, shape, what)
+    for shape in EVAL_TABLE_SHAPES:
+        run_eval_table(be, dev, shape, what)
     for rows, C, perm in ((1, 32, 0), (300, 512, 0), (1025, 100, 0), (5000, 64, 0), (64, 6400, 2), (7, 6400, 2)):
         x = ints((rows, C), 92, 3)
         s = x.double().sum(0)

@@ -257,10 +257,11 @@ def _sync(dev):
         torch.cuda.synchronize()
 
 
-def run_fwd(be, dev, shape, T, scaled=False, figures=None, what=""):
-    """mmdyn_bn_swish_fwd_b16.  scaled: part of the output is subnormal in half and part lies beyond 65504."""
+def run_fwd(be, dev, shape, T, scaled=False, figures=None, what="", inputs=None, c=C_FWD):
+    """mmdyn_bn_swish_fwd_b16 (T = fp32: mmdyn_bn_swish_fwd).  scaled: part of the output is subnormal in half and part lies beyond
+    65504.  inputs / c: another input set (y, da, mean, rstd, gamma, beta) with the constant measured on it (tests/bn_cases.py)."""
     G, rpg, C = shape
-    y, _, mean, rstd, gamma, beta = bn_inputs(shape, T, scaled)
+    y, _, mean, rstd, gamma, beta = inputs or bn_inputs(shape, T, scaled)
     ref, M = f_fwd(F64, y, mean, rstd, gamma, beta, G, rpg, C)
     if scaled:      # (preconditions, on the reference alone)
         tiny, huge = (ref.abs() < 2.0 ** E_MIN[T]) & (ref.abs() > 2.0 ** (E_MIN[T] - MANT[T] + 2)), ref.abs() > 1.01 * inf_threshold(T)
@@ -270,7 +271,7 @@ def run_fwd(be, dev, shape, T, scaled=False, figures=None, what=""):
     _sync(dev)
     what = f"{what}bn_swish_fwd {shape} {T}{' scaled' if scaled else ''}"
     a.check(what)
-    return check_rule(a.values(), ref, M, T, C_FWD, what, figures)
+    return check_rule(a.values(), ref, M, T, c, what, figures)
 
 
 def reduce_ref(shape, T):
@@ -299,11 +300,12 @@ def run_reduce(be, dev, shape, T, figures=None, what=""):
     return r
 
 
-def run_apply(be, dev, shape, T, da_is_du, figures=None, what=""):
-    """mmdyn_bn_swish_bwd_apply_b16; the sums are the fp64 sums of the reduce pass, rounded to fp32."""
+def run_apply(be, dev, shape, T, da_is_du, figures=None, what="", inputs=None, c=None):
+    """mmdyn_bn_swish_bwd_apply_b16 (T = fp32: mmdyn_bn_swish_bwd_apply); the sums are the fp64 sums of the reduce pass, rounded to
+    fp32.  inputs / c: as in run_fwd."""
     G, rpg, C = shape
-    y, da, mean, rstd, gamma, beta = bn_inputs(shape, T)
-    sums = reduce_ref(shape, T).float()
+    y, da, mean, rstd, gamma, beta = inputs or bn_inputs(shape, T)
+    sums = f_reduce(F64, da, y, mean, rstd, gamma, beta, *shape).float()
     ref, M = f_apply(F64, da, y, mean, rstd, gamma, beta, sums, G, rpg, C, da_is_du)
     dy = X.Guarded(G * rpg, C, T, dev)
     be.bn_swish_bwd_apply(da.to(dev), y.to(dev), mean.to(dev), rstd.to(dev), gamma.to(dev), beta.to(dev), sums.to(dev),
@@ -311,13 +313,14 @@ def run_apply(be, dev, shape, T, da_is_du, figures=None, what=""):
     _sync(dev)
     what = f"{what}bn_swish_bwd_apply {shape} {T} da_is_du={int(da_is_du)}"
     dy.check(what)
-    return check_rule(dy.values(), ref, M, T, C_APPLY_DU if da_is_du else C_APPLY, what, figures)
+    return check_rule(dy.values(), ref, M, T, c if c is not None else (C_APPLY_DU if da_is_du else C_APPLY), what, figures)
 
 
-def run_act_bwd(be, dev, shape, T, act, figures=None, what=""):
-    """mmdyn_act_bwd_b16: Swish by the rule; ReLU with `==` (du = dh where u > 0, zero elsewhere)."""
+def run_act_bwd(be, dev, shape, T, act, figures=None, what="", inputs=None, c=C_ACT_BWD):
+    """mmdyn_act_bwd_b16 (T = fp32: mmdyn_act_bwd): Swish by the rule; ReLU with `==` (du = dh where u > 0, zero elsewhere).
+    inputs / c: another (u, dh) [G rpg][C] with the constant measured on it."""
     G, rpg, C = shape
-    u, dh = bn_inputs(shape, T)[:2]
+    u, dh = inputs or bn_inputs(shape, T)[:2]
     du = X.Guarded(G * rpg, C, T, dev)
     be.act_bwd(dh.to(dev), u.to(dev), du.view(G * rpg, C), act)
     _sync(dev)
@@ -327,7 +330,7 @@ def run_act_bwd(be, dev, shape, T, act, figures=None, what=""):
         assert bool((u.float() <= 0).any()) and bool((u.float() > 0).any())
         return X.check_exact(du.values(), dh.double() * (u.double() > 0), what)
     ref, M = f_act_bwd(F64, dh, u)
-    return check_rule(du.values(), ref, M, T, C_ACT_BWD, what, figures)
+    return check_rule(du.values(), ref, M, T, c, what, figures)
 
 
 # ---- runners: GEMM epilogues -----------------------------------------------------------------------------------------------------

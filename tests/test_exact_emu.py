@@ -14,6 +14,7 @@ import torch
 import exact_cases as X
 from dirty import bits
 from emu_backend import EmuBackend
+from emu_backend_evalgrad import EmuBackendEvalGrad
 from mmdyn_hip.ops import DENSE, CONV, TCONV_S2P1, IM2COL3, TCONV_S1P0
 from test_kernels_gpu import IGEMM_CASES, WSP_CASES, WGRAD_CASES
 
@@ -161,7 +162,7 @@ def test_direct_kernels(family):
 
 
 def test_pure_sums():
-    X.run_sums(EMU, DEV)
+    X.run_sums(EmuBackendEvalGrad(), DEV)      # (the emulation that restates mmdyn_bn_eval_swish_bwd as well)
 
 
 def test_s1p0_rows_follow_the_output_pixels():
