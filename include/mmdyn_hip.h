@@ -960,6 +960,45 @@ int mmdyn_adam_step_guarded(float* p, const float* g, float* m, float* v, double
 int mmdyn_sgd_step(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum,
                    float weight_decay, float grad_scale, int first, void* stream);
 
+/* ---- clipping by the global L2 norm (torch.nn.utils.clip_grad_norm_), with the norm reported ---- */
+/* clip: FOUR doubles on the device, owned by the caller and zeroed once: {S = sum of squares, norm, coefficient, clipped steps}.
+ * Everything below runs on the device without a host read, so a captured step replays it.  Added without touching an existing
+ * signature: the revision stays 6.
+ *
+ * mmdyn_grad_sumsq_blocks: host query, the number of fp64 partial sums a mmdyn_grad_sumsq over n elements writes (>= 1).  A
+ * function of n alone (not of the device, not of an experiment variable), non-decreasing in n, at most 2048. */
+int mmdyn_grad_sumsq_blocks(int64_t n);
+/* clip[0] = sum_i g[i]^2 (accumulate != 0: clip[0] += ..., to chain the tensors of a parameter list), in two launches and without
+ * float atomics: the result depends neither on arrival order nor on what `partials` held.  Block b of the first launch owns a fixed
+ * contiguous chunk of g (its length follows from n alone); squares and sums are fp64 (an fp32 square is exact there); a thread
+ * adds its 4-element groups in address order, then the 64-lane shuffle tree, the four wave totals in wave order, partials[b].  The
+ * second launch is one block: thread t adds partials [t * per, (t + 1) * per), per = ceil(blocks / 256), in index order, then the
+ * same tree.  Every partial it reads was written by the first launch of the same call.  Error against the exact sum: at most
+ * 2 n 2^-53 relative.  g 16-byte aligned: 16-byte loads; g only 4-byte aligned (an offset view): dword loads of the same elements
+ * in the same order, the same bits.  n == 0: S = 0 (unchanged when accumulating).
+ * partials: mmdyn_grad_sumsq_blocks(n) doubles of workspace.
+ * Checked on the host: partials or clip null, or g null with n != 0: MMDYN_ERR_NULL; n < 0 or g not 4-byte aligned:
+ * MMDYN_ERR_SHAPE. */
+int mmdyn_grad_sumsq(const float* g, int64_t n, double* partials, double* clip, int accumulate, void* stream);
+/* One thread, fp64: clip[1] = norm = |grad_scale| sqrt(clip[0]); clip[2] = coef = min(1, max_norm / (norm + 1e-6)); clip[3] += 1
+ * when coef < 1 and the norm is finite.  grad_scale: what the optimiser step multiplies the buffer by (1 / (world size * loss
+ * scale)), so the norm is that of the gradient the step applies.  max_norm = +inf: coef is exactly 1 -- report, never clip.  A
+ * non-finite S follows IEEE arithmetic (NaN -> norm and coef NaN; +inf -> norm inf, coef 0) and is never counted as clipped: what
+ * such a step does is the guard's decision (mmdyn_adam_step_clipped).
+ * Checked on the host: clip null: MMDYN_ERR_NULL; max_norm <= 0 or NaN: MMDYN_ERR_SHAPE. */
+int mmdyn_grad_clip_coef(double* clip, float grad_scale, float max_norm, void* stream);
+/* mmdyn_adam_step whose gradient factor is f = (float)((double)grad_scale * clip[2]) instead of grad_scale: with clip[2] == 1.0 the
+ * step is mmdyn_adam_step's bit for bit, otherwise that of mmdyn_adam_step(grad_scale = f).  guarded != 0: state has SIX doubles
+ * and the step is skipped and counted as mmdyn_adam_step_guarded does (state[4] += 1, nothing else moves) when clip[1], the norm,
+ * is not finite -- a finite fp32 buffer cannot overflow the fp64 sum of its squares, so this is "the gradient holds inf / NaN"
+ * without a second pass over it (state[3] is not used).  Unguarded, a non-finite norm goes through the arithmetic, as in torch.
+ * Checked on the host: a null pointer: MMDYN_ERR_NULL. */
+int mmdyn_adam_step_clipped(float* p, const float* g, float* m, float* v, double* state, const double* clip, int64_t n,
+                            float lr, float beta1, float beta2, float eps, float grad_scale, int guarded, void* stream);
+/* mmdyn_sgd_step with the same factor: d = g * f + weight_decay * p (the decay is added after the clipping, as in torch). */
+int mmdyn_sgd_step_clipped(float* p, const float* g, float* momentum_buf, const double* clip, int64_t n, float lr,
+                           float momentum, float weight_decay, float grad_scale, int first, void* stream);
+
 /* ---- image decode in front of the path --------------------------------------------------------
  * transforms.Resize(input_size) + transforms.ToTensor() of datasets.py:23-31 / 375-385 on frames kept as uint8
  * HWC in HBM: Pillow's 8-bit anti-aliased bilinear resampler (libImaging/Resample.c: 22-bit fixed-point taps,

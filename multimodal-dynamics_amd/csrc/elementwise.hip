@@ -447,10 +447,22 @@ __global__ void adam_tick_guarded_kernel(double* __restrict__ state, float lr, f
   }
 }
 
+// The factor a step multiplies the gradient by: grad_scale (F = float: the kernels as they have always been, same arguments, same
+// instruction stream), or grad_scale times the coefficient of the clip state (F = ClipFactor: the *_clipped entry points) --
+// f = (float)((double)grad_scale * clip[2]), which is grad_scale bit for bit when the coefficient is 1.0.
+struct ClipFactor {
+  float grad_scale;
+  const double* clip;
+};
+__device__ __forceinline__ float grad_factor(float s) { return s; }
+__device__ __forceinline__ float grad_factor(const ClipFactor& c) { return (float)((double)c.grad_scale * c.clip[2]); }
+
+template <typename F>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, const double* __restrict__ state, int64_t n, float beta1,
-                            float beta2, float eps, float grad_scale, int guarded) {
+                            float beta2, float eps, F scale, int guarded) {
   if (guarded && state[5] != 0.0) return;
+  const float grad_scale = grad_factor(scale);
   const float step_size = (float)state[1], bc2s = (float)state[2];
   const int64_t n4 = n >> 2;
   auto upd = [&](float& pp, float gg, float& mm, float& vv) {
@@ -483,13 +495,115 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 
 // torch.optim.SGD(lr, momentum, weight_decay) as the reference configures it (problems.py:132-136: momentum 0.9,
 // weight decay 5e-4, no dampening, no Nesterov).  first != 0: the momentum buffer starts as the gradient.
+template <typename F>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
-                           float lr, float momentum, float weight_decay, float grad_scale, int first) {
+                           float lr, float momentum, float weight_decay, F scale, int first) {
+  const float grad_scale = grad_factor(scale);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float d = g[i] * grad_scale + weight_decay * p[i];
     float b = first ? d : momentum * buf[i] + d;
     buf[i] = b;
     p[i] = p[i] - lr * b;
+  }
+}
+
+// ---- clipping by the global L2 norm (torch.nn.utils.clip_grad_norm_ semantics), all on the device -------------------------------
+// Clip state: four doubles {S = sum of squares, norm, coefficient, clipped steps}, owned and zeroed once by the caller.
+//
+// S in two launches and no float atomics, so that it depends neither on arrival order nor on what the workspace held.  Stage 1: block b
+// owns elements [b * chunk, (b + 1) * chunk) of the buffer -- chunk and the block count follow from n alone (sumsq_cut), never from
+// the CU count or the grid cap of the other element-wise launches.  Thread t takes the 4-element groups t, t + 256, ... of the chunk
+// in that order into ONE fp64 accumulator (the square of an fp32 value is exact in fp64, so fused or not the sum rounds once per term), then
+// the 1-3 tail elements of the buffer's last chunk go to threads 0-2; wave_sum_d, the four wave totals in wave order, partials[b].
+// VEC: one 16-byte load per group; !VEC (a buffer that is only 4-byte aligned): four dword loads of the same elements, the same sums.
+constexpr int64_t SUMSQ_MIN_CHUNK = 4096;      // 256 threads x 4 groups of 4
+constexpr int64_t SUMSQ_MAX_BLOCKS = 2048;
+static inline void sumsq_cut(int64_t n, int64_t& blocks, int64_t& chunk) {
+  blocks = ceil_div64(n, SUMSQ_MIN_CHUNK);
+  blocks = blocks < 1 ? 1 : (blocks > SUMSQ_MAX_BLOCKS ? SUMSQ_MAX_BLOCKS : blocks);
+  chunk = (ceil_div64(n, blocks) + 3) & ~(int64_t)3;         // a multiple of 4: every chunk starts on a 16-byte lane of the buffer
+}
+
+__device__ __forceinline__ double block_sum_d(double s, double* red) {
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_sumsq_partial_kernel(const float* __restrict__ g, int64_t n, int64_t chunk,
+                                                                 double* __restrict__ partials) {
+  __shared__ double red[4];
+  // (rounding the chunk up to a multiple of 4 can leave the last blocks without elements: they write 0)
+  const int64_t b0 = (int64_t)blockIdx.x * chunk;
+  const int64_t lo = b0 < n ? b0 : n, hi = lo + chunk < n ? lo + chunk : n;
+  const int64_t n4 = (hi - lo) >> 2;
+  const float* base = g + lo;
+  double s = 0.0;
+#pragma unroll 4
+  for (int64_t i = threadIdx.x; i < n4; i += 256) {
+    f32x4 v;
+    if (VEC) {
+      v = *reinterpret_cast<const f32x4*>(base + 4 * i);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = base[4 * i + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += (double)v[k] * (double)v[k];
+  }
+  const int64_t t = lo + (n4 << 2) + threadIdx.x;
+  if (t < hi) s += (double)g[t] * (double)g[t];
+  const double tot = block_sum_d(s, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+// Stage 2, one block: thread t adds partials [t * per, (t + 1) * per) in index order (per = ceil(nb / 256): consecutive threads hold
+// consecutive runs), then the same shuffle tree and wave order as stage 1.  clip[0] = the total, or clip[0] + the total.
+__global__ __launch_bounds__(256) void grad_sumsq_final_kernel(const double* __restrict__ partials, int nb,
+                                                               double* __restrict__ clip, int accumulate) {
+  __shared__ double red[4];
+  const int per = (nb + 255) / 256;
+  double s = 0.0;
+  for (int j = 0; j < per; ++j) {
+    const int i = threadIdx.x * per + j;
+    if (i < nb) s += partials[i];
+  }
+  const double tot = block_sum_d(s, red);
+  if (threadIdx.x == 0) clip[0] = accumulate ? clip[0] + tot : tot;
+}
+
+// norm = |grad_scale| sqrt(S); coef = min(1, max_norm / (norm + 1e-6)), the arithmetic of torch.nn.utils.clip_grad_norm_, in fp64.
+// A step counts as clipped when coef < 1 and the norm is finite: an infinite norm (an inf in the gradient) gives coef = 0, which is
+// an overflowed step -- the guard's business -- and not a clipped one.
+__global__ void grad_clip_coef_kernel(double* __restrict__ clip, float grad_scale, float max_norm) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const double norm = fabs((double)grad_scale) * sqrt(clip[0]);
+    const double c = (double)max_norm / (norm + 1e-6);
+    const double coef = c < 1.0 ? c : (c != c ? c : 1.0);      // min(1, c) that keeps a NaN, as torch.clamp(max=1) does
+    clip[1] = norm;
+    clip[2] = coef;
+    if (coef < 1.0 && norm < __builtin_inf()) clip[3] += 1.0;
+  }
+}
+
+// The tick of the clipped step.  guarded (six doubles of state): "the gradient holds inf / NaN" is "the norm is not finite" -- a finite
+// buffer cannot overflow an fp64 sum of fp32 squares (n * 2^256 < 2^1024) -- so no pass of grad_nonfinite_kernel is needed.
+__global__ void adam_tick_clipped_kernel(double* __restrict__ state, const double* __restrict__ clip, float lr, float beta1,
+                                         float beta2, int guarded) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const double norm = clip[1];
+    if (guarded && !(fabs(norm) < __builtin_inf())) {
+      state[4] += 1.0;
+      state[5] = 1.0;
+    } else {
+      const double t = state[0] + 1.0;
+      state[0] = t;
+      state[1] = (double)lr / (1.0 - pow((double)beta1, t));
+      state[2] = sqrt(1.0 - pow((double)beta2, t));
+      if (guarded) state[5] = 0.0;
+    }
   }
 }
 
@@ -643,7 +757,7 @@ extern "C" int mmdyn_cast_bf16_to_f32(const void* src, float* dst, int64_t n, vo
 extern "C" int mmdyn_sgd_step(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum,
                               float weight_decay, float grad_scale, int first, void* stream) {
   if (!p || !g || !momentum_buf) return MMDYN_ERR_NULL;
-  hipLaunchKernelGGL(sgd_kernel, dim3(ew_grid(n)), dim3(256), 0, ST, p, g, momentum_buf, n, lr, momentum, weight_decay,
+  hipLaunchKernelGGL(sgd_kernel<float>, dim3(ew_grid(n)), dim3(256), 0, ST, p, g, momentum_buf, n, lr, momentum, weight_decay,
                      grad_scale, first);
   MMDYN_LAUNCH_CHECK();
 }
@@ -652,7 +766,7 @@ extern "C" int mmdyn_adam_step(float* p, const float* g, float* m, float* v, dou
                                void* stream) {
   if (!p || !g || !m || !v || !state) return MMDYN_ERR_NULL;
   hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, ST, state, lr, beta1, beta2);
-  hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ST, p, g, m, v, state, n, beta1,
+  hipLaunchKernelGGL(adam_kernel<float>, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ST, p, g, m, v, state, n, beta1,
                      beta2, eps, grad_scale, 0);
   MMDYN_LAUNCH_CHECK();
 }
@@ -662,7 +776,47 @@ extern "C" int mmdyn_adam_step_guarded(float* p, const float* g, float* m, float
   if (!p || !g || !m || !v || !state) return MMDYN_ERR_NULL;
   hipLaunchKernelGGL(grad_nonfinite_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ST, g, n, state);
   hipLaunchKernelGGL(adam_tick_guarded_kernel, dim3(1), dim3(64), 0, ST, state, lr, beta1, beta2);
-  hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ST, p, g, m, v, state, n, beta1,
+  hipLaunchKernelGGL(adam_kernel<float>, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ST, p, g, m, v, state, n, beta1,
                      beta2, eps, grad_scale, 1);
+  MMDYN_LAUNCH_CHECK();
+}
+extern "C" int mmdyn_grad_sumsq_blocks(int64_t n) {
+  int64_t blocks, chunk;
+  sumsq_cut(n < 0 ? 0 : n, blocks, chunk);
+  return (int)blocks;
+}
+extern "C" int mmdyn_grad_sumsq(const float* g, int64_t n, double* partials, double* clip, int accumulate, void* stream) {
+  if ((!g && n != 0) || !partials || !clip) return MMDYN_ERR_NULL;      // (an empty tensor may come without an address)
+  if (n < 0 || ((uintptr_t)g & 3)) return MMDYN_ERR_SHAPE;
+  int64_t blocks, chunk;
+  sumsq_cut(n, blocks, chunk);
+  if (((uintptr_t)g & 15) == 0)
+    hipLaunchKernelGGL(grad_sumsq_partial_kernel<true>, dim3((int)blocks), dim3(256), 0, ST, g, n, chunk, partials);
+  else
+    hipLaunchKernelGGL(grad_sumsq_partial_kernel<false>, dim3((int)blocks), dim3(256), 0, ST, g, n, chunk, partials);
+  hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(256), 0, ST, partials, (int)blocks, clip, accumulate);
+  MMDYN_LAUNCH_CHECK();
+}
+extern "C" int mmdyn_grad_clip_coef(double* clip, float grad_scale, float max_norm, void* stream) {
+  if (!clip) return MMDYN_ERR_NULL;
+  if (!(max_norm > 0.f)) return MMDYN_ERR_SHAPE;             // (also NaN)
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(64), 0, ST, clip, grad_scale, max_norm);
+  MMDYN_LAUNCH_CHECK();
+}
+extern "C" int mmdyn_adam_step_clipped(float* p, const float* g, float* m, float* v, double* state, const double* clip,
+                                       int64_t n, float lr, float beta1, float beta2, float eps, float grad_scale,
+                                       int guarded, void* stream) {
+  if (!p || !g || !m || !v || !state || !clip) return MMDYN_ERR_NULL;
+  hipLaunchKernelGGL(adam_tick_clipped_kernel, dim3(1), dim3(64), 0, ST, state, clip, lr, beta1, beta2, guarded);
+  hipLaunchKernelGGL(adam_kernel<ClipFactor>, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ST, p, g, m, v, state, n, beta1,
+                     beta2, eps, ClipFactor{grad_scale, clip}, guarded ? 1 : 0);
+  MMDYN_LAUNCH_CHECK();
+}
+extern "C" int mmdyn_sgd_step_clipped(float* p, const float* g, float* momentum_buf, const double* clip, int64_t n,
+                                      float lr, float momentum, float weight_decay, float grad_scale, int first,
+                                      void* stream) {
+  if (!p || !g || !momentum_buf || !clip) return MMDYN_ERR_NULL;
+  hipLaunchKernelGGL(sgd_kernel<ClipFactor>, dim3(ew_grid(n)), dim3(256), 0, ST, p, g, momentum_buf, n, lr, momentum,
+                     weight_decay, ClipFactor{grad_scale, clip}, first);
   MMDYN_LAUNCH_CHECK();
 }

@@ -126,6 +126,11 @@ _SIGNATURES = {
     "mmdyn_adam_step": "ppppp" + "l" + "fffff" + "p",
     "mmdyn_adam_step_guarded": "ppppp" + "l" + "fffff" + "p",
     "mmdyn_sgd_step": "ppp" + "l" + "ffff" + "i" + "p",
+    "mmdyn_grad_sumsq_blocks": "l",
+    "mmdyn_grad_sumsq": "p" + "l" + "pp" + "i" + "p",
+    "mmdyn_grad_clip_coef": "p" + "ff" + "p",
+    "mmdyn_adam_step_clipped": "pppppp" + "l" + "fffff" + "i" + "p",
+    "mmdyn_sgd_step_clipped": "pppp" + "l" + "ffff" + "i" + "p",
     "mmdyn_igemm_nt_mx": "pppppppppppp" + "iiiiiiiiiiiiii" + "i" + "pp",
     "mmdyn_wgrad_tn_mx": "ppp" + "iiiiiiiiiii" + "i" + "p",
     "mmdyn_split_planes": "pp" + "l" + "i" + "p",

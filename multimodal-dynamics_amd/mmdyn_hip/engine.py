@@ -259,7 +259,7 @@ class MVAEStep:
 
     def __init__(self, model, lr=1e-3, pose_multiplier=1000.0, betas=(0.9, 0.999), eps=1e-8, noise=None,
                  process_group=None, world_size=1, two_lanes=True, precision="fp32x3", exact_running_stats=False, sync_bn=False,
-                 defer_wgrad=None, grad_reduce_bf16=None, group_heads=True, keep_logits=False):
+                 defer_wgrad=None, grad_reduce_bf16=None, group_heads=True, keep_logits=False, max_grad_norm=None):
         # --conditional (vae.py:231-237, 286-291): the condition joins the 512 features in front of the image encoders' heads
         # and the latent in front of the image decoders' first layer; the pose MLPs are built unconditional (vae.py:117-123)
         self.conditional = bool(getattr(model, "conditional", False))
@@ -349,6 +349,17 @@ class MVAEStep:
         self.adam_m = torch.zeros_like(self.params.flat)
         self.adam_v = torch.zeros_like(self.params.flat)
         self.adam_state = torch.zeros(6, dtype=torch.float64, device=dev)     # (six: the guarded step of the fp16 modes)
+        # Clipping by the global L2 norm (None: off -- optimizer_step is the launches it has always been).  The norm is that of the
+        # gradient Adam applies: the flat buffer after the all-reduce, times 1 / (world * loss scale) -- the averaged, unscaled
+        # gradient whatever the loss scale of the fp16 modes, the same bits on every rank (each reduces the same buffer in the
+        # same order, so no further collective).  Sum of squares, coefficient and the clipped Adam step are device-side and
+        # allocate nothing, so the captured step holds them where it holds Adam.  inf: report the norm, never clip.  Fixed per
+        # engine, so the capture key does not carry it.
+        self.max_grad_norm = None if max_grad_norm is None else ops.check_max_norm(max_grad_norm, "max_grad_norm")
+        self.clip = self._sumsq_ws = None       # clip: fp64 {sum of squares, norm, coefficient, clipped steps}
+        if self.max_grad_norm is not None:
+            self.clip = torch.zeros(4, dtype=torch.float64, device=dev)
+            self._sumsq_ws = torch.empty(ops.backend_op("grad_sumsq_blocks")(self.params.total), dtype=torch.float64, device=dev)
         self.acc = torch.zeros(4, 8, dtype=torch.float64, device=dev)   # bce / mse / kl per pass (+ unmasked bce: --mask-loss)
         self.loss = torch.zeros(1, device=dev)
         self.partials = torch.zeros(8, device=dev)
@@ -1058,6 +1069,14 @@ class MVAEStep:
         for h in handles:
             h.wait()
         scale = self.loss_scale if loss_scale is None else loss_scale
+        if self.max_grad_norm is not None:
+            # one read of the gradient serves the norm AND the overflow guard of the fp16 modes (a non-finite norm skips the step)
+            ops.B.grad_sumsq(self.params.grad, self._sumsq_ws, self.clip)
+            ops.B.grad_clip_coef(self.clip, 1.0 / (self.world * scale), self.max_grad_norm)
+            ops.B.adam_step_clipped(self.params.flat, self.params.grad, self.adam_m, self.adam_v, self.adam_state, self.clip,
+                                    self.lr, self.betas[0], self.betas[1], self.eps, 1.0 / (self.world * scale),
+                                    guarded=bool(self._scale_per_sample))
+            return
         ops.B.adam_step(self.params.flat, self.params.grad, self.adam_m, self.adam_v, self.adam_state, self.lr,
                         self.betas[0], self.betas[1], self.eps, 1.0 / (self.world * scale),
                         guarded=bool(self._scale_per_sample))
@@ -1066,6 +1085,17 @@ class MVAEStep:
     def skipped_steps(self):
         """Optimiser steps the overflow guard of the fp16 modes has skipped so far (a gradient held inf / NaN)."""
         return int(self.adam_state[4])
+
+    @property
+    def grad_norm(self):
+        """``max_grad_norm`` engines: global L2 norm of the last step's averaged, unscaled gradient before clipping (None without
+        ``max_grad_norm``).  Synchronises."""
+        return None if self.clip is None else float(self.clip[1])
+
+    @property
+    def clipped_steps(self):
+        """Optimiser steps whose gradient was scaled down to ``max_grad_norm`` so far.  Synchronises."""
+        return 0 if self.clip is None else int(self.clip[3])
 
     @_with_precision
     def train_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch", available=None,

@@ -53,6 +53,9 @@ _BUILD_FLAGS = (
                                       "per-frame availability table selects each row's experts in the posterior and drops the "
                                       "reconstruction terms of absent targets (default: every frame counts as complete)"),
     ("synthetic-absent", 0.0, float, "with --synthetic-batches: share of (frame, image modality) pairs marked missing"),
+    ("grad-clip", 0.0, float, "clip every step's gradient by its global L2 norm (torch.nn.utils.clip_grad_norm_ arithmetic, on the "
+                              "device, inside the replayed step) and log Grad_norm/train_epoch and Grad_clipped/train_epoch; "
+                              "inf logs the norm without clipping; 0 = off"),
 )
 
 
@@ -67,8 +70,11 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     assert args.problem_type in config.PROBLEM_TYPES, "Invalid problem type."
+    if not args.grad_clip >= 0:                      # (a negative value, or NaN)
+        parser.error(f"--grad-clip must be a norm > 0, inf, or 0 for off (got {args.grad_clip})")
     L = args.synthetic_seq_length
     shock = 3 if args.conditional else 0
     if args.synthetic_batches > 0:

@@ -9,6 +9,7 @@ libmmdyn_hip.so.  There is no CPU / ATen fallback: a CPU tensor raises.
 exercise the host-side orchestration on a machine without a GPU; nothing in the product does.
 """
 import ctypes
+import numbers
 
 import os
 
@@ -64,6 +65,18 @@ def _half(*fmts):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def _check_clip(clip, name):
+    if not torch.is_tensor(clip) or clip.dtype != torch.float64 or clip.numel() != 4 or not clip.is_contiguous():
+        raise ValueError(f"mmdyn_{name}: clip must be four contiguous fp64 values {{sum of squares, norm, coefficient, clipped steps}}")
+
+
+def check_max_norm(value, what):
+    """``value`` as a float if it is a real number > 0 (inf allowed: report the norm, never clip), else a ValueError naming ``what``."""
+    if not (isinstance(value, numbers.Real) and not isinstance(value, bool) and float(value) > 0.0):
+        raise ValueError(f"{what} must be a real number > 0 (inf: report the gradient norm without clipping), got {value!r}")
+    return float(value)
 
 
 class Planes:
@@ -1657,6 +1670,43 @@ class HipBackend:
     def sgd_step(self, p, g, buf, lr, momentum, weight_decay, grad_scale, first):
         check(self.lib.mmdyn_sgd_step(_ptr(p), _ptr(g), _ptr(buf), p.numel(), lr, momentum, weight_decay, grad_scale,
                                       int(first), _stream()), "mmdyn_sgd_step")
+
+    # ---- clipping by the global L2 norm: clip = fp64 [4] on the device {sum of squares, norm, coefficient, clipped steps} ----
+    def grad_sumsq_blocks(self, n):
+        """Doubles of workspace ``grad_sumsq`` wants for a buffer of ``n`` elements (a function of n alone)."""
+        return self.lib.mmdyn_grad_sumsq_blocks(int(n))
+
+    def grad_sumsq(self, g, partials, clip, accumulate=False):
+        """clip[0] = sum g^2 in fp64 (``accumulate``: added to clip[0]), deterministic.  g: fp32, any number of elements, 4-byte
+        aligned (a view that starts inside a buffer is fine); partials: fp64 workspace of ``grad_sumsq_blocks(g.numel())``."""
+        _check_clip(clip, "grad_sumsq")
+        need = self.grad_sumsq_blocks(g.numel())
+        if partials is None or partials.dtype != torch.float64 or partials.numel() < need:
+            raise ValueError(f"mmdyn_grad_sumsq: partials must be an fp64 workspace of at least {need} values for {g.numel()} elements")
+        check(self.lib.mmdyn_grad_sumsq(_ptr(g), g.numel(), _ptr(partials, torch.float64), _ptr(clip, torch.float64),
+                                        int(bool(accumulate)), _stream()), "mmdyn_grad_sumsq")
+
+    def grad_clip_coef(self, clip, grad_scale, max_norm):
+        """clip[1] = |grad_scale| sqrt(clip[0]), clip[2] = min(1, max_norm / (clip[1] + 1e-6)), clip[3] += 1 when that clips."""
+        _check_clip(clip, "grad_clip_coef")
+        max_norm = check_max_norm(max_norm, "max_norm")
+        check(self.lib.mmdyn_grad_clip_coef(_ptr(clip, torch.float64), grad_scale, max_norm, _stream()), "mmdyn_grad_clip_coef")
+
+    def adam_step_clipped(self, p, g, m, v, state, clip, lr, beta1, beta2, eps, grad_scale, guarded=False):
+        """``adam_step`` with the gradient factor float32(grad_scale * clip[2]).  guarded: six doubles of state; the step is skipped
+        and counted in state[4] when the norm in clip[1] is not finite."""
+        _check_clip(clip, "adam_step_clipped")
+        if state.numel() < (6 if guarded else 3):
+            raise ValueError("mmdyn_hip: the guarded Adam step keeps six doubles of state" if guarded else
+                             "mmdyn_hip: the Adam step keeps three doubles of state")
+        check(self.lib.mmdyn_adam_step_clipped(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(state, torch.float64),
+                                               _ptr(clip, torch.float64), p.numel(), lr, beta1, beta2, eps, grad_scale,
+                                               int(bool(guarded)), _stream()), "mmdyn_adam_step_clipped")
+
+    def sgd_step_clipped(self, p, g, buf, clip, lr, momentum, weight_decay, grad_scale, first):
+        _check_clip(clip, "sgd_step_clipped")
+        check(self.lib.mmdyn_sgd_step_clipped(_ptr(p), _ptr(g), _ptr(buf), _ptr(clip, torch.float64), p.numel(), lr, momentum,
+                                              weight_decay, grad_scale, int(first), _stream()), "mmdyn_sgd_step_clipped")
 
 
     # ---- image decode (uint8 HWC frames in HBM -> float32 CHW) ----

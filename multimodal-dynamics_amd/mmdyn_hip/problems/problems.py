@@ -35,15 +35,56 @@ from ..models import functional as Fn
 from ..models.models import setup_model
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam(lr) semantics (betas (0.9, 0.999), eps 1e-8, no weight decay) on the mmdyn_adam_step
-    kernel, one launch per parameter tensor.  Used by the un-fused (reference-schedule) mode."""
+class _GlobalNormClip:
+    """``max_norm`` of the fused optimisers: the gradients of all parameter tensors are clipped by their global L2 norm, the
+    arithmetic of ``torch.nn.utils.clip_grad_norm_``, on the device.  One ``grad_sumsq`` per tensor that has a gradient (the first
+    overwrites the sum of squares, the rest accumulate), one ``grad_clip_coef``, then the clipped step per tensor.  ``max_norm=inf``
+    reports the norm and never clips; ``None`` (default) is the unclipped code path."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def _init_clip(self, max_norm):
+        self.max_norm = None if max_norm is None else ops.check_max_norm(max_norm, "max_norm")
+        self._clip = self._partials = None
+
+    def _measure(self):
+        """Sum of squares, norm and coefficient of this step's gradients; returns the parameters that have one."""
+        live = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        if not live:
+            return live
+        dev = live[0].device
+        need = max(ops.B.grad_sumsq_blocks(p.numel()) for p in live)
+        if self._clip is None:
+            self._clip = torch.zeros(4, dtype=torch.float64, device=dev)
+        if self._partials is None or self._partials.numel() < need:
+            self._partials = torch.empty(need, dtype=torch.float64, device=dev)
+        for i, p in enumerate(live):
+            ops.B.grad_sumsq(p.grad.contiguous().view(-1), self._partials, self._clip, accumulate=i > 0)
+        ops.B.grad_clip_coef(self._clip, 1.0, self.max_norm)
+        return live
+
+    @property
+    def grad_norm(self):
+        """Global L2 norm of the last step's gradients before clipping (None before the first clipped step).  Synchronises."""
+        return None if self._clip is None else float(self._clip[1])
+
+    @property
+    def clipped_steps(self):
+        """Steps whose gradients were scaled down so far.  Synchronises."""
+        return 0 if self._clip is None else int(self._clip[3])
+
+
+class FusedAdam(_GlobalNormClip, torch.optim.Optimizer):
+    """torch.optim.Adam(lr) semantics (betas (0.9, 0.999), eps 1e-8, no weight decay) on the mmdyn_adam_step
+    kernel, one launch per parameter tensor.  Used by the un-fused (reference-schedule) mode.  ``max_norm``: see
+    :class:`_GlobalNormClip` (mmdyn_adam_step_clipped)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+        self._init_clip(max_norm)
 
     @torch.no_grad()
     def step(self):
+        if self.max_norm is not None:
+            self._measure()
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
@@ -53,19 +94,27 @@ class FusedAdam(torch.optim.Optimizer):
                     st["m"], st["v"] = torch.zeros_like(p), torch.zeros_like(p)
                     st["state"] = torch.zeros(3, dtype=torch.float64, device=p.device)
                 b1, b2 = group["betas"]
+                if self.max_norm is not None:
+                    ops.B.adam_step_clipped(p.data.view(-1), p.grad.contiguous().view(-1), st["m"].view(-1), st["v"].view(-1),
+                                            st["state"], self._clip, group["lr"], b1, b2, group["eps"], 1.0)
+                    continue
                 ops.B.adam_step(p.data.view(-1), p.grad.contiguous().view(-1), st["m"].view(-1), st["v"].view(-1),
                                 st["state"], group["lr"], b1, b2, group["eps"], 1.0)
 
 
-class FusedSGD(torch.optim.Optimizer):
+class FusedSGD(_GlobalNormClip, torch.optim.Optimizer):
     """torch.optim.SGD(lr, momentum=0.9, weight_decay=5e-4) -- the reference's SGD option (problems.py:132-136) -- on
-    the mmdyn_sgd_step kernel."""
+    the mmdyn_sgd_step kernel.  ``max_norm``: see :class:`_GlobalNormClip` (mmdyn_sgd_step_clipped; the weight decay is added
+    after the clipping, as in torch)."""
 
-    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=5e-4):
+    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=5e-4, max_norm=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        self._init_clip(max_norm)
 
     @torch.no_grad()
     def step(self):
+        if self.max_norm is not None:
+            self._measure()
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
@@ -74,6 +123,10 @@ class FusedSGD(torch.optim.Optimizer):
                 first = not st
                 if first:
                     st["buf"] = torch.zeros_like(p)
+                if self.max_norm is not None:
+                    ops.B.sgd_step_clipped(p.data.view(-1), p.grad.contiguous().view(-1), st["buf"].view(-1), self._clip,
+                                           group["lr"], group["momentum"], group["weight_decay"], 1.0, first)
+                    continue
                 ops.B.sgd_step(p.data.view(-1), p.grad.contiguous().view(-1), st["buf"].view(-1), group["lr"],
                                group["momentum"], group["weight_decay"], 1.0, first)
 
@@ -177,8 +230,15 @@ class Problem:
 
     def set_optimizer(self):
         assert (self.parameters['optimizer'] in config.OPTIMIZERS), "loss name not implemented in Problem"
+        # --grad-clip (this build): clip every step's gradient by its global L2 norm and log the norm; 0 (default) = off, the unclipped
+        # launches; inf = log the norm, never clip
+        clip = self.parameters.get('grad_clip') or None
+        if clip is not None:
+            clip = ops.check_max_norm(clip, "--grad-clip")
+        self._grad_clip = clip
         if self.parameters['optimizer'] == 'SGD':      # reference: momentum 0.9, weight decay 5e-4 (problems.py:132-136)
-            self._optimizer = FusedSGD(self._model.parameters(), lr=self.parameters['lr'], momentum=0.9, weight_decay=5e-4)
+            self._optimizer = FusedSGD(self._model.parameters(), lr=self.parameters['lr'], momentum=0.9, weight_decay=5e-4,
+                                       max_norm=clip)
             return
         # the fused step takes the dict-shaped inputs of seq / dyn modeling (with the loss mask of --mask-loss when the model has
         # no pose term, and the shock condition of --conditional); everything else (plain reconstruction, cnn-vae, regressor,
@@ -193,12 +253,13 @@ class Problem:
         precision = self.parameters.get('precision', 'fp32x3')
         if use_engine:
             self._step = MVAEStep(self._model, lr=self.parameters['lr'], pose_multiplier=self._pose_multiplier,
-                                  precision=precision, exact_running_stats=bool(self.parameters.get('exact_running_stats')))
+                                  precision=precision, exact_running_stats=bool(self.parameters.get('exact_running_stats')),
+                                  max_grad_norm=clip)
         elif precision not in ('fp32', 'fp32x3'):
             raise ValueError("--precision %s is a mode of the fused cnn-mvae step; this configuration runs the module "
                              "path, which computes in fp32" % precision)
         # the module path's optimiser: also what a batch the fused step does not take falls back to
-        self._optimizer = FusedAdam(self._model.parameters(), lr=self.parameters['lr'])
+        self._optimizer = FusedAdam(self._model.parameters(), lr=self.parameters['lr'], max_norm=clip)
 
     def _anneal_KL(self, epoch):
         if epoch < self.parameters['annealing_epochs']:
@@ -214,6 +275,11 @@ class Problem:
         dev_loss = dev_acc = None        # fused path: loss and per-pass sums accumulate ON THE DEVICE, read once per epoch
         dev_n = dev_rows = 0             # (the reference's loss.item() per step, problems.py:156, would stall the replay)
         dev_perf, dev_perf_n = None, 0   # --use-availability: the per-step means over PRESENT targets, summed on the device
+        # --grad-clip: the pre-clip norms are summed where the losses are (fused: on the device, read once per epoch; module path:
+        # beside the step's float(loss)); the clipped steps of the epoch are the growth of the two device-side counts
+        clipping = getattr(self, '_grad_clip', None) is not None
+        dev_gnorm, gnorm_sum = None, 0.0
+        clipped_before = getattr(self, '_clipped_seen', 0)
         try:
             n_batches = len(self.train_loader)
         except TypeError:
@@ -246,6 +312,10 @@ class Problem:
                     dev_loss, dev_acc = torch.zeros_like(loss, dtype=torch.float64), torch.zeros_like(self._step.acc)
                 dev_loss += loss.detach().to(torch.float64)
                 dev_n += 1
+                if clipping:
+                    if dev_gnorm is None:
+                        dev_gnorm = torch.zeros((), dtype=torch.float64, device=loss.device)
+                    dev_gnorm += self._step.clip[1]
                 if avail_kw:
                     step_perf = self._fused_perf_present_dev()
                     dev_perf = step_perf if dev_perf is None else dev_perf + step_perf
@@ -260,6 +330,8 @@ class Problem:
                 loss.backward()
                 self._optimizer.step()
             train_loss += float(loss.detach()) if torch.is_tensor(loss) else float(loss)
+            if clipping:
+                gnorm_sum += self._optimizer.grad_norm or 0.0
             n += 1
             for k, v in outputs.get('perf_measure', {}).items():
                 perf[k] += v
@@ -274,6 +346,12 @@ class Problem:
             n += dev_n
         self._logger_dict['Loss/train_epoch'].append(train_loss / max(n, 1))
         self._logger_dict['KL_annealing/train_epoch'].append(self._kl_weight)
+        if clipping:
+            if dev_gnorm is not None:
+                gnorm_sum += float(dev_gnorm)
+            self._clipped_seen = (self._step.clipped_steps if self._step is not None else 0) + self._optimizer.clipped_steps
+            self._logger_dict['Grad_norm/train_epoch'].append(gnorm_sum / max(n, 1))
+            self._logger_dict['Grad_clipped/train_epoch'].append(self._clipped_seen - clipped_before)
         for k, v in perf.items():
             self._logger_dict['Perf_measure_train/' + k].append(v / max(n, 1))
         return dict(perf)
