@@ -999,6 +999,34 @@ int mmdyn_adam_step_clipped(float* p, const float* g, float* m, float* v, double
 int mmdyn_sgd_step_clipped(float* p, const float* g, float* momentum_buf, const double* clip, int64_t n, float lr,
                            float momentum, float weight_decay, float grad_scale, int first, void* stream);
 
+/* ---- exponential moving average of the parameters (torch.optim.swa_utils.AveragedModel with an EMA rule, use_buffers=False) ---- */
+/* ema_state: FOUR doubles on the device, owned by the caller: {updates done n, decay d, 1 - d_n of the current update, warm-up
+ * flag}.  The caller writes d (in [0, 1)) and the flag once and zeroes the rest; everything below runs on the device without a host
+ * read, so a captured step replays it.  Added without touching an existing signature: the revision stays 6.
+ *
+ * mmdyn_ema_tick: one thread, fp64.  d_n = d, or with the warm-up flag set min(d, (1 + n) / (10 + n)) for the count n BEFORE this
+ * update; ema_state[2] = 1 - d_n, ema_state[0] = n + 1.  adam_state (nullable): the SIX-double state of a guarded Adam step whose
+ * tick has already run; when its skip word (adam_state[5]) is set, the tick changes nothing -- a skipped step is no update of the
+ * average.  Checked on the host: ema_state null: MMDYN_ERR_NULL. */
+int mmdyn_ema_tick(double* ema_state, const double* adam_state, void* stream);
+/* ema[i] = fmaf(omd, p[i] - ema[i], ema[i]) in fp32, omd = (float)ema_state[2]: the difference rounds once, the fused multiply-add
+ * once.  One call per parameter tensor behind one mmdyn_ema_tick per optimiser step (the module path).  Both buffers 16-byte aligned:
+ * 16-byte accesses and a scalar tail; otherwise (4-byte aligned views) dword accesses -- the same bits.  No atomics; no element
+ * depends on the grid.  The call applies ema_state[2] as it stands: a caller whose step can be skipped uses mmdyn_adam_step_ema.
+ * Checked on the host: ema_state null, or ema / p null with n != 0: MMDYN_ERR_NULL; n < 0, a buffer not 4-byte aligned, or ema
+ * overlapping p: MMDYN_ERR_SHAPE. */
+int mmdyn_ema_update(float* ema, const float* p, const double* ema_state, int64_t n, void* stream);
+/* The Adam step that keeps the average in the same pass: p, g, m, v are read once, ema is read and written, each element of ema
+ * moving towards the parameter value this step has just written, by the arithmetic of mmdyn_ema_update (same bits as the step
+ * followed by mmdyn_ema_tick + mmdyn_ema_update).  clip null: mmdyn_adam_step (guarded == 0) or mmdyn_adam_step_guarded (guarded != 0)
+ * bit for bit in p, m, v and state; clip non-null: mmdyn_adam_step_clipped(guarded).  One launch more than that step: the EMA tick,
+ * behind Adam's.  A step the guard skips leaves ema and ema_state untouched as well.
+ * Checked on the host: a null pointer other than clip: MMDYN_ERR_NULL; n < 0, ema not 16-byte aligned, or ema overlapping p:
+ * MMDYN_ERR_SHAPE. */
+int mmdyn_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, double* state, const double* clip,
+                        double* ema_state, int64_t n, float lr, float beta1, float beta2, float eps, float grad_scale,
+                        int guarded, void* stream);
+
 /* ---- image decode in front of the path --------------------------------------------------------
  * transforms.Resize(input_size) + transforms.ToTensor() of datasets.py:23-31 / 375-385 on frames kept as uint8
  * HWC in HBM: Pillow's 8-bit anti-aliased bilinear resampler (libImaging/Resample.c: 22-bit fixed-point taps,

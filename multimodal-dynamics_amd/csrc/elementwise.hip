@@ -457,6 +457,52 @@ struct ClipFactor {
 __device__ __forceinline__ float grad_factor(float s) { return s; }
 __device__ __forceinline__ float grad_factor(const ClipFactor& c) { return (float)((double)c.grad_scale * c.clip[2]); }
 
+// ---- exponential moving average of the parameters (Polyak average) ------------------------------------------------------------
+// EMA state: four doubles owned by the caller {updates done n, decay d (written once by the host), 1 - d_n of the current update,
+// warm-up flag}.  The tick (one thread, fp64): d_n = d, or with warm-up min(d, (1 + n) / (10 + n)) for the count n BEFORE this
+// update; state[2] = 1 - d_n, state[0] = n + 1.  skip (the six-double state of a guarded Adam step, or null): a step the overflow
+// guard skips is no update of the average either -- the tick changes nothing.
+__global__ void ema_tick_kernel(double* __restrict__ es, const double* __restrict__ skip) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (skip && skip[5] != 0.0) return;
+    const double n = es[0], d = es[1];
+    double dn = d;
+    if (es[3] != 0.0) {
+      const double w = (1.0 + n) / (10.0 + n);
+      dn = w < d ? w : d;
+    }
+    es[2] = 1.0 - dn;
+    es[0] = n + 1.0;
+  }
+}
+
+// One element of the average: e + omd (p - e) with the difference rounded to fp32 and ONE more rounding -- the fmaf is written out,
+// so the fused Adam pass and the stand-alone kernel give the same bits whatever the compiler contracts elsewhere.
+__device__ __forceinline__ float ema_elem(float e, float p, float omd) { return __builtin_fmaf(omd, p - e, e); }
+
+// F = WithEma<float> / WithEma<ClipFactor>: the same gradient factor, and the step also moves the average `ema` towards the
+// parameter it has just written (omd = (float)ema_state[2], set by ema_tick_kernel in front of this launch).
+template <typename S>
+struct WithEma {
+  S scale;
+  float* ema;
+  const double* ema_state;
+};
+template <typename S>
+__device__ __forceinline__ float grad_factor(const WithEma<S>& w) { return grad_factor(w.scale); }
+template <typename F>
+struct ema_of {
+  static constexpr bool on = false;
+  __device__ static __forceinline__ float* ptr(const F&) { return nullptr; }
+  __device__ static __forceinline__ float omd(const F&) { return 0.f; }
+};
+template <typename S>
+struct ema_of<WithEma<S>> {
+  static constexpr bool on = true;
+  __device__ static __forceinline__ float* ptr(const WithEma<S>& w) { return w.ema; }
+  __device__ static __forceinline__ float omd(const WithEma<S>& w) { return (float)w.ema_state[2]; }
+};
+
 template <typename F>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, const double* __restrict__ state, int64_t n, float beta1,
@@ -464,6 +510,9 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   if (guarded && state[5] != 0.0) return;
   const float grad_scale = grad_factor(scale);
   const float step_size = (float)state[1], bc2s = (float)state[2];
+  constexpr bool EMA = ema_of<F>::on;
+  float* __restrict__ const ema = ema_of<F>::ptr(scale);
+  const float omd = ema_of<F>::omd(scale);
   const int64_t n4 = n >> 2;
   auto upd = [&](float& pp, float gg, float& mm, float& vv) {
     gg *= grad_scale;
@@ -476,6 +525,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
        i += (int64_t)gridDim.x * blockDim.x) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i], gg = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mm = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+    f32x4 ee;
+    if constexpr (EMA) ee = reinterpret_cast<f32x4*>(ema)[i];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float a = pp[k], b = mm[k], c = vv[k];
@@ -483,14 +534,36 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
       pp[k] = a;
       mm[k] = b;
       vv[k] = c;
+      if constexpr (EMA) ee[k] = ema_elem(ee[k], a, omd);
     }
     reinterpret_cast<f32x4*>(p)[i] = pp;
     reinterpret_cast<f32x4*>(m)[i] = mm;
     reinterpret_cast<f32x4*>(v)[i] = vv;
+    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ee;
   }
   for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
+       i += (int64_t)gridDim.x * blockDim.x) {
     upd(p[i], g[i], m[i], v[i]);
+    if constexpr (EMA) ema[i] = ema_elem(ema[i], p[i], omd);
+  }
+}
+
+// The stand-alone update (the module path: one tick per optimiser step, then one launch per parameter tensor): ema[i] moves towards
+// p[i] by omd = (float)state[2].  Every element is computed from its own two inputs: no atomics, nothing depends on the grid.
+// VEC: 16-byte accesses and a scalar tail; !VEC (a buffer that is only 4-byte aligned): dword accesses, the same bits.
+template <bool VEC>
+__global__ void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, const double* __restrict__ es, int64_t n) {
+  const float omd = (float)es[2];
+  const int64_t n4 = VEC ? n >> 2 : 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 ee = reinterpret_cast<f32x4*>(ema)[i];
+    const f32x4 pp = reinterpret_cast<const f32x4*>(p)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ee[k] = ema_elem(ee[k], pp[k], omd);
+    reinterpret_cast<f32x4*>(ema)[i] = ee;
+  }
+  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    ema[i] = ema_elem(ema[i], p[i], omd);
 }
 
 // torch.optim.SGD(lr, momentum, weight_decay) as the reference configures it (problems.py:132-136: momentum 0.9,
@@ -818,5 +891,48 @@ extern "C" int mmdyn_sgd_step_clipped(float* p, const float* g, float* momentum_
   if (!p || !g || !momentum_buf || !clip) return MMDYN_ERR_NULL;
   hipLaunchKernelGGL(sgd_kernel<ClipFactor>, dim3(ew_grid(n)), dim3(256), 0, ST, p, g, momentum_buf, n, lr, momentum,
                      weight_decay, ClipFactor{grad_scale, clip}, first);
+  MMDYN_LAUNCH_CHECK();
+}
+// n elements at ema and n at p share a byte
+static inline bool ema_overlaps(const float* ema, const float* p, int64_t n) {
+  const uintptr_t a = (uintptr_t)ema, b = (uintptr_t)p, len = (uintptr_t)n * sizeof(float);
+  return a < b + len && b < a + len;
+}
+extern "C" int mmdyn_ema_tick(double* ema_state, const double* adam_state, void* stream) {
+  if (!ema_state) return MMDYN_ERR_NULL;
+  hipLaunchKernelGGL(ema_tick_kernel, dim3(1), dim3(64), 0, ST, ema_state, adam_state);
+  MMDYN_LAUNCH_CHECK();
+}
+extern "C" int mmdyn_ema_update(float* ema, const float* p, const double* ema_state, int64_t n, void* stream) {
+  if (!ema_state || ((!ema || !p) && n != 0)) return MMDYN_ERR_NULL;
+  if (n < 0 || ((uintptr_t)ema & 3) || ((uintptr_t)p & 3) || ema_overlaps(ema, p, n)) return MMDYN_ERR_SHAPE;
+  if (n == 0) return MMDYN_OK;
+  if ((((uintptr_t)ema | (uintptr_t)p) & 15) == 0)
+    hipLaunchKernelGGL(ema_update_kernel<true>, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ST, ema, p, ema_state, n);
+  else
+    hipLaunchKernelGGL(ema_update_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, ST, ema, p, ema_state, n);
+  MMDYN_LAUNCH_CHECK();
+}
+extern "C" int mmdyn_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, double* state, const double* clip,
+                                   double* ema_state, int64_t n, float lr, float beta1, float beta2, float eps,
+                                   float grad_scale, int guarded, void* stream) {
+  if (!p || !g || !m || !v || !ema || !state || !ema_state) return MMDYN_ERR_NULL;
+  if (n < 0 || ((uintptr_t)ema & 15) || ema_overlaps(ema, p, n)) return MMDYN_ERR_SHAPE;
+  const dim3 grid(ew_grid(n / 4 + 1));
+  if (clip) {
+    hipLaunchKernelGGL(adam_tick_clipped_kernel, dim3(1), dim3(64), 0, ST, state, clip, lr, beta1, beta2, guarded);
+  } else if (guarded) {
+    hipLaunchKernelGGL(grad_nonfinite_kernel, grid, dim3(256), 0, ST, g, n, state);
+    hipLaunchKernelGGL(adam_tick_guarded_kernel, dim3(1), dim3(64), 0, ST, state, lr, beta1, beta2);
+  } else {
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, ST, state, lr, beta1, beta2);
+  }
+  hipLaunchKernelGGL(ema_tick_kernel, dim3(1), dim3(64), 0, ST, ema_state, guarded ? (const double*)state : nullptr);
+  if (clip)
+    hipLaunchKernelGGL(adam_kernel<WithEma<ClipFactor>>, grid, dim3(256), 0, ST, p, g, m, v, state, n, beta1, beta2, eps,
+                       WithEma<ClipFactor>{ClipFactor{grad_scale, clip}, ema, ema_state}, guarded ? 1 : 0);
+  else
+    hipLaunchKernelGGL(adam_kernel<WithEma<float>>, grid, dim3(256), 0, ST, p, g, m, v, state, n, beta1, beta2, eps,
+                       WithEma<float>{grad_scale, ema, ema_state}, guarded ? 1 : 0);
   MMDYN_LAUNCH_CHECK();
 }

@@ -131,6 +131,9 @@ _SIGNATURES = {
     "mmdyn_grad_clip_coef": "p" + "ff" + "p",
     "mmdyn_adam_step_clipped": "pppppp" + "l" + "fffff" + "i" + "p",
     "mmdyn_sgd_step_clipped": "pppp" + "l" + "ffff" + "i" + "p",
+    "mmdyn_ema_tick": "pp" + "p",
+    "mmdyn_ema_update": "ppp" + "l" + "p",
+    "mmdyn_adam_step_ema": "pppppppp" + "l" + "fffff" + "i" + "p",
     "mmdyn_igemm_nt_mx": "pppppppppppp" + "iiiiiiiiiiiiii" + "i" + "pp",
     "mmdyn_wgrad_tn_mx": "ppp" + "iiiiiiiiiii" + "i" + "p",
     "mmdyn_split_planes": "pp" + "l" + "i" + "p",

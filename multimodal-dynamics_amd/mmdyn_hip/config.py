@@ -18,8 +18,8 @@ _MODELS = {
     "cnn-mvae": ("cnn", "models.vae.MVAE: the hot path (engine.MVAEStep)"),
     "regressor": ("cnn", "models.models.Regressor"),
 }
-_OPTIMIZERS = {"SGD": "problems.FusedSGD (mmdyn_sgd_step; with --grad-clip: mmdyn_sgd_step_clipped)",
-               "Adam": "problems.FusedAdam (mmdyn_adam_step; with --grad-clip: mmdyn_adam_step_clipped)"}
+_OPTIMIZERS = {"SGD": "problems.FusedSGD (mmdyn_sgd_step; with --grad-clip: mmdyn_sgd_step_clipped; with --ema-decay: + mmdyn_ema_tick / mmdyn_ema_update)",
+               "Adam": "problems.FusedAdam (mmdyn_adam_step; with --grad-clip: mmdyn_adam_step_clipped; with --ema-decay: + mmdyn_ema_tick / mmdyn_ema_update)"}
 _MODALITIES = ("visual", "tactile", "pose", "visuotactile")
 
 PROBLEM_TYPES = list(_PROBLEMS)

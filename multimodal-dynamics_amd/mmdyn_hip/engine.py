@@ -259,7 +259,8 @@ class MVAEStep:
 
     def __init__(self, model, lr=1e-3, pose_multiplier=1000.0, betas=(0.9, 0.999), eps=1e-8, noise=None,
                  process_group=None, world_size=1, two_lanes=True, precision="fp32x3", exact_running_stats=False, sync_bn=False,
-                 defer_wgrad=None, grad_reduce_bf16=None, group_heads=True, keep_logits=False, max_grad_norm=None):
+                 defer_wgrad=None, grad_reduce_bf16=None, group_heads=True, keep_logits=False, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=False):
         # --conditional (vae.py:231-237, 286-291): the condition joins the 512 features in front of the image encoders' heads
         # and the latent in front of the image decoders' first layer; the pose MLPs are built unconditional (vae.py:117-123)
         self.conditional = bool(getattr(model, "conditional", False))
@@ -373,6 +374,20 @@ class MVAEStep:
             dist.broadcast(self.params.flat, 0, group=process_group)
             for b in model.buffers():
                 dist.broadcast(b, 0, group=process_group)
+        # Exponential moving average of the parameters (None: off -- no buffer, optimizer_step is the calls it has always been).  A
+        # second flat fp32 buffer that starts as the parameters (after the broadcast above, so every rank starts from rank 0's) and
+        # that the Adam launch itself moves towards the parameters it writes (mmdyn_adam_step_ema: one more one-thread launch, the
+        # EMA tick, and two more streams through the same pass).  Count, decay and warm-up live in four doubles on the device and
+        # nothing reads the host, so the captured step keeps the average on every replay.  Every rank applies the same update to the
+        # same parameter bits: the averages agree without a collective.  Fixed per engine, so the capture key does not carry it.
+        self.ema_decay = None if ema_decay is None else ops.check_ema_decay(ema_decay, "ema_decay")
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = self.ema_flat = self.ema_state = self._ema_model = None      # ema: parameter name -> view of ema_flat
+        if self.ema_decay is not None:
+            self.ema_flat = self.params.flat.clone()
+            self.ema_state = ops.new_ema_state(self.ema_decay, self.ema_warmup, dev)
+            self.ema = {k: self.ema_flat[o:o + self.params.P[k].numel()].view(self.params.P[k].shape)
+                        for k, o in self.params.offsets.items()}
         self.last = {}
         self.last_rows = None            # a step with sample_weight: the unweighted per-sample tables of its batch (dict, see forward)
         self.lanes = _Lanes(dev, two_lanes)
@@ -1069,6 +1084,15 @@ class MVAEStep:
         for h in handles:
             h.wait()
         scale = self.loss_scale if loss_scale is None else loss_scale
+        if self.ema_flat is not None:
+            # the same steps with the average kept in the Adam pass (clip None: adam_step, else adam_step_clipped, same guard rule)
+            if self.max_grad_norm is not None:
+                ops.B.grad_sumsq(self.params.grad, self._sumsq_ws, self.clip)
+                ops.B.grad_clip_coef(self.clip, 1.0 / (self.world * scale), self.max_grad_norm)
+            ops.B.adam_step_ema(self.params.flat, self.params.grad, self.adam_m, self.adam_v, self.ema_flat, self.adam_state,
+                                self.clip, self.ema_state, self.lr, self.betas[0], self.betas[1], self.eps,
+                                1.0 / (self.world * scale), guarded=bool(self._scale_per_sample))
+            return
         if self.max_grad_norm is not None:
             # one read of the gradient serves the norm AND the overflow guard of the fp16 modes (a non-finite norm skips the step)
             ops.B.grad_sumsq(self.params.grad, self._sumsq_ws, self.clip)
@@ -1096,6 +1120,48 @@ class MVAEStep:
     def clipped_steps(self):
         """Optimiser steps whose gradient was scaled down to ``max_grad_norm`` so far.  Synchronises."""
         return 0 if self.clip is None else int(self.clip[3])
+
+    # ---- the averaged weights (ema_decay) ---------------------------------------------------------------------------------------
+    def _need_ema(self):
+        if self.ema_flat is None:
+            raise ValueError("this engine keeps no average of its parameters: build it with ema_decay")
+
+    @property
+    def ema_updates(self):
+        """Updates of the average so far: the optimiser steps that were not skipped (0 without ``ema_decay``).  Synchronises."""
+        return 0 if self.ema_state is None else int(self.ema_state[0])
+
+    def ema_params(self):
+        """Parameter name -> view of ``ema_flat``, named and shaped like ``model.named_parameters()``.  The views follow training."""
+        self._need_ema()
+        return {k: self.ema[k] for k, _ in self.model.named_parameters()}
+
+    def ema_state_dict(self):
+        """A ``state_dict`` with the model's keys: parameters from the average, buffers (the BatchNorm running estimates, which are
+        averages already, and ``num_batches_tracked``) from the live model -- torch.optim.swa_utils.AveragedModel(use_buffers=False).
+        The values are the live tensors, not copies."""
+        self._need_ema()
+        return type(self.model.state_dict())((k, self.ema.get(k, v)) for k, v in self.model.state_dict().items())
+
+    def ema_model(self):
+        """A module of the model's class in ``eval()`` mode whose parameters ARE the views of ``ema_flat`` and whose buffers ARE the
+        live model's buffer tensors: it follows training without a copy, so ``MVAEInference(step.ema_model())`` serves the average
+        and ``refresh()`` after further steps packs the newer one.  Built once; later calls return the same object."""
+        self._need_ema()
+        if self._ema_model is None:
+            import copy
+            twin = copy.deepcopy(self.model)
+            for k, p in twin.named_parameters():
+                p.requires_grad_(False)
+                p.grad = None
+                p.data = self.ema[k]
+            live = dict(self.model.named_buffers())
+            for name, mod in twin.named_modules():
+                for b in list(mod._buffers):
+                    if mod._buffers[b] is not None:
+                        mod._buffers[b] = live[(name + "." if name else "") + b]
+            self._ema_model = twin.eval()
+        return self._ema_model
 
     @_with_precision
     def train_step(self, inputs, targets, kl_weight, loss_mask=None, condition=None, sample_weight=None, kl="batch", available=None,

@@ -56,6 +56,10 @@ _BUILD_FLAGS = (
     ("grad-clip", 0.0, float, "clip every step's gradient by its global L2 norm (torch.nn.utils.clip_grad_norm_ arithmetic, on the "
                               "device, inside the replayed step) and log Grad_norm/train_epoch and Grad_clipped/train_epoch; "
                               "inf logs the norm without clipping; 0 = off"),
+    ("ema-decay", 0.0, float, "keep an exponential moving average of the parameters with this decay in [0, 1) (on the device, inside "
+                              "the replayed step) and write it into the best-validation checkpoint as 'model_ema' with "
+                              "'ema_updates'; training and validation stay on the live weights; 0 = off"),
+    ("ema-warmup", False, None, "with --ema-decay: update n uses the decay min(decay, (1 + n) / (10 + n))"),
 )
 
 
@@ -75,6 +79,8 @@ def main(argv=None):
     assert args.problem_type in config.PROBLEM_TYPES, "Invalid problem type."
     if not args.grad_clip >= 0:                      # (a negative value, or NaN)
         parser.error(f"--grad-clip must be a norm > 0, inf, or 0 for off (got {args.grad_clip})")
+    if not 0 <= args.ema_decay < 1:                  # (also NaN)
+        parser.error(f"--ema-decay must be a decay in (0, 1), or 0 for off (got {args.ema_decay})")
     L = args.synthetic_seq_length
     shock = 3 if args.conditional else 0
     if args.synthetic_batches > 0:

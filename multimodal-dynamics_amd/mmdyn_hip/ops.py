@@ -79,6 +79,31 @@ def check_max_norm(value, what):
     return float(value)
 
 
+def check_ema_decay(value, what):
+    """``value`` as a float if it is a real number in [0, 1), else a ValueError naming ``what``."""
+    if not (isinstance(value, numbers.Real) and not isinstance(value, bool) and 0.0 <= float(value) < 1.0):
+        raise ValueError(f"{what} must be a real number in [0, 1), got {value!r}")
+    return float(value)
+
+
+def new_ema_state(decay, warmup, device):
+    """The EMA state of include/mmdyn_hip.h on ``device``: fp64 {updates done = 0, decay, 1 - d_n = 0, warm-up flag}."""
+    decay = check_ema_decay(decay, "ema_decay")
+    return torch.tensor([0.0, decay, 0.0, 1.0 if warmup else 0.0], dtype=torch.float64).to(device)
+
+
+def _check_ema(ema, p, ema_state, name):
+    if not torch.is_tensor(ema_state) or ema_state.dtype != torch.float64 or ema_state.numel() != 4 or not ema_state.is_contiguous():
+        raise ValueError(f"mmdyn_{name}: ema_state must be four contiguous fp64 values {{updates, decay, 1 - d_n, warm-up flag}}")
+    if ema is None:
+        return
+    if not torch.is_tensor(ema) or not torch.is_tensor(p) or ema.numel() != p.numel():
+        raise ValueError(f"mmdyn_{name}: ema must hold as many elements as p")
+    n = p.numel() * p.element_size()
+    if ema.device == p.device and ema.data_ptr() < p.data_ptr() + n and p.data_ptr() < ema.data_ptr() + n:
+        raise ValueError(f"mmdyn_{name}: ema must not alias p")
+
+
 class Planes:
     """An fp32 matrix [rows][C] kept as its exact three-term bf16 split, the operand format of the fp32x3 GEMMs that take their
     operands ALREADY SPLIT (include/mmdyn_hip.h, flag bits 7 + 8): ``t[row][plane][c]`` (torch.bfloat16), plane 0 = hi = bf16(x),
@@ -1707,6 +1732,34 @@ class HipBackend:
         _check_clip(clip, "sgd_step_clipped")
         check(self.lib.mmdyn_sgd_step_clipped(_ptr(p), _ptr(g), _ptr(buf), _ptr(clip, torch.float64), p.numel(), lr, momentum,
                                               weight_decay, grad_scale, int(first), _stream()), "mmdyn_sgd_step_clipped")
+
+    # ---- EMA of the parameters: ema_state = fp64 [4] on the device {updates done, decay, 1 - d_n, warm-up flag} (new_ema_state) ----
+    def ema_tick(self, ema_state, adam_state=None):
+        """One update of the EMA state: ema_state[2] = 1 - d_n, ema_state[0] += 1.  ``adam_state``: the six-double state of a guarded
+        Adam step that has run; when it skipped, the tick changes nothing."""
+        _check_ema(None, None, ema_state, "ema_tick")
+        if adam_state is not None and adam_state.numel() < 6:
+            raise ValueError("mmdyn_hip: the guarded Adam step keeps six doubles of state")
+        check(self.lib.mmdyn_ema_tick(_ptr(ema_state, torch.float64), _ptr(adam_state, torch.float64), _stream()), "mmdyn_ema_tick")
+
+    def ema_update(self, ema, p, ema_state):
+        """ema = fmaf(float32(ema_state[2]), p - ema, ema) per element.  fp32, 4-byte aligned views are fine."""
+        _check_ema(ema, p, ema_state, "ema_update")
+        check(self.lib.mmdyn_ema_update(_ptr(ema), _ptr(p), _ptr(ema_state, torch.float64), p.numel(), _stream()), "mmdyn_ema_update")
+
+    def adam_step_ema(self, p, g, m, v, ema, state, clip, ema_state, lr, beta1, beta2, eps, grad_scale, guarded=False):
+        """``adam_step`` (``clip`` None) or ``adam_step_clipped`` that also moves ``ema`` towards the new parameters in the same pass:
+        the bits of that step followed by ``ema_tick`` + ``ema_update``.  A step the guard skips leaves ``ema`` and ``ema_state``
+        untouched."""
+        _check_ema(ema, p, ema_state, "adam_step_ema")
+        if clip is not None:
+            _check_clip(clip, "adam_step_ema")
+        if state.numel() < (6 if guarded else 3):
+            raise ValueError("mmdyn_hip: the guarded Adam step keeps six doubles of state" if guarded else
+                             "mmdyn_hip: the Adam step keeps three doubles of state")
+        check(self.lib.mmdyn_adam_step_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), _ptr(state, torch.float64),
+                                           _ptr(clip, torch.float64), _ptr(ema_state, torch.float64), p.numel(), lr, beta1, beta2,
+                                           eps, grad_scale, int(bool(guarded)), _stream()), "mmdyn_adam_step_ema")
 
 
     # ---- image decode (uint8 HWC frames in HBM -> float32 CHW) ----

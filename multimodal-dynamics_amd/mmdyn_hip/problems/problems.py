@@ -72,17 +72,72 @@ class _GlobalNormClip:
         return 0 if self._clip is None else int(self._clip[3])
 
 
-class FusedAdam(_GlobalNormClip, torch.optim.Optimizer):
+class _ParamEma:
+    """``ema_decay`` of the fused optimisers: an exponential moving average of every parameter tensor, kept on the device.  After
+    the step's per-tensor launches: one ``ema_tick``, then one ``ema_update`` per tensor (a tensor without a gradient is averaged
+    too, as torch.optim.swa_utils.AveragedModel does).  The averages start as the parameters at construction.  ``None`` (default):
+    off, no launch, no buffer.  ``ema_names``: the parameters' names in order, the keys of :meth:`ema_params` (default "0", "1",
+    ...).  ``ema_shared``: an :class:`mmdyn_hip.engine.MVAEStep` built with ``ema_decay`` over the same parameters -- the optimiser
+    then updates THAT engine's average and count (one average per model whichever path a batch takes) and keeps none of its own."""
+
+    def _init_ema(self, ema_decay, ema_warmup, ema_names, ema_shared):
+        plist = [p for group in self.param_groups for p in group["params"]]
+        names = [str(i) for i in range(len(plist))] if ema_names is None else list(ema_names)
+        if len(names) != len(plist):
+            raise ValueError(f"ema_names holds {len(names)} names for {len(plist)} parameter tensors")
+        self._ema, self._ema_state = None, None
+        if ema_shared is not None:
+            if getattr(ema_shared, "ema", None) is None:
+                raise ValueError("ema_shared must be an engine built with ema_decay")
+            missing = [k for k in names if k not in ema_shared.ema]
+            if missing:
+                raise ValueError(f"ema_shared keeps no average of {missing[:3]}: pass the model's parameter names as ema_names")
+            self.ema_decay, self.ema_warmup = ema_shared.ema_decay, ema_shared.ema_warmup
+            self._ema = [(k, p, ema_shared.ema[k]) for k, p in zip(names, plist)]
+            self._ema_state = ema_shared.ema_state
+            return
+        self.ema_decay = None if ema_decay is None else ops.check_ema_decay(ema_decay, "ema_decay")
+        self.ema_warmup = bool(ema_warmup)
+        if self.ema_decay is not None and plist:
+            self._ema = [(k, p, p.detach().clone()) for k, p in zip(names, plist)]
+            self._ema_state = ops.new_ema_state(self.ema_decay, self.ema_warmup, plist[0].device)
+
+    def _ema_step(self):
+        if self._ema is None:
+            return
+        ops.B.ema_tick(self._ema_state)
+        for _, p, e in self._ema:
+            ops.B.ema_update(e.view(-1), p.data.view(-1), self._ema_state)
+
+    def ema_params(self):
+        """Parameter name -> its average (live tensors: they follow the steps)."""
+        if self._ema is None:
+            raise ValueError("this optimiser keeps no average of its parameters: build it with ema_decay")
+        return {k: e for k, _, e in self._ema}
+
+    @property
+    def ema_updates(self):
+        """Updates of the average so far (0 without ``ema_decay``).  Synchronises."""
+        return 0 if self._ema_state is None else int(self._ema_state[0])
+
+
+class FusedAdam(_GlobalNormClip, _ParamEma, torch.optim.Optimizer):
     """torch.optim.Adam(lr) semantics (betas (0.9, 0.999), eps 1e-8, no weight decay) on the mmdyn_adam_step
     kernel, one launch per parameter tensor.  Used by the un-fused (reference-schedule) mode.  ``max_norm``: see
-    :class:`_GlobalNormClip` (mmdyn_adam_step_clipped)."""
+    :class:`_GlobalNormClip` (mmdyn_adam_step_clipped).  ``ema_decay`` / ``ema_warmup``: see :class:`_ParamEma`."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=None, ema_decay=None, ema_warmup=False,
+                 ema_names=None, ema_shared=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._init_clip(max_norm)
+        self._init_ema(ema_decay, ema_warmup, ema_names, ema_shared)
 
     @torch.no_grad()
     def step(self):
+        self._adam_launches()
+        self._ema_step()
+
+    def _adam_launches(self):
         if self.max_norm is not None:
             self._measure()
         for group in self.param_groups:
@@ -102,17 +157,23 @@ class FusedAdam(_GlobalNormClip, torch.optim.Optimizer):
                                 st["state"], group["lr"], b1, b2, group["eps"], 1.0)
 
 
-class FusedSGD(_GlobalNormClip, torch.optim.Optimizer):
+class FusedSGD(_GlobalNormClip, _ParamEma, torch.optim.Optimizer):
     """torch.optim.SGD(lr, momentum=0.9, weight_decay=5e-4) -- the reference's SGD option (problems.py:132-136) -- on
     the mmdyn_sgd_step kernel.  ``max_norm``: see :class:`_GlobalNormClip` (mmdyn_sgd_step_clipped; the weight decay is added
-    after the clipping, as in torch)."""
+    after the clipping, as in torch).  ``ema_decay`` / ``ema_warmup``: see :class:`_ParamEma`."""
 
-    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=5e-4, max_norm=None):
+    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=5e-4, max_norm=None, ema_decay=None, ema_warmup=False,
+                 ema_names=None, ema_shared=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
         self._init_clip(max_norm)
+        self._init_ema(ema_decay, ema_warmup, ema_names, ema_shared)
 
     @torch.no_grad()
     def step(self):
+        self._sgd_launches()
+        self._ema_step()
+
+    def _sgd_launches(self):
         if self.max_norm is not None:
             self._measure()
         for group in self.param_groups:
@@ -236,9 +297,17 @@ class Problem:
         if clip is not None:
             clip = ops.check_max_norm(clip, "--grad-clip")
         self._grad_clip = clip
+        # --ema-decay (this build): an exponential moving average of the parameters, kept on the device by the step itself and
+        # written into the checkpoint as 'model_ema'; 0 (default) = off.  Training and validation compute on the live weights.
+        ema = self.parameters.get('ema_decay') or None
+        if ema is not None:
+            ema = ops.check_ema_decay(ema, "--ema-decay")
+        self._ema_decay = ema
+        names = [k for k, _ in self._model.named_parameters()]
+        ema_kw = dict(ema_decay=ema, ema_warmup=bool(self.parameters.get('ema_warmup')), ema_names=names)
         if self.parameters['optimizer'] == 'SGD':      # reference: momentum 0.9, weight decay 5e-4 (problems.py:132-136)
             self._optimizer = FusedSGD(self._model.parameters(), lr=self.parameters['lr'], momentum=0.9, weight_decay=5e-4,
-                                       max_norm=clip)
+                                       max_norm=clip, **ema_kw)
             return
         # the fused step takes the dict-shaped inputs of seq / dyn modeling (with the loss mask of --mask-loss when the model has
         # no pose term, and the shock condition of --conditional); everything else (plain reconstruction, cnn-vae, regressor,
@@ -254,12 +323,30 @@ class Problem:
         if use_engine:
             self._step = MVAEStep(self._model, lr=self.parameters['lr'], pose_multiplier=self._pose_multiplier,
                                   precision=precision, exact_running_stats=bool(self.parameters.get('exact_running_stats')),
-                                  max_grad_norm=clip)
+                                  max_grad_norm=clip, ema_decay=ema, ema_warmup=ema_kw['ema_warmup'])
         elif precision not in ('fp32', 'fp32x3'):
             raise ValueError("--precision %s is a mode of the fused cnn-mvae step; this configuration runs the module "
                              "path, which computes in fp32" % precision)
-        # the module path's optimiser: also what a batch the fused step does not take falls back to
-        self._optimizer = FusedAdam(self._model.parameters(), lr=self.parameters['lr'], max_norm=clip)
+        # the module path's optimiser: also what a batch the fused step does not take falls back to -- with an engine it then moves
+        # the engine's average with the engine's count: one average per model, whichever path a batch takes
+        if self._step is not None and ema is not None:
+            ema_kw['ema_shared'] = self._step
+        self._optimizer = FusedAdam(self._model.parameters(), lr=self.parameters['lr'], max_norm=clip, **ema_kw)
+
+    def ema_state_dict(self):
+        """The averaged weights as a ``state_dict`` with the model's keys (--ema-decay; None when it is off): parameters from the
+        average, buffers from the live model.  The engine's average when there is an engine, the optimiser's otherwise."""
+        if getattr(self, '_ema_decay', None) is None:
+            return None
+        if self._step is not None:
+            return self._step.ema_state_dict()
+        avg = self._optimizer.ema_params()
+        return type(self._model.state_dict())((k, avg.get(k, v)) for k, v in self._model.state_dict().items())
+
+    @property
+    def ema_updates(self):
+        """Updates of the average so far, on whichever path the batches went.  Synchronises."""
+        return self._step.ema_updates if self._step is not None else self._optimizer.ema_updates
 
     def _anneal_KL(self, epoch):
         if epoch < self.parameters['annealing_epochs']:
@@ -381,6 +468,11 @@ class Problem:
             self._logger_dict['Perf_measure_validation/' + k].append(v / max(n, 1))
         if val_loss < self._best_loss:      # best-validation checkpoint, same dict keys as problems.py:580-586
             state = {'model': self._model.state_dict(), 'loss': val_loss, 'epoch': epoch}
+            if getattr(self, '_ema_decay', None) is not None:
+                # --ema-decay: the averaged weights beside the live ones (copied to the host: the views go on following training)
+                state['model_ema'] = type(state['model'])((k, v.detach().to('cpu', copy=True))
+                                                          for k, v in self.ema_state_dict().items())
+                state['ema_updates'] = self.ema_updates
             torch.save(state, self._checkpoint_dir + '/epoch_' + str(epoch) + '.ckpt')
             if self._step is not None:
                 # the checkpoint keeps the reference's three keys (problems.py:751-757); how the image decoders' BatchNorm
