@@ -1027,6 +1027,24 @@ int mmdyn_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema
                         double* ema_state, int64_t n, float lr, float beta1, float beta2, float eps, float grad_scale,
                         int guarded, void* stream);
 
+/* ---- image grids of the epoch log (problems.py:580-604: torch.sigmoid, v[0][:n] / v[1][:n], torch.cat, ------------
+ * torchvision.utils.make_grid(img, nrow) and the writer's float32 * 255 -> clip -> uint8) as ONE launch.
+ * src0, src1 (nullable): contiguous fp32 [n_i][C][H][W], C in {1, 3}.  The image list is the first min(n0, take) images of src0
+ * followed by the first min(n1, take) of src1 (torch.cat((v[0][:take], v[1][:take])); src1 null with n1 == 0 is the single-tensor
+ * branch); N its length.  Layout = make_grid(img, nrow, padding, pad_value=0): xmaps = min(nrow, N), ymaps = ceil(N / xmaps),
+ * Hg = ymaps * (H + padding) + padding, Wg = xmaps * (W + padding) + padding, image k at row (k / xmaps) * (H + padding) + padding
+ * and column (k % xmaps) * (W + padding) + padding, every other pixel 0 (also the cells of a partly filled last row); C == 1 is
+ * replicated to three channels; N == 1 is the image alone, Hg = H, Wg = W.
+ * out: uint8 [Hg][Wg][3] (HWC, a PNG's scanlines), exactly Hg * Wg * 3 bytes: every byte of it is written (no memset in front), no
+ * byte outside it is touched.  Value: v = logits ? 1 / (1 + exp(-x)) : x, t = v * 255.0f in fp32,
+ * byte = t >= 255 ? 255 : (t > 0 ? (uint8)t : 0) -- truncation; NaN gives 0.  `logits` applies to both sources.
+ * Added without touching an existing signature: the revision stays 6.
+ * Checked on the host, before any launch: src0 or out null: MMDYN_ERR_NULL; src1 non-null with n1 <= 0, or null with n1 != 0; C not
+ * 1 or 3; H, W, take, nrow or n0 below 1; padding < 0; a pointer not 4-byte aligned: MMDYN_ERR_SHAPE; Hg * Wg * 3 or a source's
+ * element count >= 2^31: MMDYN_ERR_RANGE. */
+int mmdyn_image_grid_u8(const float* src0, const float* src1, uint8_t* out, int n0, int n1, int take, int C, int H, int W,
+                        int nrow, int padding, int logits, void* stream);
+
 /* ---- image decode in front of the path --------------------------------------------------------
  * transforms.Resize(input_size) + transforms.ToTensor() of datasets.py:23-31 / 375-385 on frames kept as uint8
  * HWC in HBM: Pillow's 8-bit anti-aliased bilinear resampler (libImaging/Resample.c: 22-bit fixed-point taps,

@@ -134,6 +134,7 @@ _SIGNATURES = {
     "mmdyn_ema_tick": "pp" + "p",
     "mmdyn_ema_update": "ppp" + "l" + "p",
     "mmdyn_adam_step_ema": "pppppppp" + "l" + "fffff" + "i" + "p",
+    "mmdyn_image_grid_u8": "ppp" + "iiiiiiiii" + "p",
     "mmdyn_igemm_nt_mx": "pppppppppppp" + "iiiiiiiiiiiiii" + "i" + "pp",
     "mmdyn_wgrad_tn_mx": "ppp" + "iiiiiiiiiii" + "i" + "p",
     "mmdyn_split_planes": "pp" + "l" + "i" + "p",

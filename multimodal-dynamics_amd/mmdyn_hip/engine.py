@@ -1234,6 +1234,7 @@ class MVAEStep:
             if mark is not None:
                 mark()
             warm_rows = self.last_rows if (sample_weight is not None or avail is not None) else None
+            warm_last = self.last
             try:
                 captured = self._capture(kl_weight)
             except BaseException:
@@ -1254,6 +1255,13 @@ class MVAEStep:
                 for k, t in self.last_rows.items():
                     if torch.is_tensor(t):
                         t.copy_(warm_rows[k])
+            # ... and so does `last` (recon_x, means, log_var, the logits): this call's outputs are the warm-up step's.  Copied, like the
+            # rows, so that `last` holds this step's values AND keeps naming the buffers the replays write (once per capture)
+            for k, t in self.last.items():
+                many = isinstance(t, (list, tuple))
+                for dst, src in zip(t if many else (t,), warm_last[k] if many else (warm_last[k],)):
+                    if torch.is_tensor(dst):
+                        dst.copy_(src)
             return self.loss             # the warm-up above WAS this call's optimiser step
         # the batch moves into the captured step's static buffers with ONE launch (six runtime copies before round 6)
         moves = list(zip(self._static_in + self._static_tg, list(inputs) + list(targets)))

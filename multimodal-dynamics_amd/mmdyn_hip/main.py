@@ -29,7 +29,7 @@ _REFERENCE_FLAGS = (
     ("optimizer", "Adam", str, " | ".join(config.OPTIMIZERS)),
     ("num-epochs", 100, int, "training epochs"),
     ("mask-loss", False, None, "restrict the reconstruction loss to the object segment"),
-    ("vis-pose", False, None, "accepted for compatibility (no plotting in this build)"),
+    ("vis-pose", False, None, "accepted for compatibility (no pose figures in this build; --log-images writes the image grids)"),
     ("pose-multiplier", 1000, float, "weight of the pose MSE inside the ELBO"),
     ("save-name", "run", str, "name of the log directory"),
     ("no-cuda", False, None, "rejected with an error: this build has no CPU path"),
@@ -60,6 +60,13 @@ _BUILD_FLAGS = (
                               "the replayed step) and write it into the best-validation checkpoint as 'model_ema' with "
                               "'ema_updates'; training and validation stay on the live weights; 0 = off"),
     ("ema-warmup", False, None, "with --ema-decay: update n uses the decay min(decay, (1 + n) / (10 + n))"),
+    ("log-images", 0, int, "every K-th epoch (epoch %% K == 0) and on the last one, write the reference's image log as PNG files under "
+                           "<log dir>/plot/: inputs, reconstructions and targets of the epoch's last training and validation "
+                           "batch and 50 decoded draws from the prior, each as one grid built on the device (one launch per "
+                           "grid).  The draws come from the model's noise source on every logged epoch (the reference draws "
+                           "them from torch's generator on every epoch), so the noise of later epochs differs from a run with "
+                           "the flag off, and -- the model being in train mode, as in the reference -- decoding them also "
+                           "moves the decoders' BatchNorm running statistics once per logged epoch; 0 = off"),
 )
 
 
@@ -81,6 +88,8 @@ def main(argv=None):
         parser.error(f"--grad-clip must be a norm > 0, inf, or 0 for off (got {args.grad_clip})")
     if not 0 <= args.ema_decay < 1:                  # (also NaN)
         parser.error(f"--ema-decay must be a decay in (0, 1), or 0 for off (got {args.ema_decay})")
+    if args.log_images < 0:
+        parser.error(f"--log-images must be a number of epochs >= 1, or 0 for off (got {args.log_images})")
     L = args.synthetic_seq_length
     shock = 3 if args.conditional else 0
     if args.synthetic_batches > 0:

@@ -104,6 +104,44 @@ def _check_ema(ema, p, ema_state, name):
         raise ValueError(f"mmdyn_{name}: ema must not alias p")
 
 
+def grid_shape(N, H, W, nrow, padding=2):
+    """(Hg, Wg) of ``torchvision.utils.make_grid`` on N images of H x W: xmaps = min(nrow, N) tiles per row, ceil(N / xmaps) rows,
+    ``padding`` pixels around every tile; a single image comes back alone.  Host arithmetic of mmdyn_image_grid_u8."""
+    N, H, W, nrow, padding = int(N), int(H), int(W), int(nrow), int(padding)
+    if N < 1 or H < 1 or W < 1 or nrow < 1 or padding < 0:
+        raise ValueError(f"grid_shape: N, H, W, nrow >= 1 and padding >= 0, got {(N, H, W, nrow, padding)}")
+    if N == 1:
+        return H, W
+    xmaps = min(nrow, N)
+    ymaps = -(-N // xmaps)
+    return ymaps * (H + padding) + padding, xmaps * (W + padding) + padding
+
+
+def check_grid_sources(srcs, take, nrow, padding):
+    """The one or two sources of ``image_grid`` as a list, after the checks that need no device: fp32, contiguous, 4-D, C in {1, 3},
+    one C / H / W, one device; ``take`` / ``nrow`` >= 1, ``padding`` >= 0.  A ValueError names what is wrong."""
+    srcs = [srcs] if torch.is_tensor(srcs) else srcs
+    if not isinstance(srcs, (list, tuple)) or not 1 <= len(srcs) <= 2 or not all(torch.is_tensor(s) for s in srcs):
+        raise ValueError("mmdyn_image_grid_u8: srcs is a tensor, or a list / tuple of one or two tensors")
+    for s in srcs:
+        if s.dtype != torch.float32 or s.dim() != 4 or not s.is_contiguous() or s.shape[0] < 1 or s.shape[1] not in (1, 3):
+            raise ValueError(f"mmdyn_image_grid_u8: a source is contiguous fp32 [n >= 1][C in (1, 3)][H][W], got {s.dtype} "
+                             f"{tuple(s.shape)}{'' if s.is_contiguous() else ' (not contiguous)'}")
+        if s.shape[1:] != srcs[0].shape[1:] or s.device != srcs[0].device:
+            raise ValueError(f"mmdyn_image_grid_u8: the sources differ in C / H / W or device: {tuple(srcs[0].shape)} on "
+                             f"{srcs[0].device}, {tuple(s.shape)} on {s.device}")
+    for what, v, low in (("take", take, 1), ("nrow", nrow, 1), ("padding", padding, 0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < low:
+            raise ValueError(f"mmdyn_image_grid_u8: {what} must be an integer >= {low}, got {v!r}")
+    return list(srcs)
+
+
+def check_grid_out(out, shape, device):
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() \
+            or out.device != device:
+        raise ValueError(f"mmdyn_image_grid_u8: out must be a contiguous uint8 tensor {shape} on {device}")
+
+
 class Planes:
     """An fp32 matrix [rows][C] kept as its exact three-term bf16 split, the operand format of the fp32x3 GEMMs that take their
     operands ALREADY SPLIT (include/mmdyn_hip.h, flag bits 7 + 8): ``t[row][plane][c]`` (torch.bfloat16), plane 0 = hi = bf16(x),
@@ -1760,6 +1798,25 @@ class HipBackend:
         check(self.lib.mmdyn_adam_step_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), _ptr(state, torch.float64),
                                            _ptr(clip, torch.float64), _ptr(ema_state, torch.float64), p.numel(), lr, beta1, beta2,
                                            eps, grad_scale, int(bool(guarded)), _stream()), "mmdyn_adam_step_ema")
+
+    # ---- image grids of the epoch log (problems.py:588-603: slices, cat, make_grid and the writer's uint8 conversion) ----
+    def image_grid(self, srcs, take, nrow, logits, padding=2, out=None):
+        """The uint8 [Hg, Wg, 3] grid (HWC: a PNG's scanlines) of the first ``take`` images of each source -- ``srcs``: one fp32
+        [n, C, H, W] tensor, or a list / tuple of one or two of one C / H / W --, ``nrow`` tiles per row, laid out as
+        ``torchvision.utils.make_grid(..., nrow, padding)``; ``logits``: the sources are decoder logits and go through the sigmoid.
+        One launch on the current stream; ``out`` is allocated on the sources' device when None."""
+        srcs = check_grid_sources(srcs, take, nrow, padding)
+        n = [int(s.shape[0]) for s in srcs]
+        C, H, W = (int(d) for d in srcs[0].shape[1:])
+        shape = grid_shape(sum(min(k, take) for k in n), H, W, nrow, padding) + (3,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=srcs[0].device)
+        else:
+            check_grid_out(out, shape, srcs[0].device)
+        check(self.lib.mmdyn_image_grid_u8(_ptr(srcs[0]), _ptr(srcs[1]) if len(srcs) > 1 else None, _ptr(out, torch.uint8), n[0],
+                                           n[1] if len(srcs) > 1 else 0, int(take), C, H, W, int(nrow), int(padding),
+                                           int(bool(logits)), _stream()), "mmdyn_image_grid_u8")
+        return out
 
 
     # ---- image decode (uint8 HWC frames in HBM -> float32 CHW) ----

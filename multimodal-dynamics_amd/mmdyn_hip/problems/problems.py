@@ -7,9 +7,9 @@ Mirrors the parts of /root/reference/mmdyn/pytorch/problems/problems.py that dri
 :473-546, each with the per-sample ``reduce=False`` branch, best-validation checkpoint :580-586), ``SeqModeling`` (``parse_input`` :634-673,
 ``_evaluate_model`` :683-716) and ``DynModeling.parse_input`` (:765-803).
 
-Out of scope here: the PNG/json dataset reader, TensorBoard image/figure logging,
-``Regression``.  Batches come from ``SyntheticVisuoTactile`` (random 64x64 visual + tactile + 7-DoF pose,
-the BASELINE.json workload) or from any iterable yielding the reference's ``(data_input, data_target)``
+Out of scope here: the PNG/json dataset reader, TensorBoard event files and pose figures (the image grids
+of ``_write_images`` :588-603 are written as PNG files: ``--log-images``), ``Regression``.  Batches come from
+``SyntheticVisuoTactile`` (random 64x64 visual + tactile + 7-DoF pose, the BASELINE.json workload) or from any iterable yielding the reference's ``(data_input, data_target)``
 lists.
 
 Two execution modes for cnn-mvae training:
@@ -19,9 +19,12 @@ Two execution modes for cnn-mvae training:
     the decoder passes whose output is discarded).
 """
 import json
+import math
 import os
 import pickle
+import struct
 import time
+import zlib
 from collections import defaultdict
 from contextlib import contextmanager
 from datetime import datetime
@@ -224,6 +227,19 @@ class SyntheticVisuoTactile:
             yield [x.to(self.device) for x in d], [x.to(self.device) for x in t]
 
 
+def _png_chunk(tag, data):
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def _write_png(path, grid):
+    """``grid``: uint8 CPU tensor [H][W][3] -> an 8-bit RGB PNG, non-interlaced, filter type 0 on every scanline."""
+    H, W = int(grid.shape[0]), int(grid.shape[1])
+    lines = torch.cat((torch.zeros(H, 1, dtype=torch.uint8), grid.reshape(H, W * 3)), 1)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) +
+                _png_chunk(b"IDAT", zlib.compress(lines.numpy().tobytes(), 6)) + _png_chunk(b"IEND", b""))
+
+
 class Problem:
     def __init__(self, problem_args, log_dir=None, load_dataset=None, train_loader=None, test_loader=None,
                  seq_length=1, fused=True):
@@ -233,6 +249,14 @@ class Problem:
         self._best_loss = float("inf")
         self._logger_dict = defaultdict(list)
         self.parameters = vars(problem_args) if not isinstance(problem_args, dict) else dict(problem_args)
+        # --log-images K (this build): the reference's per-epoch image log (problems.py:196-206) as PNG files under plot/, on every
+        # epoch with epoch % K == 0 and on the last one; 0 (default) = off: no _sample call, no plot/ directory
+        k = self.parameters.get('log_images') or 0
+        if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+            raise ValueError(f"--log-images must be an integer >= 0 (0 for off), got {k!r}")
+        self._log_images, self._logging_images = k, False
+        self._img_logger_dict = {}       # key -> (a tensor or a pair of tensors, they are logits): the last batch's, by reference
+        self._image_grids, self._grid_host = {}, {}
         self._cross_modal = self.parameters['input_type'] == 'visuotactile'
         self._kl_weight = self.parameters['kl_weight']
         self._pose_multiplier = self.parameters['pose_multiplier']
@@ -276,6 +300,7 @@ class Problem:
     def load_dir(self, log_dir):
         self._log_dir = log_dir
         self._checkpoint_dir = self._log_dir + '/checkpoint/'
+        self._plot_dir = self._log_dir + '/plot/'            # (created by the first logged epoch of --log-images)
         for d in (self._log_dir, self._checkpoint_dir):
             Path(d).mkdir(parents=True, exist_ok=True)
 
@@ -371,8 +396,11 @@ class Problem:
             n_batches = len(self.train_loader)
         except TypeError:
             n_batches = -1
+        last = None                      # --log-images: the last batch as parsed, with the module path's outputs
         for batch_idx, (data_input, data_target) in enumerate(self.train_loader):
             inputs, targets = self.parse_input(data_input, data_target)
+            if self._logging_images:
+                last = [inputs, targets, None]
             if self._step is not None and self._fused_applicable(inputs):
                 # on the GPU the step is replayed from HIP graphs (captured once per batch shape; the annealed KL weight
                 # is read from device memory); the emulation has no graphs
@@ -416,6 +444,8 @@ class Problem:
                 outputs, loss = self._evaluate_model(inputs, targets)
                 loss.backward()
                 self._optimizer.step()
+                if last is not None:
+                    last[2] = outputs
             train_loss += float(loss.detach()) if torch.is_tensor(loss) else float(loss)
             if clipping:
                 gnorm_sum += self._optimizer.grad_norm or 0.0
@@ -441,15 +471,20 @@ class Problem:
             self._logger_dict['Grad_clipped/train_epoch'].append(self._clipped_seen - clipped_before)
         for k, v in perf.items():
             self._logger_dict['Perf_measure_train/' + k].append(v / max(n, 1))
+        if last is not None:
+            self._log_batch_images('train', *last)
         return dict(perf)
 
     def _test_epoch(self, epoch):
         self._model.train()          # sic: the reference validates in train mode (problems.py:174)
         val_loss, n = 0.0, 0
         perf = defaultdict(float)
+        last = None
         with torch.no_grad():
             for batch_idx, (data_input, data_target) in enumerate(self.test_loader):
                 inputs, targets = self.parse_input(data_input, data_target)
+                if self._logging_images:
+                    last = [inputs, targets, None]
                 if self._step is not None and self._fused_applicable(inputs):
                     avail_kw = self._avail_kw(inputs)
                     loss = self._step.eval_step(*self._fused_io(inputs, targets), self._kl_weight,
@@ -459,6 +494,8 @@ class Problem:
                     outputs = {'perf_measure': self._fused_perf_present() if avail_kw else self._fused_perf()}
                 else:
                     outputs, loss = self._evaluate_model(inputs, targets)
+                    if last is not None:
+                        last[2] = outputs
                 val_loss += float(loss)
                 n += 1
                 for k, v in outputs.get('perf_measure', {}).items():
@@ -466,6 +503,8 @@ class Problem:
         self._logger_dict['Loss/validation_epoch'].append(val_loss / max(n, 1))
         for k, v in perf.items():
             self._logger_dict['Perf_measure_validation/' + k].append(v / max(n, 1))
+        if last is not None:
+            self._log_batch_images('validation', *last)
         if val_loss < self._best_loss:      # best-validation checkpoint, same dict keys as problems.py:580-586
             state = {'model': self._model.state_dict(), 'loss': val_loss, 'epoch': epoch}
             if getattr(self, '_ema_decay', None) is not None:
@@ -489,9 +528,18 @@ class Problem:
         for epoch in range(self.parameters['num_epochs']):
             t0 = time.time()
             self._anneal_KL(epoch)
+            k = self._log_images
+            self._logging_images = k > 0 and (epoch % k == 0 or epoch == self.parameters['num_epochs'] - 1)
             self._train_epoch(epoch)
             if self.test_loader is not None:
                 perf = self._test_epoch(epoch)
+            if self._logging_images:
+                # the reference's order (problems.py:199-206): decoded draws from the prior, then every kept tensor as a grid
+                sample = self._sample(n=50)
+                if sample is not None:
+                    self._img_logger_dict['Samples/latent_space'] = (sample, True)
+                self._write_images(epoch)
+                self._logging_images = False
             row = {k: v[-1] for k, v in self._logger_dict.items() if v}
             row.update(epoch=epoch, seconds=time.time() - t0)
             with open(os.path.join(self._log_dir, 'scalars.jsonl'), 'a') as f:
@@ -512,6 +560,72 @@ class Problem:
         with torch.no_grad():
             _, rows = self._evaluate_model(inputs, targets, reduce=False)
         return rows
+
+    # ---- --log-images: the per-epoch image log (problems.py:196-206, 561-604, 718-739) ------------------------------------------
+    def _log_batch_images(self, split, inputs, targets, outputs):
+        """Keep the tensors of an epoch's last batch under the reference's keys (overridden per problem; by reference: the grids
+        are launched by this epoch's :meth:`_write_images`, before any step that could write the engine's buffers again -- the
+        validation steps are eager and write buffers of their own; after a capturing call of the replayed step the engine's
+        ``last`` holds that call's values in the buffers the replays write).
+        ``outputs``: what the module path returned, None for a batch the fused step took."""
+
+    def _recon_images(self, outputs):
+        """The image logits of a batch: ``outputs['recon_x']`` of the module path, the fused step's otherwise; a cross-modal model
+        gives (visual, tactile) -- the pose is left out."""
+        recon = outputs['recon_x'] if outputs is not None else self._step.last['recon_x']
+        return tuple(recon[:2]) if isinstance(recon, (list, tuple)) else recon
+
+    def _grid_source(self, key, t):
+        """One tensor of the image log as the kernel takes it: contiguous fp32 [n][C][H][W]."""
+        t = t.detach()
+        if self.parameters['model_name'] == 'mlp-vae':        # problems.py:595-596
+            s = int(self.parameters.get('image_size', 64))
+            # a batch row group of the MLP is the three channel rows of one frame, so batches take the reference's view; a prior
+            # draw is ONE row of s * s values (the reference's view raises on the 50 of them, and would mix three draws into one
+            # RGB image where it fits): the draws go out as one-channel images, whatever their number
+            t = t.reshape(-1, 1 if key.startswith('Samples') else 3, s, s)
+        # the inputs and targets are the loader's fp32 frames, and the image logits are fp32 in every storage mode of the fused step
+        # (the 16-bit modes store the activations BETWEEN the layers in 16 bits: include/mmdyn_hip.h), so nothing is cast here
+        if t.dtype != torch.float32:
+            raise TypeError(f"--log-images: the image tensor {key} is {t.dtype}; the grid kernel takes fp32")
+        return t.contiguous()            # (a [::seq_length] view of the loader's frames is gathered here)
+
+    def _write_images(self, epoch, n_images=120):
+        """One ``image_grid`` launch per kept key, the grids copied into reused (pinned) host buffers behind ONE synchronisation,
+        then written to ``plot/<key with '/' as '_'>_epoch_<epoch>.png``.  ``nrow`` and the number of images taken per tensor
+        follow problems.py:589-593."""
+        kept, self._img_logger_dict = self._img_logger_dict, {}
+        if not kept:
+            return
+        path = str(self.parameters.get('dataset_path') or '')
+        l, bs = int(self._seq_length or 1), int(self.parameters['batchsize'])
+        nrow = l if (l > 1 and 'sv' not in path) else max(int(math.sqrt(bs)), 1)
+        if 'modeling' in self.parameters['problem_type'] and 'sv' not in path:
+            take = min(bs * l, n_images)
+        else:
+            take = min(bs, n_images)
+        image_grid = ops.backend_op("image_grid")
+        host = {}
+        for key, (v, logits) in kept.items():
+            srcs = [self._grid_source(key, t) for t in (v if isinstance(v, (list, tuple)) else (v,))]
+            grid = image_grid(srcs, take, nrow, logits)
+            buf = self._grid_host.get(key)
+            if buf is None or buf.shape != grid.shape:
+                buf = self._grid_host[key] = torch.empty(grid.shape, dtype=torch.uint8, pin_memory=grid.is_cuda)
+            buf.copy_(grid, non_blocking=True)
+            host[key] = buf
+        if self._device.type == 'cuda':
+            torch.cuda.current_stream().synchronize()
+        Path(self._plot_dir).mkdir(parents=True, exist_ok=True)
+        self._image_grids = {}
+        for key, buf in host.items():
+            _write_png(os.path.join(self._plot_dir, '%s_epoch_%d.png' % (key.replace('/', '_'), epoch)), buf)
+            self._image_grids[key] = buf.clone()
+
+    def image_grids(self):
+        """``{key: uint8 CPU tensor [Hg, Wg, 3]}``: the grids of the latest logged epoch (``{}`` before the first, or with
+        --log-images off)."""
+        return dict(self._image_grids)
 
     _rows_kl_mode = 0        # KL of the reduce=False rows: 0 the reference's (batch total in every row); train_batch may set 1
 
@@ -628,6 +742,10 @@ class Problem:
     @property
     def checkpoint_dir(self):
         return self._checkpoint_dir
+
+    @property
+    def plot_dir(self):
+        return self._plot_dir
 
     @property
     def num_epochs(self):
@@ -857,6 +975,11 @@ class Reconstruction(Problem):
             recon = [v_joint, t_joint]
         return {'recon_x': recon, 'means': means, 'log_var': log_var, 'perf_measure': perf}, loss
 
+    def _log_batch_images(self, split, inputs, targets, outputs):
+        """problems.py:561-574: the inputs and the reconstruction logits of the batch."""
+        self._img_logger_dict['Input_img/' + split] = (inputs, False)
+        self._img_logger_dict['Output_img/' + split] = (self._recon_images(outputs), True)
+
     def _sample(self, n=50):
         """Decoded draws from the prior; a conditional model gets a random condition per draw (problems.py:550-555): a class index
         for a categorical model, uniform [0, 1) values for a real-valued one."""
@@ -969,6 +1092,12 @@ class SeqModeling(Reconstruction):
             pose_in = avail = pose_t = mask = shock = None
         return ({'model_input': mi, 'input_object_pose': pose_in, 'input_available_modals': avail, 'shock': shock},
                 {'target_output': to, 'target_object_pose': pose_t, 'loss_mask': mask})
+
+    def _log_batch_images(self, split, inputs, targets, outputs):
+        """problems.py:718-739: the inputs, the reconstruction logits and the targets of the batch."""
+        self._img_logger_dict['Input_img/' + split] = (inputs['model_input'], False)
+        self._img_logger_dict['Output_img/' + split] = (self._recon_images(outputs), True)
+        self._img_logger_dict['Target_img/' + split] = (targets['target_output'], False)
 
     def _target_available(self, has):
         """Every target is the dataset's final frame of its sequence, which counts as present; so does the pose target."""
